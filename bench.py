@@ -10,10 +10,17 @@ bit-identical to one launch per block, tests/test_gpu_properties.py) -- four not
 (t_restart at block 0, t_release at block 32 of every 64).  `value` counts every block of every step.  (Four launches to
 a step so that the driver's 20 timed steps last ~70 ms, not 17.)
 
-Beside `value` the line carries: `host_output` -- the same path when the blocks are handed to the HOST, including
+A plain run measures the headline alone: it sets up, warms up, times the steps and prints the line.  With --full the
+line also carries: `host_output` -- the same path when the blocks are handed to the HOST, including
 `per_block_value`, the rate of the call the reference actually makes (UGen::process_block once per block through
-knh_bank_process_block, Task::run in knaster_graph/src/task.rs:25-31), for C3 and C1; and `configs` -- short legs of the
-other BASELINE.json configurations (C1, C2, C5; C4 is `c4_strong`), each kernel-only and wall.
+knh_bank_process_block, Task::run in knaster_graph/src/task.rs:25-31), for C3 and C1; `configs` -- short legs of the
+other BASELINE.json configurations (C1, C2, C5; C4 is `c4_strong`), each kernel-only and wall; `large_banks`; and the CPU
+baselines.
+
+--dump-outputs DIR writes what the timed path handed its caller in the last timed step -- the mixed blocks of that
+step's launches, [LAUNCHES_PER_STEP][BLOCKS_PER_LAUNCH][channels][block_size] -- to DIR/mix_blocks.npy (float32, or
+float64 for f64 banks).  The voices' history up to then depends on the arguments alone (the clock is brought up on a
+bank of its own), so two builds run with the same arguments can be compared output for output.
 
 Several GPUs: one process per GPU; each rank creates its share of the bank with knh_bank_create_rank (contiguous
 voice ranges, global voice indices) and the LIBRARY sums each launch's stereo blocks to rank 0 with RCCL's ncclReduce
@@ -21,8 +28,8 @@ on a stream of its own, overlapping the next launch (knaster_amd/csrc/comm.hip, 
 used for nothing on the data path: it hands the communicator id to the ranks, and provides the barrier and the
 max-over-ranks of the timing.
 
-The same line also carries BASELINE.json configs[3] ("C4": 65536 voices in all, f64, STRONG scaling over the ranks)
-as `c4_strong` (skip with --no-c4; `--config C4` makes it the headline instead).
+With --full the same line also carries BASELINE.json configs[3] ("C4": 65536 voices in all, f64, STRONG scaling over the
+ranks) as `c4_strong` (skip with --no-c4; `--config C4` makes it the headline instead).
 
 Launch: `python bench.py` (N=1) or
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`.
@@ -94,10 +101,14 @@ def parse():
     ap.add_argument("--c4-voices", type=int, default=65536, help="C4: voices in all (strong scaling)")
     ap.add_argument("--block-size", type=int, default=512)
     ap.add_argument("--allow-fma", action="store_true", help="non-bit-exact FMA kernels (reported as such)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-c4", action="store_true", help="skip the secondary C4 strong-scaling measurement")
-    ap.add_argument("--no-configs", action="store_true", help="skip the short C1 / C2 / C5 legs and the per-block boundary legs")
+    ap.add_argument("--full", action="store_true", help="beside the headline: the host-boundary legs, C4 strong scaling, the other "
+                    "configurations, the large banks and the CPU baselines (a plain run measures the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-c4", action="store_true", help="with --full: skip the secondary C4 strong-scaling measurement")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the short C1 / C2 / C5 legs and the per-block boundary legs")
     ap.add_argument("--cpu-baseline-blocks", type=int, default=0, help="0 = auto (about 10-20 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the mixed blocks of the last timed step to DIR/mix_blocks.npy")
     return ap.parse_args()
 
 
@@ -210,8 +221,9 @@ class Env:
         return float(t.item())
 
 
-def measure(env: Env, args, name: str, total_voices: int, bs: int, steps: int, warmup: int):
-    """One workload on the job's ranks: returns a dict of raw measurements (every rank), or exits on failure."""
+def measure(env: Env, args, name: str, total_voices: int, bs: int, steps: int, warmup: int, dump_dir: str | None = None):
+    """One workload on the job's ranks: returns a dict of raw measurements (every rank), or exits on failure.  dump_dir: where
+    rank 0 writes the last timed step's mixed blocks (mix_blocks.npy)."""
     import knaster_amd
     from knaster_amd import _lib as L
     from knaster_amd import configs
@@ -220,9 +232,10 @@ def measure(env: Env, args, name: str, total_voices: int, bs: int, steps: int, w
     w_all = configs.config(name, n_voices=total_voices, block_size=bs)
     lo, cnt = knaster_amd.shard_voice_range(total_voices, env.rank, env.world)
     tdtype = torch.float64 if w_all.sample_type == L.F64 else torch.float32
-    # the mixed stereo blocks of a launch: [BLOCKS_PER_LAUNCH][channels][block_size], resident in HBM; two of them, used
-    # alternately, so that the library's reduce of one launch overlaps the next launch's kernels
-    rings = [torch.zeros((BLOCKS_PER_LAUNCH, w_all.out_channels, bs), dtype=tdtype, device=env.dev) for _ in range(2)]
+    # the mixed stereo blocks of a launch: [BLOCKS_PER_LAUNCH][channels][block_size], resident in HBM; one per launch of a
+    # step, used in turn, so that the library's reduce of one launch overlaps the next launch's kernels and the last step's
+    # blocks are all still there after it (--dump-outputs)
+    rings = [torch.zeros((BLOCKS_PER_LAUNCH, w_all.out_channels, bs), dtype=tdtype, device=env.dev) for _ in range(LAUNCHES_PER_STEP)]
 
     def make_bank(collective: str):
         kwargs = dict(rank=env.rank, world=env.world)
@@ -271,10 +284,10 @@ def measure(env: Env, args, name: str, total_voices: int, bs: int, steps: int, w
 
     def run_launches(n: int):
         for _ in range(n):
-            half = launch_no[0] & 1
+            ring = rings[launch_no[0] % len(rings)]
             launch_no[0] += 1
             schedule()
-            bank.process_blocks_device(BLOCKS_PER_LAUNCH, rings[half].data_ptr(), env.stream.cuda_stream)
+            bank.process_blocks_device(BLOCKS_PER_LAUNCH, ring.data_ptr(), env.stream.cuda_stream)
 
     def run_steps(n: int):
         run_launches(n * LAUNCHES_PER_STEP)
@@ -283,15 +296,36 @@ def measure(env: Env, args, name: str, total_voices: int, bs: int, steps: int, w
         bank.synchronize()  # this rank's kernels and reduces
         env.barrier()
 
-    # untimed: bring the shader clock up (a kernel of under a few milliseconds right after an idle period runs ~25 % slow)
-    # (every rank runs the same number of launches -- each launch holds a collective: the ranks agree after every pair)
+    # untimed: the path's first-use allocations (both of the alternating record / list buffers)
+    run_launches(2)
+    bank.synchronize()
+    # untimed: bring the shader clock up (a kernel of under a few milliseconds right after an idle period runs ~25 % slow).
+    # How many launches that takes depends on the clock, so they run on a bank of their own: this rank's share of the same
+    # workload, with no collective; the measured bank's voices see the same launches in every run with the same arguments.
+    # (every rank runs the same number of rounds: the ranks agree after every pair of launches)
+    w_pre = configs.config(name, n_voices=cnt, block_size=bs) if cnt else None
+    pre = None
+    if w_pre is not None:
+        pre = knaster_amd.VoiceBank(w_pre.stages, cnt, w_pre.sample_type, w_pre.out_channels, L.MIX_TREE, env.local_rank, args.allow_fma)
+        for s, a in w_pre.ctor.items():
+            pre.set_ctor_args(s, a)
+        pre.init(configs.SAMPLE_RATE, bs)
+        v_pre = np.arange(cnt, dtype=np.uint32)
+        pre_restart = pre.prepare_many(v_pre, w_pre.restart[0], w_pre.restart[1], L.VALUE_TRIGGER)
+        pre_release = pre.prepare_many(v_pre, w_pre.release[0], w_pre.release[1], L.VALUE_TRIGGER)
     t_pre, n_pre = time.perf_counter(), 0
     while True:
-        run_launches(2)
-        bank.synchronize()
+        if pre is not None:
+            for _ in range(2):
+                pre.param_apply_prepared(pre_restart, 0)
+                pre.param_apply_prepared(pre_release, BLOCKS_PER_LAUNCH // 2)
+                pre.process_blocks_device(BLOCKS_PER_LAUNCH, 0, env.stream.cuda_stream)
+            pre.synchronize()
         n_pre += 2
         if env.max_over_ranks((time.perf_counter() - t_pre) * 1e3) >= PREWARM_MS:
             break
+    if pre is not None:
+        pre.close()
     run_steps(warmup)
     fence()
     bank.timing_reset(True)
@@ -302,15 +336,20 @@ def measure(env: Env, args, name: str, total_voices: int, bs: int, steps: int, w
     kernel_ms, launches = bank.timing_read()
     reduce_ms, reduces = bank.collective_timing_read()
     bank.timing_reset(False)
+    if dump_dir and env.rank == 0 and steps > 0:
+        # the last step's launches in the order they ran (rank 0's rings hold the sum over the ranks)
+        last = [rings[n % len(rings)] for n in range(launch_no[0] - LAUNCHES_PER_STEP, launch_no[0])]
+        os.makedirs(dump_dir, exist_ok=True)
+        np.save(os.path.join(dump_dir, "mix_blocks.npy"), torch.stack(last).cpu().numpy())
     elapsed = env.max_over_ranks(elapsed)
     kernel_avg_ms = env.max_over_ranks(kernel_ms / max(launches, 1))
     # every rank's own two numbers, so that a multi-GPU run explains itself: voice-kernel time and reduce time per launch
     per_rank = env.gather_list([kernel_ms / max(launches, 1), reduce_ms / max(reduces, 1) if reduces else 0.0, cnt])
 
-    # The same path when the boundary hands the blocks to the HOST (knh_bank_process_blocks: D2H copy of
+    # --full: the same path when the boundary hands the blocks to the HOST (knh_bank_process_blocks: D2H copy of
     # every launch's stereo blocks over PCIe + stream sync).  Reported beside `value`, never as `value`.
-    host_rate = None
-    if env.world == 1:
+    host_rate = host_rate_blocking = None
+    if env.world == 1 and args.full:
         n_host = 32
         schedule()
         bank.process_blocks(BLOCKS_PER_LAUNCH)
@@ -336,7 +375,7 @@ def measure(env: Env, args, name: str, total_voices: int, bs: int, steps: int, w
     peak = float(max(rings[0].abs().max().item(), rings[1].abs().max().item()))
     rd, wr = bank.algorithmic_bytes_per_voice_block()
     out = dict(workload=w_all, ugens=ugens, elapsed=elapsed, kernel_avg_ms=kernel_avg_ms, launches=launches, host_rate=host_rate,
-               host_rate_blocking=host_rate_blocking if env.world == 1 else None,
+               host_rate_blocking=host_rate_blocking,
                sane=sane, peak=peak, bytes_per_voice_block=rd + wr, n_pre=n_pre, voices_rank0=cnt if env.rank == 0 else None,
                ranks_seen=bank.ranks(), total_voices=total_voices, steps=steps, collective=collective, per_rank=per_rank)
     bank.close()
@@ -496,10 +535,10 @@ def main():
     bs, world = args.block_size, env.world
     headline = args.config
     if headline == "C3":
-        m = measure(env, args, "C3", args.voices_per_gpu * world, bs, args.steps, args.warmup)
-        secondary = None if args.no_c4 else measure(env, args, "C4", args.c4_voices, bs, max(4, args.steps // 2), max(1, args.warmup // 2))
+        m = measure(env, args, "C3", args.voices_per_gpu * world, bs, args.steps, args.warmup, args.dump_outputs)
+        secondary = None if args.no_c4 or not args.full else measure(env, args, "C4", args.c4_voices, bs, max(4, args.steps // 2), max(1, args.warmup // 2))
     else:
-        m = measure(env, args, "C4", args.c4_voices, bs, args.steps, args.warmup)
+        m = measure(env, args, "C4", args.c4_voices, bs, args.steps, args.warmup, args.dump_outputs)
         secondary = None
     if env.rank == 0:
         w_all, ugens, total_voices = m["workload"], m["ugens"], m["total_voices"]
@@ -538,7 +577,8 @@ def main():
                 "blocks_timed": total_blocks,
                 "residency": "value is measured with voice state, events and the mixed stereo blocks resident in HBM; the "
                              "PCIe-inclusive rate of the host-pointer boundary (knh_bank_process_blocks) is host_output",
-                "prewarm": f"{m['n_pre']} untimed launches (>= {PREWARM_MS:.0f} ms) before the warm-up steps, to bring the clock up",
+                "prewarm": f"{m['n_pre']} untimed launches (>= {PREWARM_MS:.0f} ms) of a bank of the same shape before the warm-up "
+                           f"steps, to bring the clock up",
                 "arithmetic": "fma" if args.allow_fma else "exact (bit-identical per voice to the CPU oracle)",
                 "parallelism": f"voices sharded over {world} rank(s), one process per GPU (knh_bank_create_rank); "
                                f"{BLOCKS_PER_LAUNCH} blocks per launch; the library's ncclReduce of the stereo blocks to rank 0 once per "
@@ -593,7 +633,7 @@ def main():
                         "mixer wavefronts on the other three SIMDs are all faster and hide behind it "
                         "(profiles/r03_pipe_wave_busy_cycles.txt, _filter_alone.txt)",
             }
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             pb = [per_block_boundary("C3"), per_block_boundary("C1")]
             if line["host_output"] is not None:
                 line["host_output"]["per_block_value"] = pb[0]["per_block_value"]
@@ -642,7 +682,7 @@ def main():
                 "per_rank": {"kernel_ms_per_launch": [r[0] for r in s["per_rank"]], "reduce_ms_per_launch": [r[1] for r in s["per_rank"]],
                              "voices": [r[2] for r in s["per_rank"]]},
             }
-        if not args.no_cpu_baseline and world == 1 and headline == "C3":
+        if args.full and not args.no_cpu_baseline and world == 1 and headline == "C3":
             try:
                 cores = len(os.sched_getaffinity(0))
             except AttributeError:

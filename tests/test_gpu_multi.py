@@ -274,11 +274,12 @@ def test_two_ranks_two_processes_one_gpu(knh, tmp_path):
 def test_bench_two_ranks_rehearsal(knh):
     """bench.py as the driver launches it for N = 2 (torch.distributed.run, one rank per process), both ranks on this one GPU
     with KNH_BENCH_REHEARSE=1 (the library's reduce goes through gloo): the whole N > 1 control flow -- per-rank banks,
-    global voice indices, a collective per launch, the agreed pre-warm, max over ranks -- ends in one JSON line."""
+    global voice indices, a collective per launch, the agreed pre-warm, max over ranks -- ends in one JSON line (--full: with
+    the C4 strong-scaling leg)."""
     env = dict(os.environ, KNH_BENCH_REHEARSE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--voices-per-gpu", "2048", "--c4-voices", "4096"]
+           "--voices-per-gpu", "2048", "--c4-voices", "4096", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

@@ -7,9 +7,9 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="$ROOT/gpurun_out/profiles_new"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5"   # the driver's command (one step = four 64-block launches)
+BENCH="python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --full"   # the driver's command with every leg (one step = four 64-block launches)
 
-echo "== bench (plain)"; (cd "$ROOT" && timeout -k 10 300 python3 bench.py > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err") || exit 1
+echo "== bench (every leg)"; (cd "$ROOT" && timeout -k 10 300 python3 bench.py --full > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err") || exit 1
 echo "== kernel trace + stats"
 rm -rf "$OUT/stats"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- $BENCH > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err" || { tail -5 "$OUT/stats.err"; exit 1; }
@@ -23,12 +23,12 @@ rm -rf "$OUT/stats_h"
 for C in FETCH_SIZE WRITE_SIZE; do
   echo "== pmc $C"
   rm -rf "$OUT/pmc_$C"
-  timeout -k 10 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$OUT/pmc_$C" -o bench -- python3 "$ROOT/bench.py" --gpus 1 --steps 4 --warmup 1 --no-cpu-baseline --no-c4 --no-configs > "$OUT/pmc_$C.json" 2> "$OUT/pmc_$C.err" || { tail -5 "$OUT/pmc_$C.err"; exit 1; }
+  timeout -k 10 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$OUT/pmc_$C" -o bench -- python3 "$ROOT/bench.py" --gpus 1 --steps 4 --warmup 1 --full --no-cpu-baseline --no-c4 --no-configs > "$OUT/pmc_$C.json" 2> "$OUT/pmc_$C.err" || { tail -5 "$OUT/pmc_$C.err"; exit 1; }
   find "$OUT/pmc_$C" -name "*counter_collection.csv" -exec cp {} "$OUT/pmc_$C.csv" \;
 done
 echo "== pmc SQ"
 rm -rf "$OUT/pmc_SQ"
-timeout -k 10 400 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_LDS --kernel-trace --output-format csv -d "$OUT/pmc_SQ" -o bench -- python3 "$ROOT/bench.py" --gpus 1 --steps 4 --warmup 1 --no-cpu-baseline --no-c4 --no-configs > "$OUT/pmc_SQ.json" 2> "$OUT/pmc_SQ.err" || { tail -5 "$OUT/pmc_SQ.err"; exit 1; }
+timeout -k 10 400 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_LDS --kernel-trace --output-format csv -d "$OUT/pmc_SQ" -o bench -- python3 "$ROOT/bench.py" --gpus 1 --steps 4 --warmup 1 --full --no-cpu-baseline --no-c4 --no-configs > "$OUT/pmc_SQ.json" 2> "$OUT/pmc_SQ.err" || { tail -5 "$OUT/pmc_SQ.err"; exit 1; }
 find "$OUT/pmc_SQ" -name "*counter_collection.csv" -exec cp {} "$OUT/pmc_SQ.csv" \;
 echo "== all configs"; (cd "$ROOT" && timeout -k 10 400 python3 tools/bench_configs.py > "$OUT/all_configs.jsonl" 2> "$OUT/all_configs.err") || tail -3 "$OUT/all_configs.err"
 echo "== per-block boundary (C++ twin of the Rust shim): the resident kernel, and a launch per call (KNH_RESIDENT=0)"

@@ -30,7 +30,7 @@ if "SQ_INSTS_VALU" in v:
     v["wait_inst_any_over_wave_cycles"] = v["SQ_WAIT_INST_ANY"] / v["SQ_WAVE_CYCLES"]
     v["wait_any_over_wave_cycles"] = v["SQ_WAIT_ANY"] / v["SQ_WAVE_CYCLES"]
 out["command"] = ("tools/make_profiles.sh: rocprofv3 --pmc " + " ".join(COUNTERS) + " --kernel-trace --output-format csv -- python3 bench.py "
-                  "--gpus 1 --steps 4 --warmup 1 --no-cpu-baseline --no-c4 --no-configs (per launch of 64 blocks x 16 384 voices; later half of the launches); tools/sq_summary.py")
+                  "--gpus 1 --steps 4 --warmup 1 --full --no-cpu-baseline --no-c4 --no-configs (per launch of 64 blocks x 16 384 voices; later half of the launches); tools/sq_summary.py")
 out["notes"] = [
     "SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles summed over wavefronts (MI355X_MICROARCH.md, cycle constants)",
     "1 024 wavefronts per launch: 256 workgroups x (oscillator, filter, envelope, mixer); the ratios are averages over the four roles -- "
