@@ -110,7 +110,8 @@ pub const KNH_STAGE_MATH_MUL: u16 = 35;
 pub const KNH_STAGE_MATH_DIV: u16 = 36;
 pub const KNH_STAGE_MATH_POW: u16 = 37;
 pub const KNH_STAGE_INPUT: u16 = 38;
-pub const KNH_STAGE_KIND_COUNT: u16 = 39;
+pub const KNH_STAGE_GALACTIC: u16 = 39;
+pub const KNH_STAGE_KIND_COUNT: u16 = 40;
 
 // knh_svf_type = SvfFilterType, knaster_core_dsp/src/ugens/svf.rs:19-39
 pub const KNH_SVF_LOW: u32 = 0;

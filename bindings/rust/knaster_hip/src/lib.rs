@@ -75,6 +75,13 @@ pub type Stage = knh_stage_desc;
 pub fn stage(kind: u16) -> Stage {
     Stage { kind, flags: 0, delayed_changes_per_block: 0, ar_param: 0, input: 0, input2: 0 }
 }
+/// The `Galactic` reverb stage (`KNH_STAGE_GALACTIC`: last stage of the chain, bank with two output channels) and its seven
+/// constructor arguments for the `ctor` table of `VoiceBank::new`: `Galactic::new(replace, detune, brightness, bigness, wet)`
+/// (knaster_airwindows/src/galactic.rs:145-170) plus the states of its two xorshift32 dither streams, which the reference draws
+/// from `fastrand` and this engine takes from the caller (non-zero).
+pub fn galactic(replace: f64, detune: f64, brightness: f64, bigness: f64, wet: f64, fpd_l: u32, fpd_r: u32) -> (Stage, [f64; 7]) {
+    (stage(KNH_STAGE_GALACTIC), [replace, detune, brightness, bigness, wet, fpd_l as f64, fpd_r as f64])
+}
 pub trait StageExt {
     /// `.precise_timing::<N>()` on the stage's node (wrappers_core.rs:106-111)
     fn precise_timing(self, max_changes_per_block: u16) -> Self;

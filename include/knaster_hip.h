@@ -158,6 +158,27 @@ typedef enum knh_value_kind {
  *     (another node's output feeding every voice's filter; or, with KNH_STAGE_FLAG_AR_FREQ on a following SIN_WT behind
  *     e.g. a MUL_CONST, the buffer UGen::set_ar_param_buffer hands over, ugen.rs:309-329).  knh_bank_desc.in_channels says
  *     how many there are; the samples of the next launch come from knh_bank_set_input[_device].  No parameters.
+ * KNH_STAGE_GALACTIC        (voice).out([0, 0]) >> g.push(Galactic::new(replace, detune, brightness, bigness, wet))
+ *                                                               knaster_airwindows/src/galactic.rs:14-400   1    replace, detune, brightness, bigness, wet, fpd_l, fpd_r
+ *     the stereo reverb (Inputs = U2, Outputs = U2), one per voice: both inputs are the voice's running mono signal, the two
+ *     outputs go to graph out 0 and out 1.  Must be the LAST stage, the bank must have out_channels = 2, and the chain holds
+ *     no other delay-ring stage and no Pan2; delayed_changes_per_block = 0 and ar_param = 0 (its parameters take effect at
+ *     the next process call, as in the reference).  Per-voice output is [2][n_voices][block_size] and the mix planes are the
+ *     two channels, as for a Pan2 chain; both mix modes.  A bank with this stage is one voice range on one device (no host
+ *     sharding, no multi-GPU form) and has a launch of its own (no resident form).
+ *     params: 0 replace, 1 detune, 2 brightness, 3 bigness, 4 wet (floats, hinted 0..1).  bigness outside [0, 1] (NaN
+ *     included) is KNH_ERR_OUT_OF_RANGE and changes nothing (the reference would panic in to_usize().unwrap() or take % 0).
+ *     TWO DECISIONS.  (1) fpd_l, fpd_r, the states of the two xorshift32 dither streams, are CONSTRUCTOR ARGUMENTS here
+ *     (integers 1 .. 2^32 - 1, exact in a double; 0 is refused, xorshift32 would stay at 0): the reference draws them in
+ *     Galactic::new from fastrand::Rng::with_seed(next_randomness_seed()).u32(16386..u32::MAX) (galactic.rs:147-154), a
+ *     process-global seed sequence this library does not restate.  (2) the output dither scales by 2^(exp + 62) with exp
+ *     from the reference's own frexp (galactic.rs:390-400): floor(log2|s|) + 1 in f32, cast to u32 (<= 0 -> 0), and
+ *     2_u64.pow(exp + 62) overflows for exp >= 2 (|s| >= 2): a debug build panics, a release build wraps to 0.  This
+ *     library takes the release behaviour (no dither at |s| >= 2) and reads the exponent from the float's bits instead
+ *     of calling log2f: it differs from the reference only where its log2 rounds across an integer (|s| a hair below a
+ *     power of two).  Rings: 24 of int(t / 44100 * sample_rate) samples (t = 6480, 3660, 1720, 680, 9700, 6000, 2320, 940,
+ *     15220, 8460, 4540, 3200) and two of 256 per voice, in device memory: about 550 KB per f32 voice at 48 kHz;
+ *     knh_bank_init fails with KNH_ERR_DEVICE if they do not fit.
  * KNH_STAGE_PAN2            x >> g.push(Pan2::new(pan))         pan.rs:12-37         1    pan (-1 .. 1)
  *     mono -> stereo with the cos/sin pan law: the voice's signal times left_gain goes to graph out 0, times
  *     right_gain to graph out 1 (`(voice >> pan).to_graph_out()`, knaster/examples/many_sines.rs:51-63).  Must be the
@@ -210,7 +231,8 @@ typedef enum knh_stage_kind {
   KNH_STAGE_MATH_DIV = 36,
   KNH_STAGE_MATH_POW = 37,
   KNH_STAGE_INPUT = 38,
-  KNH_STAGE_KIND_COUNT = 39
+  KNH_STAGE_GALACTIC = 39,
+  KNH_STAGE_KIND_COUNT = 40
 } knh_stage_kind;
 
 /* SvfFilterType: knaster_core_dsp/src/ugens/svf.rs:19-39 (out-of-range -> Low,
@@ -288,7 +310,7 @@ typedef struct knh_bank_desc {
   const knh_stage_desc* stages;
   /* 1: mono signal -> graph out 0.  2: `.out([0,0]).to_graph_out()`, the same
    * mono signal additively to out 0 and out 1 (graph_edit.rs:280-292,363-369) -- or, for a
-   * chain that ends in KNH_STAGE_PAN2, the Pan2's left and right outputs to out 0 and out 1. */
+   * chain that ends in KNH_STAGE_PAN2 or KNH_STAGE_GALACTIC, that stage's left and right outputs to out 0 and out 1. */
   uint32_t out_channels;
   uint32_t mix_mode;     /* knh_mix_mode */
   int32_t device;        /* HIP device ordinal, -1 = current device */

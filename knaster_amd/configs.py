@@ -78,7 +78,8 @@ def config(name: str, n_voices: int | None = None, block_size: int | None = None
     name = name.upper()
     defaults = {"C1": (1, 64, L.F32), "C2": (1024, 256, L.F32), "C3": (16384, 512, L.F32),
                 "C4": (65536, 512, L.F64), "C5": (4096, 128, L.F32),
-                "D3": (16384, 512, L.F32), "B3": (16384, 512, L.F32), "M1": (600, 64, L.F32), "P3": (16384, 512, L.F32)}
+                "D3": (16384, 512, L.F32), "B3": (16384, 512, L.F32), "M1": (600, 64, L.F32), "P3": (16384, 512, L.F32),
+                "G1": (4096, 512, L.F32)}
     nv, bs, st = defaults[name]
     nv = n_voices or nv
     bs = block_size or bs
@@ -108,6 +109,15 @@ def config(name: str, n_voices: int | None = None, block_size: int | None = None
         u = (p["q"] - 0.5) / 3.5  # three of the uniform draws, mapped onto the example's ranges
         w.ctor = {0: col(3000.0 + 7000.0 * (p["cutoff"] - 200.0) / 7800.0), 1: col(0.01 + 0.005 * u),
                   2: np.tile([0.01, 0.1], (nv, 1)), 3: col(-1.0 + 2.0 * (p["fm_ratio"] - 1.0) / 3.0)}
+        w.restart = (2, 2)
+    elif name == "G1":  # not a BASELINE.json config: a plucked sine into a Galactic reverb per voice (24 rings in HBM each)
+        w = Workload(name, [Stage(L.STAGE_SIN_WT), Stage(L.STAGE_WR_MUL), Stage(L.STAGE_MUL_ENV_AR), Stage(L.STAGE_GALACTIC)], nv, bs, st,
+                     description="SinWt.wr_mul(0.25) -> * EnvAr -> Galactic(replace, detune, brightness, bigness, wet)")
+        unit = lambda a, lo, hi: np.clip((a - lo) / (hi - lo), 0.0, 1.0)  # the draws back on 0 .. 1
+        seeds = xorshift32_stream(SEED ^ 0x5EED, 2 * nv).astype(np.float64).reshape(nv, 2)  # never 0
+        gal = np.stack([0.5 + 0.5 * unit(p["cutoff"], 200.0, 8000.0), unit(p["q"], 0.5, 4.0), unit(p["attack"], 0.002, 0.022),
+                        unit(p["release"], 0.05, 0.3), unit(p["fm_ratio"], 1.0, 4.0), seeds[:, 0], seeds[:, 1]], axis=1)
+        w.ctor = {0: col(p["freq"]), 1: col(np.full(nv, 0.25)), 2: np.tile([0.001, 0.002], (nv, 1)), 3: gal}
         w.restart = (2, 2)
     elif name == "P3":  # not a BASELINE.json config: the C3 voice panned (Pan2 behind the envelope)
         w = Workload(name, [Stage(L.STAGE_SIN_WT), Stage(L.STAGE_WR_MUL), Stage(L.STAGE_SVF),

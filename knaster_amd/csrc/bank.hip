@@ -127,6 +127,7 @@ knh_bank* make_bank(const knh_bank_desc& d, const knh::KernelEntry* entry, const
 
 #include "host_shards.hpp"
 #include "rank_bank.hpp"
+#include "galactic_bank.hpp"
 
 namespace {
 // K host threads: the bank is cut into K voice ranges of whole 64-voice groups (fewer when there are fewer groups).
@@ -186,6 +187,34 @@ knh_bank* make_rank_bank(const knh_bank_desc& d, const knh::KernelEntry* entry, 
   b->n_slots = proto->n_slots;
   b->n_params_total = proto->n_params_total;
   if (count) b->local = std::move(proto);
+  b->desc.stages = nullptr;
+  return b.release();
+}
+}  // namespace
+
+namespace {
+inline bool ends_in_galactic(const knh_bank_desc& d) { return d.n_stages > 0 && d.stages[d.n_stages - 1].kind == KNH_STAGE_GALACTIC; }
+// A chain that ends in KNH_STAGE_GALACTIC: the chain before it as an ordinary mono bank, the reverb behind it (galactic_bank.hpp).
+template <typename F>
+knh_bank* make_galactic(const knh_bank_desc& d, const std::string& inner_sig) {
+  std::unique_ptr<GalacticBank<F>> b(new GalacticBank<F>());
+  knh_bank_desc di = d;
+  di.n_stages = d.n_stages - 1;
+  di.out_channels = 1;
+  di.mix_mode = KNH_MIX_TREE;
+  b->inner.reset(static_cast<Bank<F>*>(make_bank<F>(di, knh::find_kernel(inner_sig.c_str()), inner_sig)));
+  b->desc = d;
+  b->nv = d.n_voices;
+  b->gstage = d.n_stages - 1;
+  b->stages = b->inner->stages;
+  const KindInfo& k = kKinds[KNH_STAGE_GALACTIC];
+  b->stages.push_back(StageInfo{KNH_STAGE_GALACTIC, 0, 0, b->inner->n_slots, k.n_slots, k.n_params, k.n_ctor, b->inner->n_params_total, 0, 0, 0});
+  b->n_slots = b->inner->n_slots;
+  b->n_params_total = b->inner->n_params_total + k.n_params;
+  b->gctor.assign(static_cast<size_t>(d.n_voices) * 7, 0.0);
+  b->par.assign(static_cast<size_t>(d.n_voices) * 5, F(0));
+  b->drifted.assign(d.n_voices, 0);
+  b->h_params.resize(d.n_voices);
   b->desc.stages = nullptr;
   return b.release();
 }
@@ -287,6 +316,13 @@ static int32_t check_desc(const knh_bank_desc* desc, knh_bank** out_bank, std::s
     int rc = build_signature(desc->stages, desc->n_stages, sig, &why);
     if (rc != KNH_OK) { g_create_error = why; return rc; }
     if (desc->stages[desc->n_stages - 1].kind == KNH_STAGE_PAN2 && desc->out_channels != 2) { g_create_error = "a chain ending in Pan2 has two output channels (out_channels = 2)"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (ends_in_galactic(*desc)) {
+      if (desc->out_channels != 2) { g_create_error = "a chain ending in Galactic has two output channels (out_channels = 2)"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (desc->n_stages < 2) { g_create_error = "stage needs a preceding signal"; return KNH_ERR_INVALID_ARGUMENT; }
+      // the signature the kernels are looked up by is that of the chain BEFORE the reverb (galactic_bank.hpp)
+      rc = build_signature(desc->stages, desc->n_stages - 1, sig, &why);
+      if (rc != KNH_OK) { g_create_error = why; return rc; }
+    }
     return KNH_OK;
   });
 }
@@ -296,6 +332,7 @@ int32_t knh_bank_create_multi_device(const knh_bank_desc* desc, const int32_t* d
     std::string sig;
     int rc = check_desc(desc, out_bank, &sig);
     if (rc != KNH_OK) return rc;
+    if (ends_in_galactic(*desc)) { g_create_error = "a chain that ends in Galactic is one voice range on one device"; return KNH_ERR_UNSUPPORTED_CHAIN; }
     if (!devices || n_devices == 0 || n_devices > 64) { g_create_error = "devices: 1 to 64 device ordinals"; return KNH_ERR_INVALID_ARGUMENT; }
     if (desc->mix_mode != KNH_MIX_TREE) { g_create_error = "a bank sharded over several GPUs mixes with KNH_MIX_TREE (the sum over GPUs re-associates)"; return KNH_ERR_INVALID_ARGUMENT; }
     int visible = 0;
@@ -322,6 +359,7 @@ static int32_t create_rank_bank(const knh_bank_desc* desc, uint32_t rank, uint32
     std::string sig;
     int rc = check_desc(desc, out_bank, &sig);
     if (rc != KNH_OK) return rc;
+    if (ends_in_galactic(*desc)) { g_create_error = "a chain that ends in Galactic is one voice range on one device"; return KNH_ERR_UNSUPPORTED_CHAIN; }
     if (world == 0 || rank >= world) { g_create_error = "rank must be below world"; return KNH_ERR_INVALID_ARGUMENT; }
     if (world > 1 && !comm_id && !reduce) { g_create_error = "more than one rank needs a communicator id (knh_comm_unique_id) or a reduce function"; return KNH_ERR_INVALID_ARGUMENT; }
     if (desc->mix_mode != KNH_MIX_TREE) { g_create_error = "a bank sharded over several GPUs mixes with KNH_MIX_TREE (the sum over GPUs re-associates)"; return KNH_ERR_INVALID_ARGUMENT; }
@@ -350,6 +388,10 @@ static int32_t create_bank(const knh_bank_desc* desc, uint32_t host_threads, knh
     int rc = check_desc(desc, out_bank, &sig);
     if (rc != KNH_OK) return rc;
     if (host_threads > 64) { g_create_error = "host_threads must be at most 64"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (ends_in_galactic(*desc)) {  // (one range whatever host_threads says: the reverb's launch is per bank)
+      *out_bank = desc->sample_type == KNH_F64 ? make_galactic<double>(*desc, sig) : make_galactic<float>(*desc, sig);
+      return KNH_OK;
+    }
     // a chain without a pre-built kernel is fused at knh_bank_init time (hiprtc); entry == nullptr marks it
     const knh::KernelEntry* entry = knh::find_kernel(sig.c_str());
     // the reference's exact mix order (KNH_MIX_LEFT_FOLD) and banks of a single voice group keep one range

@@ -37,6 +37,14 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     if (st[i].kind == KNH_STAGE_MUL_ENVELOPE && sig->find('V') != std::string::npos) { *why = "at most one Envelope stage per chain"; return KNH_ERR_INVALID_ARGUMENT; }
     if (st[i].kind == KNH_STAGE_PAN2 && i + 1 != n) { *why = "Pan2 ends the chain: it must be the last stage"; return KNH_ERR_INVALID_ARGUMENT; }
     if (st[i].kind == KNH_STAGE_PAN2 && st[i].delayed_changes_per_block > 0) { *why = "Pan2 cannot be wrapped in WrPreciseTiming here (its gains change at block boundaries)"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (st[i].kind == KNH_STAGE_GALACTIC) {  // the reverb ends a chain of its own kind (galactic_bank.hpp)
+      if (i + 1 != n) { *why = "Galactic ends the chain: it must be the last stage"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (st[i].delayed_changes_per_block > 0) { *why = "Galactic cannot be wrapped in WrPreciseTiming here (its parameters take effect at the next process call)"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (st[i].ar_param != 0 || st[i].input2 != 0) { *why = "Galactic has no audio-rate parameter (ar_param = 0, input2 = 0)"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (st[i].flags != 0) { *why = "Galactic takes no stage flags"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (st[i].input != 0 && st[i].input != i) { *why = "both inputs of Galactic are the voice's running signal (input = 0)"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (sig->find_first_of("DYZ") != std::string::npos) { *why = "a chain that ends in Galactic holds no other delay stage"; return KNH_ERR_INVALID_ARGUMENT; }
+    }
     if (st[i].ar_param != 0) {  // an audio-rate parameter: the node's float parameter ar_param - 1 is driven by the signal input2 names
       const uint32_t p = st[i].ar_param - 1u;
       if (p >= static_cast<uint32_t>(kKinds[st[i].kind].n_params) || expected_value_kind(st[i].kind, p) != KNH_VALUE_FLOAT) { *why = "ar_param names a float parameter of the stage (1 + its index)"; return KNH_ERR_INVALID_ARGUMENT; }

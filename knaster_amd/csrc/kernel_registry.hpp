@@ -3,6 +3,8 @@
 // Signature: one character per device stage, in chain order:
 //   W SinWt   R SinWt.ar_params() driven by the running signal   N SinNumeric
 //   S SvfFilter   L OnePoleLpf   H OnePoleHpf   A x*EnvAsr   E x*EnvAr   V x*Envelope (segments)   D SampleDelay   P Phasor   X SafetyLimiter   B PolyBlep   Y AllpassDelay   Z AllpassFeedbackDelay   F BufferReader   U WhiteNoise   K PinkNoise   O BrownNoise   G RandomLin
+//   Q Galactic (last stage only: the stereo reverb; never part of a fused kernel -- galactic_bank.hpp runs the chain before it
+//     through one of the kernels below and the reverb in kernels_galactic.hip)
 //   J Pan2 (last stage only: two output channels)   I an input channel of the bank node (a source shared by all voices)
 //   + - * / ^  MathUGen of two signals; "@a" / "@a,b" after a stage: the stage(s) whose output it reads, when not the one before it
 //   m x*value   a x+value   s x-value   d x/value   v value-x   q value/x   p x.powf(value)   i x.powi(n)

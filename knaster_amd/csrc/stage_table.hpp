@@ -53,6 +53,7 @@ const KindInfo kKinds[KNH_STAGE_KIND_COUNT] = {
     /* MATH_DIV    */ {0, 0, 0, 1, '/', {nullptr}},
     /* MATH_POW    */ {0, 0, 0, 1, '^', {nullptr}},
     /* INPUT       */ {1, 0, 1, 0, 'I', {nullptr}},
+    /* GALACTIC    */ {0, 5, 7, 1, 'Q', {"replace", "detune", "brightness", "bigness", "wet"}},  // state and rings: galactic_bank.hpp
 };
 inline bool is_math2_kind(uint16_t kind) { return kind >= KNH_STAGE_MATH_ADD && kind <= KNH_STAGE_MATH_POW; }
 // A voice that is a graph rather than a chain: explicit operands, a MathUGen of two signals, or a second source.

@@ -1349,6 +1349,7 @@ struct Bank final : knh_bank {
     return KNH_OK;
   }
   bool pan = false;          // the chain ends in a Pan2
+  F* stage_out = nullptr;    // set by a bank that wraps this one (galactic_bank.hpp): the voices' signals of the block go here, [n_voices][block_size]
   unsigned fold_planes = 1;  // channel planes of the partial rows and of the per-voice output: 2 for a Pan2 chain
   hipError_t ensure_voices() {
     if (d_voices) return hipSuccess;
@@ -2205,10 +2206,11 @@ struct Bank final : knh_bank {
       if (rc != KNH_OK) return rc;
       res_make_room();
     }
-    const bool want_voices = voices_host != nullptr || (desc.mix_mode == KNH_MIX_LEFT_FOLD);
+    const bool want_voices = voices_host != nullptr || (desc.mix_mode == KNH_MIX_LEFT_FOLD) || stage_out != nullptr;
     if (desc.mix_mode == KNH_MIX_LEFT_FOLD && n_blocks > 1)
       return fail(KNH_ERR_INVALID_ARGUMENT, "KNH_MIX_LEFT_FOLD processes one block per call");
-    if (want_voices) KNH_HIP(ensure_voices());
+    if (stage_out && n_blocks > 1) return fail(KNH_ERR_INTERNAL, "a bank that feeds a following stage renders one block per launch");
+    if (want_voices && !stage_out) KNH_HIP(ensure_voices());
     const unsigned n_waves = interp ? nv : (nv + 63) / 64;
     if (n_blocks > partials_blocks) {
       KNH_HIP(hipStreamSynchronize(s));
@@ -2266,7 +2268,7 @@ struct Bank final : knh_bank {
       a.events = d_out_events2[out_in_use];
     }
     a.partials = d_partials;
-    a.voices_out = want_voices ? d_voices : nullptr;
+    a.voices_out = want_voices ? (stage_out ? stage_out : d_voices) : nullptr;
     a.done_frames = d_done;
     a.flags = flags_now;
     std::pair<hipEvent_t, hipEvent_t>* tp = nullptr;
@@ -2288,6 +2290,8 @@ struct Bank final : knh_bank {
     if (interp) KNH_HIP(launch_interp(a, s));
     else KNH_HIP(launch_voice(a, n_waves, s));
     if (tp) KNH_HIP(hipEventRecord(tp->second, s));
+    if (stage_out && interp)  // (the interpreter's rows are the voices' signals)
+      KNH_HIP(hipMemcpyAsync(stage_out, d_partials, static_cast<size_t>(nv) * block_size * sizeof(F), hipMemcpyDeviceToDevice, s));
     if (out_in_use >= 0) {  // the resolver may rewrite this set of lists once this kernel has read it
       KNH_HIP(hipEventRecord(lists_free[out_in_use], s));
       lists_busy[out_in_use] = true;

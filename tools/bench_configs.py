@@ -13,8 +13,10 @@ import knaster_amd
 from knaster_amd import _lib as L, configs
 
 
-def run(name, n_voices=None, launches=16, blocks=32, allow_fma=False, host_threads=0):
+def run(name, n_voices=None, launches=16, blocks=32, allow_fma=False, host_threads=0, detune=None):
     w = configs.config(name, n_voices=n_voices)
+    if detune is not None and name == "G1":  # G1 with one detune everywhere (0: no f64 phase, no sin)
+        w.ctor[3][:, 1] = detune
     b = knaster_amd.VoiceBank(w.stages, w.n_voices, w.sample_type, w.out_channels, L.MIX_TREE, -1, allow_fma, host_threads)
     for s, a in w.ctor.items():
         b.set_ctor_args(s, a)
@@ -63,10 +65,19 @@ def run(name, n_voices=None, launches=16, blocks=32, allow_fma=False, host_threa
     if w.delay_times is not None:  # the ring: one sample read and one written per frame
         rd += 4 * w.block_size
         wr += 4 * w.block_size
+    extra = {}
+    if name == "G1":  # 24 long rings + the two short ones, one sample read and one written per frame each; the staged input; two outputs
+        word = 8 if w.sample_type else 4
+        rd += (24 + 2 + 1) * word * w.block_size
+        wr += (24 + 2 + 1 + 2) * word * w.block_size
+        vs = float(w.n_voices) * w.block_size * blocks
+        extra = {"voice_samples_per_s": vs * launches / dt, "kernel_only_voice_samples_per_s": vs * n / (kms * 1e-3),
+                 "ring_algorithmic_GBps": 50 * word * vs * n / (kms * 1e-3) / 1e9, "blocks_per_launch": blocks,
+                 "detune": "per voice" if detune is None else detune}
     print(json.dumps({"config": name, "voices": w.n_voices, "block_size": w.block_size, "sample_type": "f64" if w.sample_type else "f32",
                       "ugens_per_voice": ugens, "allow_fma": allow_fma, "host_threads": max(1, host_threads), "ugen_samples_per_s": work / dt,
                       "kernel_only_ugen_samples_per_s": work / (kms * 1e-3), "us_per_block_kernel": kms * 1e3 / (n * blocks),
-                      "hbm_algorithmic_GBps": (rd + wr) * w.n_voices * blocks * n / (kms * 1e-3) / 1e9}), flush=True)
+                      "hbm_algorithmic_GBps": (rd + wr) * w.n_voices * blocks * n / (kms * 1e-3) / 1e9, **extra}), flush=True)
     b.close()
 
 
@@ -75,6 +86,11 @@ if __name__ == "__main__":
         run("C3", n_voices=65536)
         run("C3", n_voices=262144, launches=4)
         run("D3")
+        run("D3", n_voices=65536)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "G1":  # the reverb: 4 096 voices, 64 blocks per launch; the same with no detune; D3 beside it
+        run("G1", launches=8, blocks=64)
+        run("G1", launches=8, blocks=64, detune=0.0)
         run("D3", n_voices=65536)
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "only":  # tools/bench_configs.py only C5 C3 C2:1024 ...
