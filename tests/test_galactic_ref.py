@@ -127,6 +127,156 @@ def test_scalar_and_vectorised_agree_bit_for_bit(f32, detune):
         assert np.abs(a).max() > 1e-3
 
 
+def _both(f32, sr, args, x, between=None, n_calls=3, seeds=((424242, 31337), (5, 6))):
+    """`x` through Galactic (two voices, the second with other seeds) and through one ScalarGalactic per voice, in `n_calls`
+    process calls; between(k, set_param) moves parameters after call k.  Asserts every sample of both channels of both voices
+    bit-identical; returns (left, right) of voice 0 and the vectorised object."""
+    dtype = np.float32 if f32 else np.float64
+    x = np.asarray(x).astype(dtype)
+    v = gr.Galactic(2, dtype, *args, [s[0] for s in seeds], [s[1] for s in seeds])
+    v.init(sr)
+    ss = [gr.ScalarGalactic(f32, sr, *args, *s) for s in seeds]
+
+    def set_param(index, value):
+        v.set_param(index, value)
+        for s in ss:
+            s.p[index] = s.r(value)
+
+    n = len(x) // n_calls
+    got = [[], []]
+    want = [[[], []], [[], []]]
+    for k in range(n_calls):
+        seg = x[k * n:(k + 1) * n]
+        ol, orr = v.process(np.tile(seg, (2, 1)), np.tile(seg, (2, 1)))
+        got[0].append(ol)
+        got[1].append(orr)
+        for i, s in enumerate(ss):
+            sl, sr_ = s.process([float(t) for t in seg])
+            want[i][0] += sl
+            want[i][1] += sr_
+        if between is not None:
+            between(k, set_param)
+    u = np.uint32 if f32 else np.uint64
+    got = [np.concatenate(g, axis=1) for g in got]
+    for i in range(2):
+        for c in range(2):
+            w = np.array(want[i][c], dtype=dtype)
+            assert np.isfinite(w).all()
+            differ = np.flatnonzero(got[c][i].view(u) != w.view(u))
+            assert differ.size == 0, f"voice {i} channel {c}: {differ.size} samples differ, first at {differ[0]}"
+    for s, want_vib, want_old in zip(ss, v.vib_m, v.oldfpd):
+        assert s.vib == want_vib and s.old == want_old
+    return got[0][0], got[1][0], v
+
+
+def _burst(n, amp=0.1, seed=11):
+    rng = np.random.default_rng(seed)
+    x = np.zeros(n)
+    m = min(400, n // 4)
+    x[:m] = rng.standard_normal(m) * amp * np.linspace(1, 0, m)
+    x[n // 2:n // 2 + 20] = 2.0 * amp
+    return x
+
+
+@pytest.mark.parametrize("f32", [True, False])
+@pytest.mark.parametrize("sr,min_len", [(1500, 2), (2000, 3), (8000, 12), (22050, 34), (96000, 148)])
+def test_scalar_and_vectorised_agree_at_other_sample_rates(f32, sr, min_len):
+    """Rings of 2 .. 33 131 samples: the short ones wrap many times per call.  bigness starts at 0 (the shortest rings the rate
+    has), then moves as in the 44.1 kHz case: growth, then the shrink that strands `position`.  brightness 0.5 keeps the
+    one-pole's coefficient (brightness + 1e-5)^2 / sqrt(sr / 44100) below 2 down to 1 500 Hz (1.36 there)."""
+    n = 2400 if sr < 44100 else 1500
+
+    def between(k, set_param):
+        set_param(gr.Galactic.BIGNESS, [0.9, 0.0][k % 2])
+
+    dtype = np.float32 if f32 else np.float64
+    probe = gr.Galactic(1, dtype, 0.3, 0.0, 0.5, 0.0, 0.6, 1, 1)
+    probe.init(sr)
+    probe.process(np.zeros((1, 1), dtype=dtype), np.zeros((1, 1), dtype=dtype))
+    seen = min(int(d.delay_length[0]) for d in probe.delays_left)
+    assert seen == min_len
+    left, right, _ = _both(f32, sr, (0.3, 0.0, 0.5, 0.0, 0.6), _burst(n), between)
+    assert np.abs(left).max() > 1e-3 and np.abs(right).max() > 1e-3
+
+
+@pytest.mark.parametrize("f32", [True, False])
+@pytest.mark.parametrize("detune,least_resets", [(0.05, 1), (3.0, 5)])
+def test_scalar_and_vectorised_agree_through_phase_resets(f32, detune, least_resets):
+    """detune 0.05: the phase leaves 3.0 in steps of 429496.7 * 1.25e-7 = 0.054 and first passes 2 pi some 60 samples in;
+    detune 3.0 (the 0 .. 1 of the parameter is a hint: nothing clamps it): after the first reset a step is
+    oldfpd * 0.027 = 0.012 .. 0.019, a reset every 340 .. 540 samples."""
+    n = 3000
+    resets = [0, 0]
+    old = [429496.7295, 429496.7295]
+
+    dtype = np.float32 if f32 else np.float64
+    # count the resets on the vectorised object, call by call of 100 samples (oldfpd changes at a reset: the seeds' streams
+    # do not repeat a value within 2^32 - 1 steps)
+    x = _burst(n).astype(dtype)
+    v = gr.Galactic(2, dtype, 0.6, detune, 0.7, 0.05, 0.6, [424242, 5], [31337, 6])
+    v.init(44100)
+    for k in range(0, n, 100):
+        seg = np.tile(x[k:k + 100], (2, 1))
+        v.process(seg, seg)
+        for i in range(2):
+            if v.oldfpd[i] != old[i]:
+                resets[i] += 1
+                old[i] = v.oldfpd[i]
+    assert min(resets) >= least_resets, resets
+    assert v.oldfpd[0] != v.oldfpd[1]
+    left, right, v3 = _both(f32, 44100, (0.6, detune, 0.7, 0.05, 0.6), x)
+    assert np.array_equal(v3.oldfpd, v.oldfpd) and np.array_equal(v3.vib_m, v.vib_m)  # (100-sample calls or 1 000: the same)
+    assert np.abs(left).max() > 1e-3 and np.abs(right).max() > 1e-3
+
+
+@pytest.mark.parametrize("f32", [True, False])
+def test_scalar_and_vectorised_agree_when_detune_moves(f32):
+    """0 -> 0.6 -> 0 -> 0.05: the phase is still at its initial 3.0 in the first call, moves, is frozen at some other value
+    (its sine is no longer the constant of the first call), and moves again, slowly."""
+    seq = [0.6, 0.0, 0.05]
+    frozen = []
+
+    def between(k, set_param):
+        if k < len(seq):
+            set_param(gr.Galactic.DETUNE, seq[k])
+
+    n = 3200
+    x = np.concatenate([_burst(n // 4, seed=s) for s in range(4)])
+    left, right, v = _both(f32, 44100, (0.6, 0.0, 0.7, 0.05, 0.6), x, between, n_calls=4)
+    assert np.all(v.vib_m != 3.0)
+    # the call with detune back at 0 must have run with the phase off 3.0: replay the first two calls and look
+    dtype = np.float32 if f32 else np.float64
+    w = gr.Galactic(1, dtype, 0.6, 0.0, 0.7, 0.05, 0.6, 424242, 31337)
+    w.init(44100)
+    for k in range(3):
+        seg = x[k * 800:(k + 1) * 800].astype(dtype).reshape(1, -1)
+        w.process(seg, seg)
+        frozen.append(float(w.vib_m[0]))
+        if k < 2:
+            w.set_param(gr.Galactic.DETUNE, seq[k])
+    assert frozen[0] == 3.0 and frozen[1] != 3.0 and frozen[2] == frozen[1]
+    assert np.abs(left).max() > 1e-3 and np.abs(right).max() > 1e-3
+
+
+@pytest.mark.parametrize("f32", [True, False])
+def test_scalar_and_vectorised_agree_on_loud_output(f32):
+    """Output samples in all three classes of the dither's exponent: |s| < 1 (2^62), 1 <= |s| < 2 (2^63), |s| >= 2 (2_u64.pow
+    wraps to 0 in a release build: no dither).  The input is a decaying sine of amplitude 3 or 40, dry (wet 0), mixed (0.3)
+    and reverb alone (1); over the six runs each class must hold at least 5 % of the samples."""
+    n = 1500
+    t = np.arange(n)
+    mags = []
+    for amp in (3.0, 40.0):
+        for wet in (0.0, 0.3, 1.0):
+            x = amp * np.sin(t * 0.31) * np.exp(-t / 500.0)
+            left, right, _ = _both(f32, 44100, (0.8, 0.0, 0.7, 0.05, wet), x)
+            mags.append(np.abs(np.concatenate([left, right])))
+    mag = np.concatenate(mags)
+    for lo, hi in [(0.0, 1.0), (1.0, 2.0), (2.0, np.inf)]:
+        share = np.count_nonzero((mag >= lo) & (mag < hi)) / mag.size
+        assert share >= 0.05, (lo, hi, share)
+
+
 def _chain(*extra, galactic=Stage(L.STAGE_GALACTIC)):
     return [Stage(L.STAGE_SIN_WT), *extra, galactic]
 

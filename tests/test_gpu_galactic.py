@@ -38,9 +38,10 @@ def settings(nv, seed=1, detune=0.0, replace_lo=0.0):
     return p
 
 
-def src_ctor(nv, amp=0.25):
-    freq = 110.0 + 7.0 * np.arange(nv)
-    return {0: freq.reshape(nv, 1), 1: np.full((nv, 1), amp), 2: np.tile([0.0005, 0.002], (nv, 1))}  # 24 + 96 samples of burst
+def src_ctor(nv, amp=0.25, sr=SR):
+    """The burst has the same shape in samples at every rate: 110 + 7 v Hz and 0.5 ms + 2 ms at 48 kHz."""
+    freq = (110.0 + 7.0 * np.arange(nv)) * (sr / SR)
+    return {0: freq.reshape(nv, 1), 1: np.full((nv, 1), amp), 2: np.tile([24.0 / sr, 96.0 / sr], (nv, 1))}  # 24 + 96 samples of burst
 
 
 def gal_ctor(p):
@@ -48,31 +49,50 @@ def gal_ctor(p):
 
 
 class Rig:
-    """The GPU bank(s), the oracle's source chain and the restatement, driven with identical calls."""
+    """The GPU bank(s), the oracle's source chain and the restatement, driven with identical calls.
+    sr: the sample rate of all three.  src: another chain in front of the reverb, as (stages, {stage: ctor args}, (stage, param)
+    of the trigger fire() sends); the default is SRC with src_ctor.  peak_limit: the bound ref_block asserts on the
+    restatement's output (None: the case is about loud output)."""
 
-    def __init__(self, knh, oracle, nv, st, bs, p, mixes=(L.MIX_LEFT_FOLD,), amp=0.25):
-        self.nv, self.bs = nv, bs
+    def __init__(self, knh, oracle, nv, st, bs, p, mixes=(L.MIX_LEFT_FOLD,), amp=0.25, sr=SR, src=None, peak_limit=1.0):
+        self.nv, self.bs, self.sr = nv, bs, sr
         self.dtype = np.float64 if st == L.F64 else np.float32
+        stages, ctor, self.trigger = src if src is not None else (SRC, src_ctor(nv, amp, sr), (2, 2))
+        stages = list(stages)
+        self.G = len(stages)  # the Galactic stage
         self.gpu, self.mixes = [], list(mixes)
         for mix in mixes:
-            b = knh.VoiceBank(SRC + [Stage(L.STAGE_GALACTIC)], nv, st, 2, mix)
-            for s, a in src_ctor(nv, amp).items():
+            b = knh.VoiceBank(stages + [Stage(L.STAGE_GALACTIC)], nv, st, 2, mix)
+            for s, a in ctor.items():
                 b.set_ctor_args(s, a)
-            b.set_ctor_args(G, gal_ctor(p))
-            b.init(SR, bs)
+            b.set_ctor_args(self.G, gal_ctor(p))
+            b.init(sr, bs)
             self.gpu.append(b)
-        self.src = oracle.OracleBank(SRC, nv, st, 1)
-        for s, a in src_ctor(nv, amp).items():
+        self.src = oracle.OracleBank(stages, nv, st, 1)
+        for s, a in ctor.items():
             self.src.set_ctor_args(s, a)
-        self.src.init(SR, bs)
+        self.src.init(sr, bs)
         self.ref = gr.Galactic(nv, self.dtype, p["replace"], p["detune"], p["brightness"], p["bigness"], p["wet"],
                                p["fpd_l"].astype(np.uint32), p["fpd_r"].astype(np.uint32))
-        self.ref.init(SR)
-        self.peak = 0.0
+        self.ref.init(sr)
+        self.peak, self.peak_limit = 0.0, peak_limit
 
     def fire(self):
         for b in self.gpu + [self.src]:
-            fire_all(b, self.nv, 2, 2)
+            fire_all(b, self.nv, *self.trigger)
+
+    def inner(self, call):
+        """call(bank) on every bank that holds the chain in front of the reverb: the GPU banks and the oracle's."""
+        for b in self.gpu + [self.src]:
+            call(b)
+
+    def set_param(self, param, values, voices=None):
+        """One of the reverb's parameters on the GPU banks (param_apply_many) and on the restatement."""
+        v = np.arange(self.nv, dtype=np.uint32) if voices is None else np.asarray(voices, dtype=np.uint32)
+        values = np.broadcast_to(np.asarray(values, dtype=np.float64), v.shape)
+        for b in self.gpu:
+            b.param_apply_many(v, self.G, param, L.VALUE_FLOAT, values)
+        self.ref.set_param(param, values, voices=v)
 
     def ref_block(self):
         _, dry, _, _ = self.src.process_block()
@@ -80,7 +100,8 @@ class Rig:
         out_l, out_r = self.ref.process(dry, dry)
         want = np.stack([out_l, out_r])
         self.peak = max(self.peak, float(np.abs(want).max()))
-        assert self.peak < 1.0, "the restatement's output must stay below 1.0: change the input, not the bound"
+        if self.peak_limit is not None:
+            assert self.peak < self.peak_limit, "the restatement's output must stay below 1.0: change the input, not the bound"
         return want
 
     def close(self):
