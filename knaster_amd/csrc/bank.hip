@@ -12,12 +12,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -35,8 +37,10 @@ using knh_dev::VoiceKernelArgs;
 
 #include "stage_table.hpp"
 #include "bank_base.hpp"
-#include "voice_bank.hpp"
 #include "chain_signature.hpp"
+#include "event_resolver.hpp"
+#include "resident_call.hpp"
+#include "voice_bank.hpp"
 
 namespace {
 
@@ -49,8 +53,7 @@ knh_bank* make_bank(const knh_bank_desc& d, const knh::KernelEntry* entry, const
   {  // KNH_PIPELINE=0 forces the single-wave kernel (A/B measurements); KNH_JIT=1 forces run-time fusion
     const char* jit_env = std::getenv("KNH_JIT");
     if (jit_env && jit_env[0] == '1') b->entry = nullptr;
-    // KNH_PIPELINE: 0 = single-wave kernel, 1 (default) = linear wave pipeline, 2 = five-role pipeline
-    // (voice_dag.hpp; bit-identical, measured 5-8 % slower than level 1 on MI355X, kept for experiments)
+    // KNH_PIPELINE: 0 = single-wave kernel, 1 (default) or 2 = linear wave pipeline
     const char* env = std::getenv("KNH_PIPELINE");
     const int level = env && env[0] >= '0' && env[0] <= '2' ? env[0] - '0' : 1;
     b->pipeline_level = level;
@@ -62,7 +65,6 @@ knh_bank* make_bank(const knh_bank_desc& d, const knh::KernelEntry* entry, const
     const char* big_env = std::getenv("KNH_PIPE_BIG");
     const unsigned forms = big_env && big_env[0] == '0' ? 1u : (big_env && big_env[0] == '1' ? 3u : 7u);
     if (b->entry && level >= 1) b->pipe = knh::find_pipe(sig.c_str(), forms);
-    if (b->entry && level >= 2 && d.sample_type == KNH_F32) b->dag = knh::find_dag(sig.c_str());
     // Occupancy regime: the wave pipeline minimises latency when every 64-voice group can have a CU to
     // itself (<= ~1.5 groups per CU); beyond that throughput wins and the groups are packed 4 or 8 to a
     // workgroup (one or two wavefronts per SIMD) sharing one staged sine table.  KNH_WIDE=0/4/8 overrides.

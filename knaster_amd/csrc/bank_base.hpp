@@ -105,3 +105,11 @@ struct knh_bank {
     if (warnings.size() < 32) warnings.push_back(msg);
   }
 };
+
+// in a function with a fail(code, message) in scope (a bank's, or one that passes it on to its bank)
+#define KNH_HIP(expr)                                                                                      \
+  do {                                                                                                     \
+    hipError_t e_ = (expr);                                                                                \
+    if (e_ != hipSuccess)                                                                                  \
+      return fail(KNH_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));                      \
+  } while (0)

@@ -1,5 +1,7 @@
 // chain_signature.hpp -- a chain descriptor (knh_stage_desc[]) checked and turned into the device signature
-// (kernel_registry.hpp: one character per stage, operands and signal slots for graph-shaped voices).  Included by bank.hip only.
+// (kernel_registry.hpp: one character per stage, operands and signal slots for graph-shaped voices), and what a bank's init
+// reads off the two: the frame-parallel interpreter's program, the envelopes' task order, whether a voice can finish.
+// Included by bank.hip only.
 #pragma once
 
 namespace {
@@ -117,6 +119,111 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     *sig = out + "#" + std::to_string(busy.size());  // "#R": the number of slots
   }
   return KNH_OK;
+}
+
+// The signature of a voice made of SinWt oscillators and arithmetic alone (interp_can_run) -> the program of the
+// frame-parallel interpreter (kernels_interp.hip), one op per stage; *n_sigs its signal slots, *out the slot of the voice's
+// output.  False: the signature is malformed.
+bool parse_frame_program(const std::string& signature, const std::vector<StageInfo>& stages, std::vector<knh_dev::InterpOp>* prog, unsigned* n_sigs, unsigned* out) {
+  const bool graph = signature_is_dag(signature);
+  prog->clear();
+  size_t si = 0;
+  const char* p = signature.c_str();
+  while (*p && *p != '#') {
+    knh_dev::InterpOp op{};
+    const char c = *p++;
+    int v[3] = {-1, -1, -1};
+    if (*p == '@') {
+      ++p;
+      for (int k = 0; k < 3; ++k) {
+        if (*p == '_') { ++p; } else { v[k] = 0; while (*p >= '0' && *p <= '9') v[k] = v[k] * 10 + (*p++ - '0'); }
+        if (*p == ',') ++p;
+      }
+    }
+    switch (c) {
+      case 'W': op.kind = knh_dev::INTERP_SIN_WT; break;
+      case 'm': op.kind = knh_dev::INTERP_VAL_MUL; break;
+      case 'a': op.kind = knh_dev::INTERP_VAL_ADD; break;
+      case 's': op.kind = knh_dev::INTERP_VAL_SUB; break;
+      case 'd': op.kind = knh_dev::INTERP_VAL_DIV; break;
+      case 'v': op.kind = knh_dev::INTERP_VAL_VSUB; break;
+      case 'q': op.kind = knh_dev::INTERP_VAL_VDIV; break;
+      case '*': op.kind = knh_dev::INTERP_MATH_MUL; break;
+      case '+': op.kind = knh_dev::INTERP_MATH_ADD; break;
+      case '-': op.kind = knh_dev::INTERP_MATH_SUB; break;
+      default: op.kind = knh_dev::INTERP_MATH_DIV; break;
+    }
+    if (!graph) {  // a plain chain: one signal, every stage works on it in place
+      v[0] = c == 'W' ? -1 : 0;
+      v[2] = 0;
+    }
+    if (si >= stages.size() || v[2] < 0 || (c != 'W' && v[0] < 0)) return false;
+    op.a = static_cast<unsigned short>(v[0] < 0 ? 0 : v[0]);
+    op.b = static_cast<unsigned short>(v[1] < 0 ? 0 : v[1]);
+    op.o = static_cast<unsigned short>(v[2]);
+    op.slot = static_cast<uint32_t>(stages[si].slot_base);
+    prog->push_back(op);
+    ++si;
+  }
+  *n_sigs = *p == '#' ? static_cast<unsigned>(std::atoi(p + 1)) : (graph ? 0u : 1u);
+  *out = prog->empty() ? 0u : prog->back().o;
+  return si == stages.size() && *n_sigs != 0;
+}
+
+// VoiceKernelArgs::env_ranks of a voice that is a graph with several envelope stages: which envelope's mark_done names the
+// voice's done frame when several finish in one block -- the last one in the reference's TASK order (graph_gen.rs:196-200),
+// which for a graph is the order Graph::calculate_node_order sorts the nodes into (graph.rs:1938-2067): depth first from
+// the output, a node's inputs in channel order, each node after everything it reads; nodes the output does not depend on
+// come last, in the order they were pushed.  0: list order (every chain; and graphs whose task order agrees with it).
+uint64_t envelope_task_ranks(const std::string& signature, const std::vector<StageInfo>& stages) {
+  if (!signature_is_dag(signature)) return 0;
+  const int n = static_cast<int>(stages.size());
+  auto is_src = [&](int i) { return std::strchr("WNPUKOGBFI", kKinds[stages[i].kind].sig) != nullptr && !(stages[i].flags & KNH_STAGE_FLAG_AR_FREQ); };
+  auto node_output = [&](int k) { while (k + 1 < n && is_wrapper_kind(stages[k + 1].kind)) ++k; return k; };
+  std::vector<int> a(n, -1), b(n, -1);
+  for (int i = 0; i < n; ++i) {
+    if (is_math2_kind(stages[i].kind)) { a[i] = node_output(stages[i].input - 1); b[i] = node_output(stages[i].input2 - 1); }
+    else if (i > 0 && !is_src(i)) a[i] = stages[i].input ? node_output(stages[i].input - 1) : i - 1;
+    // an audio-rate parameter edge: followed after the node's input edges (graph.rs:1938-1980)
+    if (stages[i].ar_param && !is_math2_kind(stages[i].kind)) b[i] = node_output(stages[i].input2 - 1);
+  }
+  std::vector<int> order, state(n, 0), stack{n - 1};
+  while (!stack.empty()) {  // post-order, first operand first
+    const int k = stack.back();
+    if (state[k] == 0) { state[k] = 1; if (a[k] >= 0 && state[a[k]] == 0) { stack.push_back(a[k]); continue; } }
+    if (state[k] == 1) { state[k] = 2; if (b[k] >= 0 && state[b[k]] == 0) { stack.push_back(b[k]); continue; } }
+    if (state[k] == 2) { state[k] = 3; order.push_back(k); }
+    stack.pop_back();
+  }
+  for (int i = 0; i < n; ++i) if (state[i] == 0) order.push_back(i);
+  std::vector<int> rank(n, 0);
+  for (size_t r = 0; r < order.size(); ++r) rank[order[r]] = static_cast<int>(r);
+  std::vector<int> envs;
+  for (int i = 0; i < n; ++i)
+    if (stages[i].kind == KNH_STAGE_MUL_ENV_ASR || stages[i].kind == KNH_STAGE_MUL_ENV_AR || stages[i].kind == KNH_STAGE_MUL_ENVELOPE) envs.push_back(i);
+  bool in_list_order = true;
+  for (size_t j = 1; j < envs.size(); ++j) in_list_order = in_list_order && rank[envs[j - 1]] < rank[envs[j]];
+  uint64_t ranks = 0;
+  if (!in_list_order && envs.size() <= 15) {
+    std::vector<int> by_rank(envs);
+    std::sort(by_rank.begin(), by_rank.end(), [&](int x, int y) { return rank[x] < rank[y]; });
+    for (size_t j = 0; j < envs.size(); ++j) {
+      const uint64_t place = 1 + static_cast<uint64_t>(std::find(by_rank.begin(), by_rank.end(), envs[j]) - by_rank.begin());
+      ranks |= place << (4 * j);
+    }
+  }
+  return ranks;
+}
+
+// The chain has a stage that can end a voice: without one ALL_DONE is never reported (a chain without an envelope never finishes).
+bool chain_can_finish(const std::vector<StageInfo>& stages) {
+  for (const StageInfo& st : stages)
+    if (st.kind == KNH_STAGE_MUL_ENV_ASR || st.kind == KNH_STAGE_MUL_ENV_AR || st.kind == KNH_STAGE_MUL_ENVELOPE || st.kind == KNH_STAGE_BUFFER_READER) return true;
+  return false;
+}
+// A block's done / running voice counts -> the flags of knh_bank_process_block.
+inline uint32_t done_flags(uint32_t n_done, uint32_t n_running, bool can_finish) {
+  return (n_done ? KNH_FLAG_ANY_DONE : 0u) | (can_finish && n_running == 0 ? KNH_FLAG_ALL_DONE : 0u);
 }
 
 }  // namespace

@@ -21,7 +21,7 @@ enum { INTERP_VAL_MUL = 0, INTERP_VAL_ADD, INTERP_VAL_SUB, INTERP_VAL_DIV, INTER
 struct InterpOp { u32 kind; unsigned short a, b, o, pad; u32 slot; };  // 16 bytes
 static_assert(sizeof(InterpOp) == 16, "one 16-byte LDS read per stage");
 // Device-side resolution of WrPreciseTiming change queues (kernels_events.hip).  DevRec is the host's 24-byte record of one
-// call (Bank::QRec: the same bytes); DevStage what the resolver needs to know of a stage.
+// call (QRec, event_resolver.hpp: the same bytes); DevStage what the resolver needs to know of a stage.
 struct DevRec {
   u32 voice;
   unsigned short delay;   // set_delay_within_block_for_param value, when the arm bit is set
@@ -82,12 +82,6 @@ struct PipeEntry {
 };
 // the first entry for the chain whose form is in `forms` (bit i = form i)
 const PipeEntry* find_pipe(const char* signature, unsigned forms = 7u, int groups_per_workgroup = 1);
-// Five-role (dependence-cut) pipeline for source -> SVF -> x*envelope -> post chains, f32 banks (voice_dag.hpp).
-struct DagEntry {
-  const char* signature;
-  VoiceLaunchFn<float> f32[2];
-};
-const DagEntry* find_dag(const char* signature);
 // Many-wave builds of the single-wave kernel (4 or 8 voice groups per workgroup) for large banks.
 struct WideEntry {
   const char* signature;

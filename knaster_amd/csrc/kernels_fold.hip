@@ -1,44 +1,11 @@
-// kernels_fold.hip -- the mix kernels (tree fold, exact left fold, sum of host shards) and, only when the library is
-// built with KNH_BUILD_DAG=1, the experimental five-role pipeline of voice_dag.hpp (measured slower than the linear
-// pipeline; not part of the default build).
+// kernels_fold.hip -- the mix kernels: tree fold, exact left fold, sum of host shards, and the resident call's fold server.
 #include <cstring>
 
 #include "kernel_registry.hpp"
-#ifdef KNH_WITH_DAG
-#include "voice_dag.hpp"
-#endif
 #include "voice_pipe.hpp"
 
 namespace knh {
 using namespace knh_dev;
-
-#ifdef KNH_WITH_DAG
-template <bool FMA, bool AR, typename SRC, typename POST>
-static hipError_t launch_dag(const VoiceKernelArgs<float>& args, unsigned n_wavefronts, hipStream_t stream) {
-  if (n_wavefronts == 0) return hipSuccess;
-  hipLaunchKernelGGL((voice_dag_kernel<float, FMA, AR, SRC, POST>), dim3(n_wavefronts), dim3(320), 0, stream, args);
-  return hipGetLastError();
-}
-#define KNH_DAG(sig, ar, src, post) {sig, {launch_dag<false, ar, src, post>, launch_dag<true, ar, src, post>}}
-typedef Group<> G_none;
-typedef Group<SinWt, MulVal> G_Wm;
-typedef Group<SinWt> G_W;
-typedef Group<SinNum> G_N;
-typedef Group<MulVal> G_m;
-static const DagEntry kDags[] = {
-    KNH_DAG("WmSA", false, G_Wm, G_none),  // C3
-    KNH_DAG("WSA", false, G_W, G_none),
-    KNH_DAG("WSAm", false, G_W, G_m),
-    KNH_DAG("NSAm", false, G_N, G_m),
-};
-const DagEntry* find_dag(const char* signature) {
-  for (const DagEntry& e : kDags)
-    if (std::strcmp(e.signature, signature) == 0) return &e;
-  return nullptr;
-}
-#else
-const DagEntry* find_dag(const char*) { return nullptr; }
-#endif
 
 template <typename F>
 static hipError_t launch_fold(bool tree, const F* rows, unsigned n_rows, unsigned row_len, unsigned frame_begin, unsigned frame_end,

@@ -2,31 +2,12 @@
 // (never of audio-evolving state) and turns each UGen::param_apply into device state patches: all transcendental work (tan /
 // pow / sqrt / exp for filter coefficients, the f64 phase-increment product) happens here with the same libm the reference's
 // std-backed num-traits would call; WrPreciseTiming's queues, WrSmoothParams' ramps, the per-launch event lists, the kernel
-// choice and the launch itself.  Included by bank.hip only.
+// choice and the launch itself.  Two protocols with the device live behind types of their own, each owning its resources:
+// the per-block call on a resident launch (resident_call.hpp) and the change queues the device resolves (event_resolver.hpp).
+// Included by bank.hip only.
 #pragma once
 
 namespace {
-
-#define KNH_HIP(expr)                                                                                      \
-  do {                                                                                                     \
-    hipError_t e_ = (expr);                                                                                \
-    if (e_ != hipSuccess)                                                                                  \
-      return fail(KNH_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-  } while (0)
-
-// ---- resident launches (voice_chain.hpp, Resident) -----------------------------------------------------------------------
-// A resident kernel keeps every CU's LDS: another bank's launch on the same device could not start beside it.  So there is at
-// most one per device, and whoever is about to launch anything there asks it to leave first.  One mutex guards every
-// transition (a bank is single-caller, but two banks may belong to two threads).
-struct ResidentSlot {
-  std::mutex mu;
-  knh_bank* owner[64] = {};
-  void (*leave[64])(knh_bank*) = {};
-};
-inline ResidentSlot& resident_slot() {
-  static ResidentSlot s;
-  return s;
-}
 
 template <typename F>
 struct Bank final : knh_bank {
@@ -34,7 +15,6 @@ struct Bank final : knh_bank {
   const knh::KernelEntry* entry = nullptr;
   const knh::PipeEntry* pipe = nullptr;  // wave-specialised variant, used when built for this chain
   bool pipe_pair = false;                // ... in its two-groups-per-workgroup form (banks of more groups than CUs)
-  const knh::DagEntry* dag = nullptr;    // five-role variant (f32, source -> SVF -> x*env -> post chains)
   const knh::WideEntry* wide = nullptr;  // 4/8 voice groups per workgroup, for banks larger than the chip's SIMD count
   int wide_waves = 0;                    // 0 = not used, else 4 or 8
   // a graph-shaped voice of SinWt oscillators and arithmetic run by the frame-parallel interpreter (kernels_interp.hip)
@@ -120,24 +100,10 @@ struct Bank final : knh_bank {
   // param_apply / set_delay calls addressed to later blocks of the next multi-block launch
   struct Call { uint8_t is_delay; uint16_t delay; uint32_t voice, stage, param, kind; double f; int64_t i; };
   std::vector<std::vector<Call>> future;  // [block_offset]
-  // Calls to a node wrapped in WrPreciseTiming (and in nothing that keeps host state of its own): one compact record per
-  // call, per block in arrival order.  When the block is assembled a single pass replays them against the armed delays
-  // and each node's queue state (precise_timing.rs:65-135) and writes the device events; no queue is ever materialised.
-  struct QRec {         // (the same bytes as knh_dev::DevRec: records of device-resolved stages are read by the resolver kernels as they are)
-    uint32_t voice;
-    uint16_t delay;     // set_delay_within_block_for_param value, when `arm` is set
-    uint16_t stage;     // (graph-shaped voices hold up to 512 stages, frame-parallel ones 4 096)
-    uint8_t param;
-    uint8_t kb;         // bits 0-3 ParameterValue kind, bit 4 arm, bit 5 has a value
-    uint16_t block;     // device-resolved stages: the block of the launch the call is addressed to
-    uint32_t pad;
-    union { double f; int64_t i; } v;
-    uint32_t kind() const { return kb & 15u; }
-    bool arm() const { return (kb & 0x10u) != 0; }
-    bool has_value() const { return (kb & 0x20u) != 0; }
-  };
-  static_assert(sizeof(QRec) == sizeof(knh_dev::DevRec) && offsetof(QRec, v) == offsetof(knh_dev::DevRec, value) &&
-                offsetof(QRec, block) == offsetof(knh_dev::DevRec, block) && offsetof(QRec, kb) == offsetof(knh_dev::DevRec, kb), "QRec is DevRec");
+  // Calls to a node wrapped in WrPreciseTiming (and in nothing that keeps host state of its own): one compact record
+  // (QRec, event_resolver.hpp) per call, per block in arrival order.  When the block is assembled a single pass replays them
+  // against the armed delays and each node's queue state (precise_timing.rs:65-135) and writes the device events; no queue
+  // is ever materialised.
   std::vector<std::vector<QRec>> qfuture;  // [block_offset]
   struct NodeQ { uint32_t epoch; uint16_t at; uint16_t taken : 15, blocked : 1; };  // a node's queue during the block `epoch`
   std::vector<NodeQ> node_q;               // [voice * n_wrapped + wrapped index of the stage]
@@ -148,41 +114,11 @@ struct Bank final : knh_bank {
     if (qfuture.size() <= block_offset) qfuture.resize(block_offset + 1);
     return qfuture[block_offset];
   }
-  // ---- change queues resolved on the device (kernels_events.hip) ---------------------------------------------------
-  // Stages wrapped in WrPreciseTiming whose setters need no host library call (SinWt, SinNumeric, constants and wr_mul,
-  // the EnvAsr / EnvAr times and triggers): the host appends the call's record to pinned memory and that is all; armed
-  // delays, queue order, capacity, the patches and the per-voice lists are the resolver kernels' (KNH_DEV_EVENTS=0: the host's,
-  // as in round 2).  Stages that do need the host (SvfFilter: tan, one-pole: exp, ...) keep the host path; a node's queue
-  // lives in exactly one of the two places.
+  // Which wrapped stages have their change queues resolved on the device (event_resolver.hpp): their records go to the
+  // resolver, every other wrapped stage's to qfuture (the host path).
   std::vector<uint8_t> stage_dev;             // [stage]
   std::vector<uint8_t> dev_class;             // [stage * 8 + param]: 1 + the value kind a device-resolved node's parameter takes, 0: not one
-  bool dev_events = false;
-  QRec* h_recs2[2] = {nullptr, nullptr};      // pinned; two alternate: the resolver of a launch reads one while the host fills the other
-  size_t h_recs_cap2[2] = {0, 0};
-  hipEvent_t recs_done[2] = {nullptr, nullptr};
-  bool recs_busy[2] = {false, false};
-  unsigned recs_parity = 0;
-  QRec* h_recs = nullptr;                     // = h_recs2[recs_parity]
-  size_t n_recs = 0;
-  uint32_t recs_max_block = 0;
-  knh_dev::DevStage* d_stages = nullptr;
-  uint16_t* d_armed = nullptr;
-  uint32_t *d_ev_cnt = nullptr, *d_rec_start = nullptr;
-  knh_dev::u64* d_keys = nullptr;
-  knh_dev::DevRec* d_recs = nullptr;          // the launch's records, copied by the counting kernel (one pass over PCIe)
-  size_t d_keys_cap = 0;
-  // The resolver runs on a stream of its own, so that it works on launch k + 1 while the voice kernel of launch k runs; the
-  // lists it makes therefore come in two sets, used alternately: a set is rewritten only after the voice kernel that read it
-  // has finished (lists_free), and a voice kernel starts only when its set is complete (recs_done of that launch).
-  hipStream_t ev_stream = nullptr;
-  hipEvent_t lists_free[2] = {nullptr, nullptr};
-  bool lists_busy[2] = {false, false};
-  uint32_t* d_out_start2[2] = {nullptr, nullptr};
-  Event* d_out_events2[2] = {nullptr, nullptr};
-  size_t d_out_cap2[2] = {0, 0};
-  unsigned out_parity = 0;
-  int out_in_use = -1;                        // the set the voice kernel being launched reads
-  uint32_t* h_ev_overflow = nullptr;          // mapped pinned: a resolver kernel found a change queue full (looked at by the next process call)
+  DevEventResolver resolver;
   static bool dev_resolvable_kind(uint16_t kind) {
     switch (kind) {
       case KNH_STAGE_SIN_WT: case KNH_STAGE_SIN_NUMERIC: case KNH_STAGE_MUL_ENV_ASR: case KNH_STAGE_MUL_ENV_AR:
@@ -191,117 +127,9 @@ struct Bank final : knh_bank {
       default: return false;
     }
   }
-  int dev_reserve(size_t more) {  // room for `more` records in the buffer being filled
-    const unsigned b = recs_parity;
-    if (n_recs + more <= h_recs_cap2[b]) return KNH_OK;
-    const size_t cap = std::max<size_t>((n_recs + more) * 2, 16384);
-    QRec* fresh = nullptr;
-    KNH_HIP(hipSetDevice(device));
-    KNH_HIP(hipHostMalloc(&fresh, cap * sizeof(QRec)));
-    if (n_recs) std::memcpy(fresh, h_recs2[b], n_recs * sizeof(QRec));
-    if (h_recs2[b]) KNH_HIP(hipHostFree(h_recs2[b]));  // (the buffer being filled is not one a kernel reads)
-    h_recs2[b] = fresh;
-    h_recs_cap2[b] = cap;
-    h_recs = fresh;
-    return KNH_OK;
-  }
-  int push_rec(uint32_t block_offset, QRec r) {
-    if (!stage_dev[r.stage]) { qblock(block_offset).push_back(r); return KNH_OK; }
-    int rc = dev_reserve(1);
-    if (rc != KNH_OK) return rc;
-    r.block = static_cast<uint16_t>(block_offset);
-    h_recs[n_recs++] = r;
-    recs_max_block = std::max(recs_max_block, block_offset);
-    return KNH_OK;
-  }
-  // The launch's records -> the per-voice event lists in device memory, merged with the host-made list (ev_start / events,
-  // pinned, or null).  Enqueued on `s` in front of the voice kernel.
-  int resolve_on_device(hipStream_t s, uint32_t n_blocks, uint32_t fb, uint32_t fe, bool have_host, size_t host_total) {
-    const unsigned b = recs_parity;
-    size_t n_now = n_recs;
-    if (recs_max_block >= n_blocks) {  // calls addressed beyond this launch: they wait, in the other buffer, for the next one
-      const unsigned o = b ^ 1u;
-      if (recs_busy[o]) { KNH_HIP(hipEventSynchronize(recs_done[o])); recs_busy[o] = false; }
-      size_t keep = 0, later = 0;
-      for (size_t i = 0; i < n_recs; ++i) later += h_recs[i].block >= n_blocks;
-      if (later > h_recs_cap2[o]) {
-        if (h_recs2[o]) KNH_HIP(hipHostFree(h_recs2[o]));
-        h_recs2[o] = nullptr;
-        h_recs_cap2[o] = std::max<size_t>(later * 2, 16384);
-        KNH_HIP(hipHostMalloc(&h_recs2[o], h_recs_cap2[o] * sizeof(QRec)));
-      }
-      later = 0;
-      uint32_t mx = 0;
-      for (size_t i = 0; i < n_recs; ++i) {
-        if (h_recs[i].block >= n_blocks) {
-          QRec r = h_recs[i];
-          r.block = static_cast<uint16_t>(r.block - n_blocks);
-          mx = std::max<uint32_t>(mx, r.block);
-          h_recs2[o][later++] = r;
-        } else {
-          h_recs[keep++] = h_recs[i];
-        }
-      }
-      n_now = keep;
-      n_recs = later;  // what the next launch starts with
-      recs_max_block = mx;
-    } else {
-      n_recs = 0;
-      recs_max_block = 0;
-    }
-    const unsigned set = out_parity;
-    out_parity ^= 1u;
-    if (n_now > d_keys_cap) {
-      KNH_HIP(hipStreamSynchronize(ev_stream));
-      if (d_keys) KNH_HIP(hipFree(d_keys));
-      if (d_recs) KNH_HIP(hipFree(d_recs));
-      d_keys = nullptr; d_recs = nullptr;
-      d_keys_cap = std::max<size_t>(n_now * 2, 16384);
-      KNH_HIP(hipMalloc(&d_keys, d_keys_cap * sizeof(knh_dev::u64)));
-      KNH_HIP(hipMalloc(&d_recs, d_keys_cap * sizeof(knh_dev::DevRec)));
-    }
-    if (host_total + n_now > d_out_cap2[set]) {
-      if (lists_busy[set]) { KNH_HIP(hipEventSynchronize(lists_free[set])); lists_busy[set] = false; }
-      KNH_HIP(hipStreamSynchronize(ev_stream));
-      if (d_out_events2[set]) KNH_HIP(hipFree(d_out_events2[set]));
-      d_out_events2[set] = nullptr;
-      d_out_cap2[set] = std::max<size_t>((host_total + n_now) * 2, 16384);
-      KNH_HIP(hipMalloc(&d_out_events2[set], d_out_cap2[set] * sizeof(Event)));
-    }
-    if (lists_busy[set]) { KNH_HIP(hipStreamWaitEvent(ev_stream, lists_free[set], 0)); lists_busy[set] = false; }
-    knh_dev::EventResolveArgs ra{};
-    ra.recs = reinterpret_cast<const knh_dev::DevRec*>(h_recs2[b]);
-    ra.n_recs = static_cast<uint32_t>(n_now);
-    ra.stages = d_stages;
-    ra.n_voices = nv;
-    ra.block_size = static_cast<uint32_t>(block_size);
-    ra.frame_begin = fb;
-    ra.frame_end = fe;
-    ra.n_blocks = n_blocks;
-    ra.sample_rate = sample_rate;
-    ra.f64 = sizeof(F) == 8 ? 1u : 0u;
-    ra.f2pi = f2pi;
-    ra.armed = d_armed;
-    ra.host_start = have_host ? h_ev_start : nullptr;
-    ra.host_events = h_events;
-    ra.cnt = d_ev_cnt;
-    ra.val_cnt = d_ev_cnt + nv;
-    ra.cursor = d_ev_cnt + 2 * static_cast<size_t>(nv);
-    ra.rec_start = d_rec_start;
-    ra.keys = d_keys;
-    ra.dev_recs = d_recs;
-    ra.out_start = d_out_start2[set];
-    ra.out_events = d_out_events2[set];
-    ra.overflow = h_ev_overflow;
-    KNH_HIP(knh::launch_resolve_events(ra, ev_stream));
-    KNH_HIP(hipEventRecord(recs_done[b], ev_stream));  // the records are read, and the lists complete: one event says both
-    recs_busy[b] = true;
-    KNH_HIP(hipStreamWaitEvent(s, recs_done[b], 0));  // the voice kernel reads this set
-    out_in_use = static_cast<int>(set);
-    // the host goes on filling the other buffer
-    recs_parity = b ^ 1u;
-    if (recs_busy[recs_parity]) { KNH_HIP(hipEventSynchronize(recs_done[recs_parity])); recs_busy[recs_parity] = false; }
-    h_recs = h_recs2[recs_parity];
+  int push_rec(uint32_t block_offset, const QRec& r) {
+    if (stage_dev[r.stage]) return resolver.push(block_offset, r);
+    qblock(block_offset).push_back(r);
     return KNH_OK;
   }
 
@@ -346,47 +174,21 @@ struct Bank final : knh_bank {
   F* h_out = nullptr;  // [channels][block] then 2 x u32 flags
   // Blocking calls with a host destination (knh_bank_process_block: the call the reference makes once per block) hand the
   // mixed block over without a copy command: the fold kernel writes it into h_out -- mapped pinned host memory -- and then
-  // an epoch number into h_done, which the host polls (knh_dev::HostDone).  KNH_MAPPED_OUT=0: the copies and the stream
-  // wait of round 2 (A/B runs).
+  // an epoch number into h_done, which the host polls (knh_dev::HostDone).  Every other call takes the copies and the
+  // stream wait.
   uint32_t* h_done = nullptr;        // pinned: [0] epoch, [1] flags[0], [2] flags[1]
   uint32_t* d_fold_count = nullptr;  // device: workgroups of the fold kernel that are through
   uint32_t done_epoch = 0;
-  bool mapped_out = true;
-  // ---- the per-block call on a resident launch (voice_chain.hpp, Resident) ------------------------------------------------
-  // knh_bank_process_block -- the call the reference makes once per block (Task::run, knaster_graph/src/task.rs:25-31) -- of
-  // a bank on the pipelined kernel form with a mixer wavefront: the first such call launches the kernel, and it stays until
-  // something else needs the device state (any other entry point that reads it or launches), another bank launches on the
-  // device, or the host stays away for KNH_RESIDENT_IDLE_US (default 5 000).  KNH_RESIDENT=0: never (a launch per call).
-  int res_policy = -1;                 // -1 not decided, 0 never, 1 where possible
-  bool res_on = false;                 // a resident kernel is running (or has ended by itself) on own_stream
-  uint32_t res_epoch = 0;              // the last epoch handed out (24 bits)
-  uint64_t* res_bell = nullptr;        // the command word as the host writes it ...
-  uint64_t* res_bell_dev = nullptr;    // ... and as the kernel reads it (the same fine-grained device word behind a large BAR; else mapped pinned memory)
-  bool res_bell_is_device = false;
-  uint64_t* d_res_relay = nullptr;
-  uint64_t *d_res_rows = nullptr, *d_res_wg_flags = nullptr, *d_res_group_rows = nullptr, *d_res_group_flags = nullptr;  // granules (voice_chain.hpp)
-  uint32_t *d_res_arrivals = nullptr, *d_res_group_arrivals = nullptr;
-  hipStream_t res_stream = nullptr;    // the fold server runs beside the voice kernel
-  uint64_t* h_res_out = nullptr;       // mapped pinned: the block as the fold server's root leaves it, granules {sample bits, tag}: [plane][block_size][W], then the flags granule
-  uint32_t* h_res_done = nullptr;      // mapped pinned: epoch, done count, running count
-  uint32_t res_max_tiles = 0;
-  uint32_t res_cooldown = 0;           // calls to sit out after another bank asked this one to leave
-  uint64_t res_idle_ticks = 500000;    // 5 ms of the 100 MHz clock
-  uint64_t res_calls = 0, res_launches = 0;
-  void resident_stats(uint64_t* calls, uint64_t* launches) override { if (calls) *calls = res_calls; if (launches) *launches = res_launches; }
-  // diagnostics: the last call's milestones on the device clock (ticks of 10 ns): the voice kernel saw the command, the fold
-  // server's root did, its first tile was complete, its last tile was, it had written everything
-  void resident_trace(uint64_t* five) override {
-    for (int k = 0; k < 5; ++k) five[k] = 0;
-    if (!h_res_done) return;
-    for (int k = 0; k < 5; ++k) std::memcpy(&five[k], h_res_done + 8 + 2 * k, 8);
-  }
+  // the per-block call on a resident launch (resident_call.hpp); which kernel forms can be resident is decided here
+  ResidentCall<F> resident;
+  void resident_stats(uint64_t* calls, uint64_t* launches) override { resident.stats(calls, launches); }
+  void resident_trace(uint64_t* five) override { resident.trace(five); }
   bool jit_pipe = false;  // the run-time fused kernel is a pipeline (mixer form, short tiles), not a one-wavefront kernel
   bool res_possible() const {
     // Kernel forms in which every workgroup can be resident at once and the fold server can take the rows: the pipelined forms
     // with a mixer wavefront and one voice group per workgroup, and the one-wavefront kernel (pre-built or fused at run time);
     // up to 256 voice groups (the server folds 8 x 32 rows), tree mix, no bank inputs (their upload rides in a stream).
-    if (interp || dag || uses_input || desc.mix_mode != KNH_MIX_TREE) return false;
+    if (interp || uses_input || desc.mix_mode != KNH_MIX_TREE) return false;
     if ((nv + 63u) / 64u > 256u || block_size > 4096) return false;
     if (wide_waves != 0) return false;
     if (jit) return true;
@@ -400,99 +202,6 @@ struct Bank final : knh_bank {
     if (jit || !pipe) return 64u;                             // the one-wavefront kernel hands its rows over in 64-frame tiles
     const bool big = pipe->long_tiles != 0;
     return sizeof(F) == 8 ? (big ? 32u : 16u) : (big ? 64u : 32u);
-  }
-  static hipError_t launch_res_server(const knh_dev::ResServerArgs<float>& a, hipStream_t s) { return knh::launch_res_server_f32(a, s); }
-  static hipError_t launch_res_server(const knh_dev::ResServerArgs<double>& a, hipStream_t s) { return knh::launch_res_server_f64(a, s); }
-  static void res_leave_thunk(knh_bank* b) { static_cast<Bank<F>*>(b)->res_leave_locked(true); }
-  // the caller holds resident_slot().mu
-  int res_leave_locked(bool evicted) {
-    if (!res_on) return KNH_OK;
-    KNH_HIP(hipSetDevice(device));
-    res_epoch = (res_epoch + 1u) & 0xFFFFFFu;
-    const uint64_t cmd = static_cast<uint64_t>(res_epoch) | (1ull << 58);
-    __atomic_store_n(res_bell, cmd, __ATOMIC_RELEASE);
-#if defined(__x86_64__)
-    if (res_bell_is_device) __builtin_ia32_sfence();
-#endif
-    hipError_t e = hipStreamSynchronize(own_stream);  // (bounded on the device side: every wait of the kernels is)
-    const hipError_t e2 = hipStreamSynchronize(res_stream);
-    if (e == hipSuccess) e = e2;
-    res_on = false;
-    ResidentSlot& rs = resident_slot();
-    if (device >= 0 && device < 64 && rs.owner[device] == this) { rs.owner[device] = nullptr; rs.leave[device] = nullptr; }
-    if (evicted) res_cooldown = 256;
-    if (e != hipSuccess) return fail(KNH_ERR_DEVICE, std::string("the resident kernel ended with an error: ") + hipGetErrorString(e));
-    return KNH_OK;
-  }
-  int res_leave() {
-    if (!res_on) return KNH_OK;
-    std::lock_guard<std::mutex> lock(resident_slot().mu);
-    return res_leave_locked(false);
-  }
-  // before anything is launched on this device by this bank: no other bank's resident kernel is in the way
-  void res_make_room() {
-    ResidentSlot& rs = resident_slot();
-    if (device < 0 || device >= 64) return;
-    std::lock_guard<std::mutex> lock(rs.mu);
-    if (rs.owner[device] && rs.owner[device] != this) rs.leave[device](rs.owner[device]);
-  }
-  int res_alloc() {
-    if (h_res_done) return KNH_OK;
-    KNH_HIP(hipSetDevice(device));
-    int large_bar = 0;
-    (void)hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, device);
-    const char* be = std::getenv("KNH_RESIDENT_BELL");  // "host": the command word in pinned host memory whatever the BAR
-    if (large_bar && !(be && be[0] == 'h')) {
-      void* p = nullptr;
-      if (hipExtMallocWithFlags(&p, 64, hipDeviceMallocFinegrained) == hipSuccess && p) {
-        KNH_HIP(hipMemset(p, 0xFF, 64));
-        KNH_HIP(hipDeviceSynchronize());
-        res_bell = res_bell_dev = static_cast<uint64_t*>(p);
-        res_bell_is_device = true;
-      }
-    }
-    if (!res_bell) {
-      KNH_HIP(hipHostMalloc(&res_bell, 64, hipHostMallocMapped | hipHostMallocCoherent));
-      res_bell_dev = res_bell;
-      *res_bell = ~0ull;
-    }
-    res_max_tiles = static_cast<uint32_t>((block_size + res_tile_frames() - 1) / res_tile_frames());
-    {
-      // granules: every one starts with a tag no call will ever carry (all ones)
-      const size_t w = sizeof(F) == 8 ? 2 : 1, rows = (nv + 63) / 64;
-      const size_t n_rows = static_cast<size_t>(res_max_tiles) * 2 * rows * 64 * w, n_group = static_cast<size_t>(res_max_tiles) * 2 * 8 * 64 * w;
-      KNH_HIP(hipMalloc(&d_res_rows, n_rows * 8));
-      KNH_HIP(hipMemset(d_res_rows, 0xFF, n_rows * 8));
-      KNH_HIP(hipMalloc(&d_res_group_rows, n_group * 8));
-      KNH_HIP(hipMemset(d_res_group_rows, 0xFF, n_group * 8));
-      KNH_HIP(hipMalloc(&d_res_wg_flags, rows * 8));
-      KNH_HIP(hipMemset(d_res_wg_flags, 0xFF, rows * 8));
-      KNH_HIP(hipMalloc(&d_res_group_flags, 64));
-      KNH_HIP(hipMemset(d_res_group_flags, 0xFF, 64));
-      KNH_HIP(hipMalloc(&d_res_arrivals, (static_cast<size_t>(res_max_tiles) + 1) * 8 * sizeof(uint32_t)));
-      KNH_HIP(hipMemset(d_res_arrivals, 0, (static_cast<size_t>(res_max_tiles) + 1) * 8 * sizeof(uint32_t)));
-      KNH_HIP(hipMalloc(&d_res_group_arrivals, (static_cast<size_t>(res_max_tiles) + 1) * sizeof(uint32_t)));
-      KNH_HIP(hipMemset(d_res_group_arrivals, 0, (static_cast<size_t>(res_max_tiles) + 1) * sizeof(uint32_t)));
-      // The fold server must run BESIDE the voice kernel, so it must not sit behind it in one hardware queue (the runtime
-      // multiplexes streams onto a few).  A stream of another priority gets a queue of its own; res_launch checks that both
-      // kernels have started before anything relies on it.
-      int prio_low = 0, prio_high = 0;
-      (void)hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);
-      if (hipStreamCreateWithPriority(&res_stream, hipStreamNonBlocking, prio_high) != hipSuccess) KNH_HIP(hipStreamCreateWithFlags(&res_stream, hipStreamNonBlocking));
-    }
-    KNH_HIP(hipMalloc(&d_res_relay, 1024));  // the command word, and (words 16 ..) a call's range events (voice_chain.hpp RES_RELAY_RANGES)
-    KNH_HIP(hipMemset(d_res_relay, 0xFF, 1024));
-    {
-      const size_t n_gran = 2 * static_cast<size_t>(block_size) * (sizeof(F) == 8 ? 2 : 1) + 8;
-      KNH_HIP(hipHostMalloc(&h_res_out, n_gran * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent));
-      std::memset(h_res_out, 0xFF, n_gran * sizeof(uint64_t));  // (a tag no call carries)
-    }
-    KNH_HIP(hipHostMalloc(&h_res_done, 256, hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(h_res_done, 0, 256);
-    h_res_done[0] = 0xFFFFFFFFu; h_res_done[1] = 0u; h_res_done[2] = 0u; h_res_done[4] = 0xFFFFFFFFu; h_res_done[5] = 0xFFFFFFFFu;
-    KNH_HIP(hipDeviceSynchronize());
-    if (const char* e = std::getenv("KNH_RESIDENT_IDLE_US")) { const long us = std::atol(e); if (us >= 50 && us <= 2000000) res_idle_ticks = static_cast<uint64_t>(us) * 100u; }
-    return KNH_OK;
   }
   void fill_launch_args(VoiceKernelArgs<F>& a, uint32_t n_blocks, uint32_t fb, uint32_t fe) {
     a.state = d_state;
@@ -522,199 +231,6 @@ struct Bank final : knh_bank {
     a.flags = d_flags;
     a.res = knh_dev::Resident{};
   }
-  // the caller holds resident_slot().mu; the command word already carries `first_epoch`'s command or will
-  static bool res_debug() { static const bool on = std::getenv("KNH_DEBUG_RES") != nullptr; return on; }
-  int res_launch(uint32_t first_epoch) {
-    if (res_debug()) std::fprintf(stderr, "[knh resident] launch, first epoch %u, %u voices, tile %u frames\n", first_epoch, nv, res_tile_frames());
-    VoiceKernelArgs<F> a;
-    fill_launch_args(a, 1, 0, static_cast<uint32_t>(block_size));
-    a.flags = d_flags + 32;  // (a third set: the two the ordinary launches alternate stay as their fold kernels left them)
-    a.res.bell = reinterpret_cast<const knh_dev::u64*>(res_bell_dev);
-    a.res.relay = reinterpret_cast<knh_dev::u64*>(d_res_relay);
-    a.res.rows = reinterpret_cast<knh_dev::u64*>(d_res_rows);
-    a.res.wg_flags = reinterpret_cast<knh_dev::u64*>(d_res_wg_flags);
-    for (int k = 0; k < 2; ++k) { a.res.ev_start[k] = h_ev_start2[k]; a.res.events[k] = h_events2[k]; }
-    a.res.idle_ticks = res_idle_ticks;
-    a.res.host_started = h_res_done + 4;
-    a.res.first_epoch = first_epoch;
-    a.res.max_tiles = res_max_tiles;
-    // (0: only workgroup 0 reads the host's word, also when it lives in device memory.  With every workgroup reading it, a
-    // command that arrives just as workgroup 0 gives up waiting would be taken by some workgroups and not by it: the relay makes
-    // workgroup 0 the one place where "this command" or "leave" is decided.  Costs 0.5 us per call.)
-    a.res.bell_is_device = 0u;
-    {  // the fold server first: a handful of wavefronts that will sit beside the voice kernel's workgroups
-      knh_dev::ResServerArgs<F> sa{};
-      sa.relay = reinterpret_cast<const knh_dev::u64*>(d_res_relay);
-      sa.bell = nullptr;  // (as for the voice kernel: the relay decides)
-      sa.rows = reinterpret_cast<const knh_dev::u64*>(d_res_rows);
-      sa.wg_flags = reinterpret_cast<const knh_dev::u64*>(d_res_wg_flags);
-      sa.group_rows = reinterpret_cast<knh_dev::u64*>(d_res_group_rows);
-      sa.group_flags = reinterpret_cast<knh_dev::u64*>(d_res_group_flags);
-      sa.host_out = reinterpret_cast<knh_dev::u64*>(h_res_out);
-      sa.host_done = h_res_done;
-      sa.idle_ticks = res_idle_ticks;
-      sa.first_epoch = first_epoch;
-      sa.n_rows = (nv + 63) / 64;
-      sa.planes = pan ? 2u : 1u;
-      sa.out_channels = desc.out_channels;
-      sa.block_size = static_cast<uint32_t>(block_size);
-      sa.tile_frames = res_tile_frames();
-      KNH_HIP(launch_res_server(sa, res_stream));
-    }
-    KNH_HIP(launch_voice(a, (nv + 63) / 64, own_stream));
-    res_on = true;
-    res_launches += 1;
-    ResidentSlot& rs = resident_slot();
-    if (device >= 0 && device < 64) { rs.owner[device] = this; rs.leave[device] = &Bank<F>::res_leave_thunk; }
-    // Both kernels are running?  (If the two streams share a hardware queue, the second kernel waits for the first to END --
-    // which, for kernels that wait for each other's work, is never in time.  Then this bank keeps to a launch per call.)
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint64_t spin = 0;; ++spin) {
-      if (__atomic_load_n(&h_res_done[4], __ATOMIC_ACQUIRE) == first_epoch && __atomic_load_n(&h_res_done[5], __ATOMIC_ACQUIRE) == first_epoch) break;
-      if ((spin & 0xFFu) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.05) {
-        if (res_debug()) std::fprintf(stderr, "[knh resident] handshake failed: voice %u server %u (want %u)\n", h_res_done[4], h_res_done[5], first_epoch);
-        res_policy = 0;
-        warn("the resident voice kernel and its fold server did not start side by side (a shared hardware queue?): this bank launches per call");
-        int rc = res_leave_locked(false);
-        return rc != KNH_OK ? rc : KNH_ERR_UNSUPPORTED_CHAIN;  // (res_call: fall back to an ordinary launch)
-      }
-#if defined(__x86_64__)
-      __builtin_ia32_pause();
-#endif
-    }
-    return KNH_OK;
-  }
-  // One block through the resident kernel: frames [fb, fe) of the block into out_host ([channels][block_size], written at
-  // their place).  The event list of the call (if any) is the pinned list upload_events has just made.
-  int res_call(uint32_t fb, uint32_t fe, bool have_events, void* out_host, uint32_t* out_flags) {
-    ResidentSlot& rs = resident_slot();
-    std::lock_guard<std::mutex> lock(rs.mu);
-    KNH_HIP(hipSetDevice(device));
-    if (device >= 0 && device < 64 && rs.owner[device] && rs.owner[device] != this) rs.leave[device](rs.owner[device]);
-    const uint64_t payload = (static_cast<uint64_t>(fb) << 24) | (static_cast<uint64_t>(fe) << 40) | (have_events ? 1ull << 56 : 0ull) |
-                             (have_events && list_in_use == 1 ? 1ull << 57 : 0ull) | (have_events ? static_cast<uint64_t>(res_n_ranges & 15u) << 59 : 0ull);
-    if (have_events && list_in_use >= 0) { list_busy[list_in_use] = false; list_in_use = -1; }  // (no stream order to keep: the call is over when this returns)
-    uint32_t epoch = 0;
-    auto ring = [&]() -> int {  // the next epoch's command; a kernel to take it if there is none
-      res_epoch = (res_epoch + 1u) & 0xFFFFFFu;
-      epoch = res_epoch;
-      if (!res_on) { int rc = res_launch(epoch); if (rc != KNH_OK) return rc; }  // (KNH_ERR_UNSUPPORTED_CHAIN: no resident launch for this bank after all)
-#if defined(__x86_64__)
-      __builtin_ia32_sfence();  // the event list is in memory before the word that announces it
-#endif
-      __atomic_store_n(res_bell, static_cast<uint64_t>(epoch) | payload, __ATOMIC_RELEASE);
-#if defined(__x86_64__)
-      if (res_bell_is_device) __builtin_ia32_sfence();
-#endif
-      return KNH_OK;
-    };
-    { int rc = ring(); if (rc != KNH_OK) return rc; }
-    res_calls += 1;
-    const auto t0 = std::chrono::steady_clock::now();
-    // Waits for something the device stores (`ready`): 0 = there; kRestart = the kernel had ended by itself and the command has
-    // gone out again under a new epoch (whatever was read so far belongs to no call: start over); anything else = an error.
-    constexpr int kRestart = -12345;
-    auto wait_for = [&](auto&& ready) -> int {
-      for (uint64_t spin = 1;; ++spin) {
-        if (ready()) return 0;
-        if ((spin & 0x3FFFu) == 0) {
-          const hipError_t q = hipStreamQuery(own_stream);
-          if (q == hipSuccess) {
-            // The kernel has ended by itself (the host was away for longer than its patience) just as this command was written.
-            // Its workgroup 0 left "leave" in the relay under THIS epoch, so the command goes out again under the next one, to a
-            // new launch.
-            if (ready()) return 0;
-            if (res_debug()) std::fprintf(stderr, "[knh resident] the kernel ended without answering epoch %u (done word %u, %.3f ms into the call, server stream %s; root wavefronts at %x %x %x %x)\n", epoch, h_res_done[0],
-                                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), hipStreamQuery(res_stream) == hipSuccess ? "idle" : "busy",
-                                          h_res_done[20], h_res_done[21], h_res_done[22], h_res_done[23]);
-            // (its fold server has then heard "leave" over the relay too.  A server that is still busy was in the middle of a
-            // call: the voice kernel took the command, and taking it again would render the block twice.)
-            hipError_t qs = hipStreamQuery(res_stream);
-            for (int k = 0; k < 200 && qs == hipErrorNotReady; ++k) { std::this_thread::sleep_for(std::chrono::microseconds(500)); qs = hipStreamQuery(res_stream); }
-            res_on = false;
-            if (qs != hipSuccess) {
-              res_policy = 0;
-              (void)res_leave_locked(false);
-              return fail(KNH_ERR_DEVICE, "the resident voice kernel ended in the middle of a call (its mix never arrived)");
-            }
-            int rc = ring();
-            if (rc != KNH_OK) return rc;
-            return kRestart;
-          } else if (q != hipErrorNotReady) {
-            res_on = false;
-            return fail(KNH_ERR_DEVICE, std::string("hipStreamQuery: ") + hipGetErrorString(q));
-          }
-          if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 10.0) {
-            return fail(KNH_ERR_DEVICE, "the resident kernel did not answer within 10 s");
-          }
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-      }
-    };
-    // The block arrives tile by tile as granules {sample bits, tag = epoch << 8 | tile}: every frame is taken the moment its
-    // tag is there (the early tiles while the kernel is still at the later ones), a mono mix copied to every channel; the
-    // call's done / running counts come as one more granule behind the last tile.
-    constexpr size_t W = sizeof(F) == 8 ? 2 : 1;
-    const uint32_t n = fe - fb, tf = res_tile_frames(), planes = fold_planes;
-    F* const out = static_cast<F*>(out_host);
-    uint64_t flag_word = 0;
-    for (bool again = true; again;) {
-      again = false;
-      for (uint32_t rel = 0; rel < n && !again; ++rel) {
-        const uint32_t tag = (epoch << 8) | ((rel / tf) & 0xFFu);
-        for (uint32_t p = 0; p < planes && !again; ++p) {
-          volatile uint64_t* g = h_res_out + (static_cast<size_t>(p) * block_size + fb + rel) * W;
-          // (the device's stores took these lines out of the CPU's caches: a tile that has landed is eight cache misses in a row
-          // unless they are asked for together -- 0.7 us at the end of every call)
-          if ((reinterpret_cast<uintptr_t>(g) & 63u) == 0) {
-            __builtin_prefetch(const_cast<const uint64_t*>(g) + 8, 0, 3);
-            __builtin_prefetch(const_cast<const uint64_t*>(g) + 16, 0, 3);
-            __builtin_prefetch(const_cast<const uint64_t*>(g) + 24, 0, 3);
-            __builtin_prefetch(const_cast<const uint64_t*>(g) + 32, 0, 3);
-          }
-          uint64_t w0 = 0, w1 = 0;
-          auto ready = [&]() -> bool {
-            w0 = __atomic_load_n(g, __ATOMIC_RELAXED);
-            if (static_cast<uint32_t>(w0 >> 32) != tag) return false;
-            if (W == 2) { w1 = __atomic_load_n(g + 1, __ATOMIC_RELAXED); if (static_cast<uint32_t>(w1 >> 32) != tag) return false; }
-            return true;
-          };
-          if (!ready()) {
-            const int rc = wait_for(ready);
-            if (rc == kRestart) { again = true; break; }
-            if (rc != 0) return rc;
-          }
-          F v;
-          if (W == 1) { const uint32_t bits = static_cast<uint32_t>(w0); std::memcpy(&v, &bits, sizeof(F) < 4 ? sizeof(F) : 4); }
-          else { const uint64_t bits = (w0 & 0xFFFFFFFFull) | (w1 << 32); std::memcpy(&v, &bits, sizeof(F)); }
-          if (planes == 2) out[static_cast<size_t>(p) * block_size + fb + rel] = v;
-          else for (uint32_t c = 0; c < desc.out_channels; ++c) out[static_cast<size_t>(c) * block_size + fb + rel] = v;
-        }
-      }
-      if (again) continue;
-      volatile uint64_t* gf = h_res_out + static_cast<size_t>(planes) * block_size * W;
-      const uint32_t ftag = (epoch << 8) | 255u;
-      auto fready = [&]() -> bool { flag_word = __atomic_load_n(gf, __ATOMIC_RELAXED); return static_cast<uint32_t>(flag_word >> 32) == ftag; };
-      if (!fready()) {
-        const int rc = wait_for(fready);
-        if (rc == kRestart) { again = true; continue; }
-        if (rc != 0) return rc;
-      }
-    }
-    if (out_flags) {
-      uint32_t fl = 0;
-      const uint32_t n_done = static_cast<uint32_t>(flag_word) & 0xFFFFu, n_run = (static_cast<uint32_t>(flag_word) >> 16) & 0xFFFFu;
-      if (n_done) fl |= KNH_FLAG_ANY_DONE;
-      bool has_env = false;
-      for (const StageInfo& st : stages) has_env = has_env || st.kind == KNH_STAGE_MUL_ENV_ASR || st.kind == KNH_STAGE_MUL_ENV_AR || st.kind == KNH_STAGE_MUL_ENVELOPE ||
-                          st.kind == KNH_STAGE_BUFFER_READER;
-      if (has_env && n_run == 0) fl |= KNH_FLAG_ALL_DONE;
-      *out_flags = fl;
-    }
-    return KNH_OK;
-  }
   // timing
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> timing_pool;
@@ -722,42 +238,24 @@ struct Bank final : knh_bank {
   double timing_ms = 0.0;
   uint64_t timing_launches = 0;
 
+  // What may still read or write the bank's memory is idle before any of it is freed: the bank's own stream (a resident
+  // kernel is asked to leave first), the resolver's, and the stream the last launch was given.  The members that own
+  // resources of their own (resident, resolver) free them after this body, when those streams are idle too.
   ~Bank() override {
     if (device >= 0) (void)hipSetDevice(device);
-    (void)res_leave();
-    {
-      void* rdev[] = {res_bell_is_device ? static_cast<void*>(res_bell) : nullptr, d_res_relay, d_res_rows, d_res_wg_flags, d_res_group_rows, d_res_group_flags, d_res_arrivals, d_res_group_arrivals};
-      if (res_stream) { (void)hipStreamSynchronize(res_stream); (void)hipStreamDestroy(res_stream); }
-      void* rhost[] = {res_bell_is_device ? nullptr : static_cast<void*>(res_bell), h_res_out, h_res_done};
-      if (own_stream) (void)hipStreamSynchronize(own_stream);
-      for (void* p : rdev) if (p) (void)hipFree(p);
-      for (void* p : rhost) if (p) (void)hipHostFree(p);
-    }
-    // everything that may still read or write this bank's memory has finished before any of it is freed: the bank's own
-    // stream, the resolver's (its kernels read the pinned record and event lists), and the stream the last launch was given
+    (void)resident.leave();
     if (own_stream) (void)hipStreamSynchronize(own_stream);
-    if (ev_stream) (void)hipStreamSynchronize(ev_stream);
+    resolver.quiesce();
     if (flags_stream_set && flags_stream != own_stream) (void)hipStreamSynchronize(flags_stream);
     void* dev_ptrs[] = {d_state, d_sine, d_seg_table, d_delay, d_buffer, d_partials, d_out, d_voices, d_done, d_flags, d_input, d_prog, d_sin_slots, d_fold_count};
     for (void* p : dev_ptrs)
       if (p) (void)hipFree(p);
-    void* host_ptrs[] = {h_ev_start2[0], h_ev_start2[1], h_events2[0], h_events2[1], h_out, h_input, h_done, h_ev_overflow};
+    void* host_ptrs[] = {h_ev_start2[0], h_ev_start2[1], h_events2[0], h_events2[1], h_out, h_input, h_done};
     for (void* p : host_ptrs)
       if (p) (void)hipHostFree(p);
     for (hipEvent_t e : list_done)
       if (e) (void)hipEventDestroy(e);
     if (in_copied) (void)hipEventDestroy(in_copied);
-    for (hipEvent_t e : recs_done)
-      if (e) (void)hipEventDestroy(e);
-    if (ev_stream) (void)hipStreamSynchronize(ev_stream);
-    void* ev_dev[] = {d_stages, d_armed, d_ev_cnt, d_rec_start, d_out_start2[0], d_out_start2[1], d_keys, d_recs, d_out_events2[0], d_out_events2[1]};
-    for (void* p : ev_dev)
-      if (p) (void)hipFree(p);
-    for (hipEvent_t e : lists_free)
-      if (e) (void)hipEventDestroy(e);
-    if (ev_stream) (void)hipStreamDestroy(ev_stream);
-    for (QRec* p : h_recs2)
-      if (p) (void)hipHostFree(p);
     for (auto& p : timing_pool) {
       (void)hipEventDestroy(p.first);
       (void)hipEventDestroy(p.second);
@@ -853,48 +351,7 @@ struct Bank final : knh_bank {
       bool can = !entry && bs <= 1024 && stages.size() <= 4096;
       for (const StageInfo& S : stages) can = can && S.flags == 0 && S.dcpb == 0 && S.ar_param == 0 && std::strchr("Wmasdvq*+-/", kKinds[S.kind].sig) != nullptr;
       if (can && !(ie && ie[0] == '0')) {
-        h_prog.clear();
-        size_t si = 0;
-        const char* p = signature.c_str();
-        while (*p && *p != '#') {
-          knh_dev::InterpOp op{};
-          const char c = *p++;
-          int v[3] = {-1, -1, -1};
-          if (*p == '@') {
-            ++p;
-            for (int k = 0; k < 3; ++k) {
-              if (*p == '_') { ++p; } else { v[k] = 0; while (*p >= '0' && *p <= '9') v[k] = v[k] * 10 + (*p++ - '0'); }
-              if (*p == ',') ++p;
-            }
-          }
-          switch (c) {
-            case 'W': op.kind = knh_dev::INTERP_SIN_WT; break;
-            case 'm': op.kind = knh_dev::INTERP_VAL_MUL; break;
-            case 'a': op.kind = knh_dev::INTERP_VAL_ADD; break;
-            case 's': op.kind = knh_dev::INTERP_VAL_SUB; break;
-            case 'd': op.kind = knh_dev::INTERP_VAL_DIV; break;
-            case 'v': op.kind = knh_dev::INTERP_VAL_VSUB; break;
-            case 'q': op.kind = knh_dev::INTERP_VAL_VDIV; break;
-            case '*': op.kind = knh_dev::INTERP_MATH_MUL; break;
-            case '+': op.kind = knh_dev::INTERP_MATH_ADD; break;
-            case '-': op.kind = knh_dev::INTERP_MATH_SUB; break;
-            default: op.kind = knh_dev::INTERP_MATH_DIV; break;
-          }
-          if (!signature_is_dag(signature)) {  // a plain chain: one signal, every stage works on it in place
-            v[0] = c == 'W' ? -1 : 0;
-            v[2] = 0;
-          }
-          if (si >= stages.size() || v[2] < 0 || (c != 'W' && v[0] < 0)) return fail(KNH_ERR_UNSUPPORTED_CHAIN, "interpreter: malformed graph signature");
-          op.a = static_cast<unsigned short>(v[0] < 0 ? 0 : v[0]);
-          op.b = static_cast<unsigned short>(v[1] < 0 ? 0 : v[1]);
-          op.o = static_cast<unsigned short>(v[2]);
-          op.slot = static_cast<uint32_t>(stages[si].slot_base);
-          h_prog.push_back(op);
-          ++si;
-        }
-        interp_sigs = *p == '#' ? static_cast<unsigned>(std::atoi(p + 1)) : (signature_is_dag(signature) ? 0u : 1u);
-        interp_out = h_prog.empty() ? 0u : h_prog.back().o;
-        if (si != stages.size() || interp_sigs == 0) return fail(KNH_ERR_UNSUPPORTED_CHAIN, "interpreter: malformed graph signature");
+        if (!parse_frame_program(signature, stages, &h_prog, &interp_sigs, &interp_out)) return fail(KNH_ERR_UNSUPPORTED_CHAIN, "interpreter: malformed graph signature");
         if (knh::interp_lds_bytes(static_cast<unsigned>(h_prog.size()), static_cast<unsigned>(n_slots), interp_sigs, static_cast<unsigned>(bs), sizeof(F) == 8) <= 158u * 1024u)
           interp = true;
         const char* fj = std::getenv("KNH_FRAME_JIT");
@@ -917,47 +374,7 @@ struct Bank final : knh_bank {
         }
       }
     }
-    env_ranks = 0;
-    if (signature_is_dag(signature)) {
-      // Which envelope's mark_done names the voice's done frame when several finish in one block: the last one in the
-      // reference's TASK order (graph_gen.rs:196-200), which for a graph is the order Graph::calculate_node_order sorts the
-      // nodes into (graph.rs:1938-2067): depth first from the output, a node's inputs in channel order, each node after
-      // everything it reads; nodes the output does not depend on come last, in the order they were pushed.
-      const int n = static_cast<int>(stages.size());
-      auto is_src = [&](int i) { return std::strchr("WNPUKOGBFI", kKinds[stages[i].kind].sig) != nullptr && !(stages[i].flags & KNH_STAGE_FLAG_AR_FREQ); };
-      auto node_output = [&](int k) { while (k + 1 < n && is_wrapper_kind(stages[k + 1].kind)) ++k; return k; };
-      std::vector<int> a(n, -1), b(n, -1);
-      for (int i = 0; i < n; ++i) {
-        if (is_math2_kind(stages[i].kind)) { a[i] = node_output(stages[i].input - 1); b[i] = node_output(stages[i].input2 - 1); }
-        else if (i > 0 && !is_src(i)) a[i] = stages[i].input ? node_output(stages[i].input - 1) : i - 1;
-        // an audio-rate parameter edge: followed after the node's input edges (graph.rs:1938-1980)
-        if (stages[i].ar_param && !is_math2_kind(stages[i].kind)) b[i] = node_output(stages[i].input2 - 1);
-      }
-      std::vector<int> order, state(n, 0), stack{n - 1};
-      while (!stack.empty()) {  // post-order, first operand first
-        const int k = stack.back();
-        if (state[k] == 0) { state[k] = 1; if (a[k] >= 0 && state[a[k]] == 0) { stack.push_back(a[k]); continue; } }
-        if (state[k] == 1) { state[k] = 2; if (b[k] >= 0 && state[b[k]] == 0) { stack.push_back(b[k]); continue; } }
-        if (state[k] == 2) { state[k] = 3; order.push_back(k); }
-        stack.pop_back();
-      }
-      for (int i = 0; i < n; ++i) if (state[i] == 0) order.push_back(i);
-      std::vector<int> rank(n, 0);
-      for (size_t r = 0; r < order.size(); ++r) rank[order[r]] = static_cast<int>(r);
-      std::vector<int> envs;
-      for (int i = 0; i < n; ++i)
-        if (stages[i].kind == KNH_STAGE_MUL_ENV_ASR || stages[i].kind == KNH_STAGE_MUL_ENV_AR || stages[i].kind == KNH_STAGE_MUL_ENVELOPE) envs.push_back(i);
-      bool in_list_order = true;
-      for (size_t j = 1; j < envs.size(); ++j) in_list_order = in_list_order && rank[envs[j - 1]] < rank[envs[j]];
-      if (!in_list_order && envs.size() <= 15) {
-        std::vector<int> by_rank(envs);
-        std::sort(by_rank.begin(), by_rank.end(), [&](int x, int y) { return rank[x] < rank[y]; });
-        for (size_t j = 0; j < envs.size(); ++j) {
-          const uint64_t place = 1 + static_cast<uint64_t>(std::find(by_rank.begin(), by_rank.end(), envs[j]) - by_rank.begin());
-          env_ranks |= place << (4 * j);
-        }
-      }
-    }
+    env_ranks = envelope_task_ranks(signature, stages);
     const char* jp = std::getenv("KNH_JIT_PIPE");
     // (a single voice group with a pre-built kernel stays on it: nothing to gain, and no compile at init)
     // (a voice that is a graph, not a chain, runs in the single-wave form: the pipeline's edges carry one signal)
@@ -965,7 +382,7 @@ struct Bank final : knh_bank {
     // many wavefronts as there are to keep requests in flight: the thresholds of the pre-built chains, bank.hip make_bank)
     // (a chain with a pre-built one-wavefront kernel but no pre-built wide form keeps the fused pipeline up to 512 groups)
     const unsigned jit_pipe_max = !entry && (sizeof(F) == 8 || signature.find_first_of("DYZ") != std::string::npos) ? 256u : 512u;
-    const bool pipe_jit = !interp && !pipe && !dag && wide_waves == 0 && pipeline_level >= 1 && n_groups <= jit_pipe_max && !(jp && jp[0] == '0') &&
+    const bool pipe_jit = !interp && !pipe && wide_waves == 0 && pipeline_level >= 1 && n_groups <= jit_pipe_max && !(jp && jp[0] == '0') &&
                           !(entry && n_groups == 1) && !signature_is_dag(signature);
     if (pipe_jit) {
       std::string why;
@@ -1290,10 +707,6 @@ struct Bank final : knh_bank {
     std::memset(h_done, 0, 64);
     KNH_HIP(hipMalloc(&d_fold_count, sizeof(uint32_t)));
     KNH_HIP(hipMemset(d_fold_count, 0, sizeof(uint32_t)));
-    {
-      const char* me = std::getenv("KNH_MAPPED_OUT");
-      mapped_out = !(me && me[0] == '0');
-    }
     if (desc.mix_mode == KNH_MIX_LEFT_FOLD) KNH_HIP(ensure_voices());
     bool any_wrapped = false;
     for (auto& S : stages) any_wrapped = any_wrapped || S.dcpb > 0;
@@ -1315,27 +728,13 @@ struct Bank final : knh_bank {
                                    static_cast<short>(on ? n_dev : -1), 0};
         if (on) { stage_dev[si] = 1; ++n_dev; }
       }
-      dev_events = n_dev > 0;
       dev_class.assign(stages.size() * 8u, 0);
       for (size_t si = 0; si < stages.size(); ++si)
         if (stage_dev[si])
           for (int pp = 0; pp < stages[si].n_params && pp < 8; ++pp) dev_class[si * 8u + pp] = static_cast<uint8_t>(1 + expected_value_kind(stages[si].kind, pp));
-      if (dev_events) {
-        KNH_HIP(hipMalloc(&d_stages, ds.size() * sizeof(knh_dev::DevStage)));
-        KNH_HIP(hipMemcpy(d_stages, ds.data(), ds.size() * sizeof(knh_dev::DevStage), hipMemcpyHostToDevice));
-        KNH_HIP(hipHostMalloc(&h_ev_overflow, 64, hipHostMallocMapped | hipHostMallocCoherent));
-        *h_ev_overflow = 0u;
-        KNH_HIP(hipMalloc(&d_armed, static_cast<size_t>(n_params_total) * nv * sizeof(uint16_t)));
-        KNH_HIP(hipMemset(d_armed, 0, static_cast<size_t>(n_params_total) * nv * sizeof(uint16_t)));
-        KNH_HIP(hipMalloc(&d_ev_cnt, static_cast<size_t>(nv) * 3 * sizeof(uint32_t)));
-        KNH_HIP(hipMemset(d_ev_cnt, 0, static_cast<size_t>(nv) * 3 * sizeof(uint32_t)));  // (kept zero by the resolver's last pass)
-        KNH_HIP(hipMalloc(&d_rec_start, (static_cast<size_t>(nv) + 1) * sizeof(uint32_t)));
-        KNH_HIP(hipStreamCreateWithFlags(&ev_stream, hipStreamNonBlocking));
-        for (int b = 0; b < 2; ++b) {
-          KNH_HIP(hipMalloc(&d_out_start2[b], (static_cast<size_t>(nv) + 1) * sizeof(uint32_t)));
-          KNH_HIP(hipEventCreateWithFlags(&recs_done[b], hipEventDisableTiming));
-          KNH_HIP(hipEventCreateWithFlags(&lists_free[b], hipEventDisableTiming));
-        }
+      if (n_dev > 0) {
+        const int rc = resolver.init(DevEventResolver::Setup{this, nv, static_cast<uint32_t>(n_params_total), static_cast<uint32_t>(bs), sr, sizeof(F) == 8, f2pi}, ds);
+        if (rc != KNH_OK) return rc;
       }
     }
     smooth.assign(stages.size(), {});
@@ -1345,9 +744,32 @@ struct Bank final : knh_bank {
         smooth[si].assign(static_cast<size_t>(nv) * stages[si].n_params, SmoothState{});
         smooth_mark[si].assign(nv, 0u);
       }
+    can_finish = chain_can_finish(stages);
+    {  // the per-block call on a resident launch (resident_call.hpp): what it needs to know of this bank, now that the kernel form is chosen
+      typename ResidentCall<F>::Setup rs{};
+      rs.bank = this;
+      rs.own_stream = own_stream;
+      rs.n_rows = (nv + 63u) / 64u;
+      rs.fold_planes = fold_planes;
+      rs.out_channels = desc.out_channels;
+      rs.block_size = static_cast<uint32_t>(bs);
+      rs.tile_frames = res_tile_frames();
+      rs.can_finish = can_finish;
+      rs.ev_start = h_ev_start2;
+      rs.events = h_events2;
+      rs.launch_voice = [this](const knh_dev::Resident& r) {
+        VoiceKernelArgs<F> a;
+        fill_launch_args(a, 1, 0, static_cast<uint32_t>(block_size));
+        a.flags = d_flags + 32;  // (a third set: the two the ordinary launches alternate stay as their fold kernels left them)
+        a.res = r;
+        return launch_voice(a, (nv + 63) / 64, own_stream);
+      };
+      resident.setup(rs);
+    }
     initialised = true;
     return KNH_OK;
   }
+  bool can_finish = false;   // the chain has a stage that can end a voice (ALL_DONE is reported only then)
   bool pan = false;          // the chain ends in a Pan2
   F* stage_out = nullptr;    // set by a bank that wraps this one (galactic_bank.hpp): the voices' signals of the block go here, [n_voices][block_size]
   unsigned fold_planes = 1;  // channel planes of the partial rows and of the per-voice output: 2 for a Pan2 chain
@@ -1542,15 +964,15 @@ struct Bank final : knh_bank {
     int rc = KNH_OK;
     size_t k = 0;
     while (k < count) {
-      if (dev_events) {
+      if (resolver.active()) {
         // Calls to nodes whose queues the DEVICE resolves: one table look-up and one 24-byte record in pinned memory per call,
         // whatever the order of stages and parameters in the batch (a host that addresses two parameters of alternate voices
         // -- BASELINE config C5 -- sends runs of one call).  dev_class[stage][param] = 1 + the ParameterValue kind it takes.
         const size_t ns = stages.size();
         if (stgs[k] < ns && params[k] < 8u && kinds[k] < 8u && dev_class[stgs[k] * 8u + params[k]] == kinds[k] + 1u) {
-          int r2 = dev_reserve(count - k);
+          int r2 = resolver.reserve(count - k);
           if (r2 != KNH_OK) return r2;
-          uint64_t* out = reinterpret_cast<uint64_t*>(h_recs + n_recs);  // three 8-byte words per record (QRec's layout)
+          uint64_t* out = reinterpret_cast<uint64_t*>(resolver.tail());  // three 8-byte words per record (QRec's layout)
           const uint64_t blk = static_cast<uint64_t>(block_offset & 0xFFFFu) << 16;
           size_t p = k, w = 0;
           for (; p < count; ++p) {
@@ -1567,8 +989,7 @@ struct Bank final : knh_bank {
             out[3 * w + 2] = val;
             ++w;
           }
-          n_recs += w;
-          recs_max_block = std::max(recs_max_block, block_offset);
+          resolver.commit(w, block_offset);
           k = p;
           continue;
         }
@@ -2050,7 +1471,7 @@ struct Bank final : knh_bank {
       list_busy[lb] = false;
     }
     if (total > h_events_cap2[lb]) {
-      { int rl = res_leave(); if (rl != KNH_OK) return rl; }  // (a resident kernel knows the list by its address)
+      { int rl = resident.leave(); if (rl != KNH_OK) return rl; }  // (a resident kernel knows the list by its address)
       size_t cap = std::max<size_t>(total, 1024) * 2;
       if (h_events2[lb]) KNH_HIP(hipHostFree(h_events2[lb]));
       h_events2[lb] = nullptr;
@@ -2133,10 +1554,7 @@ struct Bank final : knh_bank {
     if (n_blocks > 1 && voices_host) return fail(KNH_ERR_INVALID_ARGUMENT, "per-voice output is only available for single blocks");
     KNH_HIP(hipSetDevice(device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : own_stream;
-    if (h_ev_overflow && __atomic_load_n(h_ev_overflow, __ATOMIC_RELAXED) != 0u) {  // a resolver kernel of an earlier launch dropped a change
-      __atomic_store_n(h_ev_overflow, 0u, __ATOMIC_RELAXED);
-      warn("Not enough space for scheduled changes in WrPreciseTiming, change ignored");
-    }
+    if (resolver.take_overflow()) warn("Not enough space for scheduled changes in WrPreciseTiming, change ignored");
     const uint32_t fb = static_cast<uint32_t>(offset), fe = static_cast<uint32_t>(offset + ftp);
     // Assemble the launch's state patches block by block, in the order the reference would apply them.
     for (uint32_t b = 0; b < n_blocks; ++b) {
@@ -2160,14 +1578,10 @@ struct Bank final : knh_bank {
       }
     }
     // (whether this call goes to a resident launch -- below -- decides what its events may look like)
-    if (res_policy < 0) {
-      const char* e = std::getenv("KNH_RESIDENT");
-      res_policy = e && e[0] == '0' ? 0 : 1;
-    }
-    const bool res_ok = res_policy == 1 && sync && out_host && !out_device && !voices_host && !stream && n_blocks == 1 && fe > fb && mapped_out &&
-                        !accumulate && !timing && !(dev_events && n_recs > 0) && res_possible();
+    const bool res_now = sync && out_host && !out_device && !voices_host && !stream && n_blocks == 1 && fe > fb && !accumulate && !timing &&
+                         !resolver.pending() && res_possible() && resident.enabled() && resident.ready();
     bool have_events = false;
-    int rc = upload_events(s, &have_events, n_blocks, res_ok && res_cooldown == 0 && res_ranges_ok());
+    int rc = upload_events(s, &have_events, n_blocks, res_now && res_ranges_ok());
     if (rc != KNH_OK) return rc;
     if (!future.empty()) {  // calls addressed beyond this launch move up; those now due for the next
                             // block are applied right away, ahead of anything that arrives later
@@ -2186,14 +1600,12 @@ struct Bank final : knh_bank {
     // bank's kernel form has one (res_possible); anything else first asks a resident kernel (this bank's, or another bank's
     // on this device) to leave: it would be in the way of the launch, and it holds the voices' state in its registers.
     {
-      if (res_ok && res_cooldown == 0) {
-        rc = res_alloc();
-        if (rc != KNH_OK) return rc;
-        const int held_list = list_in_use;
-        rc = res_call(fb, fe, have_events, out_host, out_flags);
+      if (res_now) {
+        const int held_list = list_in_use, call_list = have_events ? list_in_use : -1;
+        if (call_list >= 0) { list_busy[call_list] = false; list_in_use = -1; }  // (no stream order to keep: the call is over when it returns)
+        rc = resident.call(fb, fe, call_list, res_n_ranges, out_host, out_flags);
         if (rc != KNH_ERR_UNSUPPORTED_CHAIN) return rc;
         list_in_use = held_list;  // the kernels would not run side by side: this call, and the bank from now on, takes the launch per call
-        if (held_list >= 0) list_busy[held_list] = false;
         if (res_n_ranges) {  // the launch per call reads per-voice lists: the call's range events once more, spelled out
           pending_ranges.swap(sent_ranges);
           for (RangeEvent& r : pending_ranges) r.at = 0;
@@ -2201,10 +1613,10 @@ struct Bank final : knh_bank {
           if (rc != KNH_OK) return rc;
         }
       }
-      if (res_cooldown) --res_cooldown;
-      rc = res_leave();
+      resident.sat_out();
+      rc = resident.leave();
       if (rc != KNH_OK) return rc;
-      res_make_room();
+      ResidentCall<F>::make_room(device, this);
     }
     const bool want_voices = voices_host != nullptr || (desc.mix_mode == KNH_MIX_LEFT_FOLD) || stage_out != nullptr;
     if (desc.mix_mode == KNH_MIX_LEFT_FOLD && n_blocks > 1)
@@ -2241,8 +1653,6 @@ struct Bank final : knh_bank {
     flags_last = flags_now;
     VoiceKernelArgs<F> a;
     fill_launch_args(a, n_blocks, fb, fe);
-    a.input = nullptr;
-    a.in_channels = desc.in_channels;
     if (uses_input) {
       if (in_blocks_set != n_blocks) return fail(KNH_ERR_INVALID_ARGUMENT, "a bank with KNH_STAGE_INPUT stages needs knh_bank_set_input for exactly the blocks of this call");
       if (in_device) {
@@ -2261,15 +1671,14 @@ struct Bank final : knh_bank {
     }
     a.ev_start = have_events ? h_ev_start : nullptr;  // pinned host memory, device-visible
     a.events = h_events;
-    if (dev_events && n_recs > 0) {  // calls to nodes whose queues the device resolves: the lists are made there, the host's merged in
-      int r2 = resolve_on_device(s, n_blocks, fb, fe, have_events, have_events ? h_ev_start[nv] : 0u);
+    if (resolver.pending()) {  // calls to nodes whose queues the device resolves: the lists are made there, the host's merged in
+      DevEventResolver::Lists lists{};
+      int r2 = resolver.resolve(s, n_blocks, fb, fe, have_events ? h_ev_start : nullptr, h_events, have_events ? h_ev_start[nv] : 0u, &lists);
       if (r2 != KNH_OK) return r2;
-      a.ev_start = d_out_start2[out_in_use];
-      a.events = d_out_events2[out_in_use];
+      a.ev_start = lists.ev_start;
+      a.events = lists.events;
     }
-    a.partials = d_partials;
     a.voices_out = want_voices ? (stage_out ? stage_out : d_voices) : nullptr;
-    a.done_frames = d_done;
     a.flags = flags_now;
     std::pair<hipEvent_t, hipEvent_t>* tp = nullptr;
     if (timing) {
@@ -2292,11 +1701,7 @@ struct Bank final : knh_bank {
     if (tp) KNH_HIP(hipEventRecord(tp->second, s));
     if (stage_out && interp)  // (the interpreter's rows are the voices' signals)
       KNH_HIP(hipMemcpyAsync(stage_out, d_partials, static_cast<size_t>(nv) * block_size * sizeof(F), hipMemcpyDeviceToDevice, s));
-    if (out_in_use >= 0) {  // the resolver may rewrite this set of lists once this kernel has read it
-      KNH_HIP(hipEventRecord(lists_free[out_in_use], s));
-      lists_busy[out_in_use] = true;
-      out_in_use = -1;
-    }
+    { int r2 = resolver.kernel_enqueued(s); if (r2 != KNH_OK) return r2; }
     if (have_events && list_in_use >= 0) {
       KNH_HIP(hipEventRecord(list_done[list_in_use], s));
       list_busy[list_in_use] = true;
@@ -2304,7 +1709,7 @@ struct Bank final : knh_bank {
     }
 
     // A blocking call for host memory: the fold kernel writes into the pinned block itself and tells the host when it is through
-    const bool hand_over = sync && out_host && !out_device && !voices_host && mapped_out && fe > fb;
+    const bool hand_over = sync && out_host && !out_device && !voices_host && fe > fb;
     F* dst = out_device ? static_cast<F*>(out_device) : (hand_over ? h_out : d_out);
     knh_dev::HostDone hd{nullptr, nullptr, nullptr, 0u};
     if (hand_over) {
@@ -2362,15 +1767,7 @@ struct Bank final : knh_bank {
           std::memcpy(static_cast<F*>(out_host) + c * block_size + offset, h_out + c * block_size + offset, ftp * sizeof(F));
       }
     }
-    if (out_flags) {
-      uint32_t fl = 0;
-      if (h_flags[0]) fl |= KNH_FLAG_ANY_DONE;
-      bool has_env = false;
-      for (const StageInfo& st : stages) has_env = has_env || st.kind == KNH_STAGE_MUL_ENV_ASR || st.kind == KNH_STAGE_MUL_ENV_AR || st.kind == KNH_STAGE_MUL_ENVELOPE ||
-                          st.kind == KNH_STAGE_BUFFER_READER;
-      if (has_env && h_flags[1] == 0) fl |= KNH_FLAG_ALL_DONE;  // a chain without an envelope never finishes
-      *out_flags = fl;
-    }
+    if (out_flags) *out_flags = done_flags(h_flags[0], h_flags[1], can_finish);
     return KNH_OK;
   }
   uint32_t partials_blocks = 1, out_blocks = 1;
@@ -2391,7 +1788,6 @@ struct Bank final : knh_bank {
     if (wide_waves == 4) return wide->f32_w4[desc.allow_fma ? 1 : 0](a, n_waves, s);
     if (wide_waves == 8) return wide->f32_w8[desc.allow_fma ? 1 : 0](a, n_waves, s);
     if (wide_waves == 16) return wide->f32_w16[desc.allow_fma ? 1 : 0](a, n_waves, s);
-    if (dag) return dag->f32[desc.allow_fma ? 1 : 0](a, n_waves, s);
     if (pipe) return pipe->f32[desc.allow_fma ? 1 : 0](a, n_waves, s);
     return entry->f32[desc.allow_fma ? 1 : 0](a, n_waves, s);
   }
@@ -2413,7 +1809,7 @@ struct Bank final : knh_bank {
   int read_done_frames(uint32_t* out) override {
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (!out) return fail(KNH_ERR_INVALID_ARGUMENT, "null output");
-    { int rl = res_leave(); if (rl != KNH_OK) return rl; }  // (a resident kernel's stores reach the copy engine when it ends)
+    { int rl = resident.leave(); if (rl != KNH_OK) return rl; }  // (a resident kernel's stores reach the copy engine when it ends)
     KNH_HIP(hipSetDevice(device));
     KNH_HIP(hipStreamSynchronize(own_stream));
     KNH_HIP(hipMemcpy(out, d_done, static_cast<size_t>(nv) * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -2421,7 +1817,7 @@ struct Bank final : knh_bank {
   }
   int debug_read(uint32_t* out16) override {
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
-    { int rl = res_leave(); if (rl != KNH_OK) return rl; }
+    { int rl = resident.leave(); if (rl != KNH_OK) return rl; }
     KNH_HIP(hipSetDevice(device));
     KNH_HIP(hipDeviceSynchronize());
     KNH_HIP(hipMemcpy(out16, flags_last ? flags_last : d_flags, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -2429,7 +1825,7 @@ struct Bank final : knh_bank {
   }
   int synchronize() override {
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
-    { int rl = res_leave(); if (rl != KNH_OK) return rl; }
+    { int rl = resident.leave(); if (rl != KNH_OK) return rl; }
     KNH_HIP(hipSetDevice(device));
     KNH_HIP(hipDeviceSynchronize());
     return KNH_OK;
@@ -2447,7 +1843,7 @@ struct Bank final : knh_bank {
   }
   int timing_reset(int enable) override {
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
-    { int rl = res_leave(); if (rl != KNH_OK) return rl; }  // (kernel time is measured launch by launch: a timed bank launches per call)
+    { int rl = resident.leave(); if (rl != KNH_OK) return rl; }  // (kernel time is measured launch by launch: a timed bank launches per call)
     KNH_HIP(hipSetDevice(device));
     int rc = timing_collect();
     if (rc != KNH_OK) return rc;

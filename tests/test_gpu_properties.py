@@ -133,7 +133,7 @@ def test_full_size_c5_fm_with_sample_accurate_changes(knh, oracle):
 @pytest.mark.parametrize("name,n_voices,block_size", [("C3", 1000, 512), ("C4", 300, 100), ("C5", 260, 128), ("C2", 200, 48),
                                                       ("D3", 500, 512), ("B3", 300, 256)])
 def test_pipelined_kernel_equals_single_wave_kernel(knh, monkeypatch, name, n_voices, block_size):
-    """KNH_PIPELINE 0 = one wavefront per 64 voices, 1 = linear wave pipeline, 2 = five-role pipeline where built;
+    """KNH_PIPELINE 0 = one wavefront per 64 voices, 1 (and 2) = linear wave pipeline;
     "1big" = the linear pipeline with 64-sample tiles and the fold in its last stage group (KNH_PIPE_BIG=1, where built);
     "1inplace" = 64-sample tiles, the last stage group works in place and a mixer wavefront folds (the default where built)."""
     w = configs.config(name, n_voices=n_voices, block_size=block_size)
