@@ -211,11 +211,35 @@ impl<F: Float, I: Size> GpuVoiceBank<F, I> {
         })
     }
 
-    /// `Buffer::from_vec(samples, sample_rate)` for the chain's `BufferReader` stage: one single-channel buffer shared
-    /// by every voice of the bank.  Before the bank is pushed (init runs at push time, graph.rs:462-475).
+    /// `Buffer::from_vec(samples, sample_rate)` for the chain's `BufferReader` stage: entry 0 of the stage's pool of
+    /// single-channel buffers, the one every voice reads unless `assign_buffers` says otherwise.  Before the bank is pushed
+    /// (init runs at push time, graph.rs:462-475).
     pub fn set_buffer(&mut self, stage: usize, samples: &[F], buffer_sample_rate: f64) -> Result<(), BankError> {
         let rc = unsafe { knh_bank_set_buffer(self.h, stage as u32, samples.as_ptr() as *const c_void, samples.len(), buffer_sample_rate) };
         if rc != KNH_OK { Err(last_error(self.h)) } else { Ok(()) }
+    }
+
+    /// One more buffer in the pool of the `BufferReader` stage; returns its pool index (0, 1, 2, ... in call order).
+    /// Before the bank is pushed.
+    pub fn add_buffer(&mut self, stage: usize, samples: &[F], buffer_sample_rate: f64) -> Result<u32, BankError> {
+        let mut index = 0u32;
+        let rc = unsafe { knh_bank_add_buffer(self.h, stage as u32, samples.as_ptr() as *const c_void, samples.len(), buffer_sample_rate, &mut index) };
+        if rc != KNH_OK { Err(last_error(self.h)) } else { Ok(index) }
+    }
+    /// Voice `voices[i]` reads pool entry `buffer_ids[i]`.  `ctor`: `[rate, looping, start_s]` per voice.  Before the bank
+    /// is pushed it may be `None` (the constructor arguments stay); afterwards it is required, and the voice's reader is
+    /// from the next block on what `BufferReader::new(pool[id], rate, looping).start_at(start_s)` is after init.
+    pub fn assign_buffers(&mut self, stage: usize, voices: &[u32], buffer_ids: &[u32], ctor: Option<&[[f64; 3]]>) -> Result<(), BankError> {
+        if voices.len() != buffer_ids.len() || ctor.map_or(false, |c| c.len() != voices.len()) {
+            return Err(BankError("assign_buffers: voices, buffer_ids and ctor must have one length".into()));
+        }
+        let c = ctor.map_or(core::ptr::null(), |c| c.as_ptr() as *const f64);
+        let rc = unsafe { knh_bank_assign_buffers(self.h, stage as u32, voices.len(), voices.as_ptr(), buffer_ids.as_ptr(), c) };
+        if rc != KNH_OK { Err(last_error(self.h)) } else { Ok(()) }
+    }
+    /// Entries in the pool of the `BufferReader` stage.
+    pub fn buffer_count(&self, stage: usize) -> u32 {
+        unsafe { knh_bank_buffer_count(self.h, stage as u32) }
     }
 
     /// Flat parameter index of (`voice`, `stage`, parameter name), e.g. `"cutoff_freq"`, `"t_restart"`, `"wr_mul"`.

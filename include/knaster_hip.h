@@ -117,8 +117,11 @@ typedef enum knh_value_kind {
  *     the Schroeder allpass around an AllpassDelay.  params: 0 delay_time (seconds; longer than the ring: ignored -- the
  *     reference does not check and would index out of bounds), 1 feedback
  * KNH_STAGE_BUFFER_READER   g.push(BufferReader::<F, U1>::new(buffer, rate, looping).start_at(start))  buffer.rs:19-191  1  rate, looping (0/1), start (s)
- *     a source: plays the single-channel Buffer given to knh_bank_set_buffer (shared by every voice) with linear
- *     interpolation; one-shot voices mark done at the frame after their last one and are silent afterwards.
+ *     a source: plays a single-channel Buffer with linear interpolation; one-shot voices mark done at the frame after
+ *     their last one and are silent afterwards.  The stage has a pool of Buffers (knh_bank_set_buffer: entry 0,
+ *     knh_bank_add_buffer: one more), each with its own length and sample rate; every voice reads the entry
+ *     knh_bank_assign_buffers gave it (entry 0 otherwise), and can be given another one -- a new reader on it -- while
+ *     the bank runs.  Seconds-valued parameters convert with the rate of the voice's own Buffer.
  *     params: 0 rate, 1 looping(bool), 2 start_s, 3 duration_s, 4 end_s, 5 t_restart(trigger).  Not combinable with
  *     delayed_changes_per_block (the reference's block loop ignores partial blocks).  At most one per chain.
  * KNH_STAGE_PHASOR          g.push(Phasor::new(freq))           osc.rs:172-214       1    freq
@@ -369,6 +372,30 @@ int32_t knh_bank_set_ctor_args(knh_bank* bank, uint32_t stage, uint32_t first_vo
 /* Buffer::from_vec(samples, sample_rate) (dsp/buffer.rs:58-66) for the chain's BufferReader stage: `n_frames` samples of
  * the bank's sample type, copied into device memory at init.  Before knh_bank_init. */
 int32_t knh_bank_set_buffer(knh_bank* bank, uint32_t stage, const void* samples, size_t n_frames, double buffer_sample_rate);
+/* The pool of Buffers of BufferReader stage `stage`: knh_bank_set_buffer makes (or replaces) entry 0, knh_bank_add_buffer
+ * adds one more single-channel Buffer; *out_index (may be NULL) = its pool index (0, 1, 2, ... in call order).  Before
+ * knh_bank_init only.  The pool is one device allocation (every Buffer's start rounded up to 64 samples) and holds at most
+ * 2^32 - 1 samples; host-sharded, multi-device and rank banks give every range / rank the whole pool.
+ * A refused call (not a BufferReader stage, a null or empty Buffer, a bad rate, after init, a pool too large) changes nothing. */
+int32_t knh_bank_add_buffer(knh_bank* bank, uint32_t stage, const void* samples, size_t n_frames, double buffer_sample_rate,
+                            uint32_t* out_index);
+/* Voice voices[i] reads pool entry buffer_ids[i] (every voice: entry 0 until told otherwise).
+ * ctor: NULL, or [count][3] = rate, looping, start_s (the stage's constructor arguments).
+ * Before knh_bank_init: the Buffer the voice is constructed on (a non-NULL ctor also replaces its constructor arguments).
+ * After knh_bank_init: takes effect at the first frame of the next process call, and ctor must be non-NULL.  From then on
+ * the voice's reader is what the reference has once the old node is freed and
+ * BufferReader::new(pool[id], rate, looping).start_at(start_s) is pushed and initialised (buffer.rs:43-72, 110-118): rate
+ * scale, start, duration (the whole new Buffer) and end from the new Buffer's sample rate, read pointer at the start, not
+ * finished; earlier duration_s / end_s / start_s calls are forgotten, later ones convert with the new rate; the voice's
+ * entry of knh_bank_read_done_frames is not-done until the new reader finishes.
+ * Refused, changing nothing: a stage that is not a BufferReader, a voice or buffer index out of range
+ * (KNH_ERR_OUT_OF_RANGE), ctor == NULL after init, and -- after init -- a chain in which another stage can also mark a
+ * voice done (EnvAsr, EnvAr, Envelope: KNH_ERR_UNSUPPORTED_CHAIN, the single done frame per voice could not be attributed)
+ * or whose reader is wrapped in WrSmoothParams (KNH_ERR_UNSUPPORTED_CHAIN). */
+int32_t knh_bank_assign_buffers(knh_bank* bank, uint32_t stage, size_t count, const uint32_t* voices,
+                                const uint32_t* buffer_ids, const double* ctor);
+/* Entries in the pool of BufferReader stage `stage` (0 for any other stage). */
+uint32_t knh_bank_buffer_count(const knh_bank* bank, uint32_t stage);
 int32_t knh_bank_init(knh_bank* bank, uint32_t sample_rate, size_t block_size);
 void knh_bank_destroy(knh_bank* bank);
 

@@ -70,6 +70,9 @@ PROTOTYPES = {
     "knh_bank_create_sharded": (C.c_int32, [C.POINTER(BankDesc), C.c_uint32, C.POINTER(C.c_void_p)]),
     "knh_bank_set_ctor_args": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "knh_bank_set_buffer": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_double]),
+    "knh_bank_add_buffer": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_double, C.POINTER(C.c_uint32)]),
+    "knh_bank_assign_buffers": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "knh_bank_buffer_count": (C.c_uint32, [C.c_void_p, C.c_uint32]),
     "knh_bank_init": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_size_t]),
     "knh_bank_destroy": (None, [C.c_void_p]),
     "knh_bank_inputs": (C.c_uint16, [C.c_void_p]),

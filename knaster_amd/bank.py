@@ -137,6 +137,31 @@ class VoiceBank:
         a = np.ascontiguousarray(np.asarray(samples, dtype=self.dtype))
         self._check(self._lib.knh_bank_set_buffer(self._h, stage, a.ctypes.data_as(C.c_void_p), a.shape[0], float(buffer_sample_rate)))
 
+    def add_buffer(self, stage: int, samples, buffer_sample_rate: float) -> int:
+        """One more Buffer in the pool of the BufferReader stage -> its pool index (knh_bank_add_buffer); before init."""
+        a = np.ascontiguousarray(np.asarray(samples, dtype=self.dtype))
+        index = C.c_uint32(0)
+        self._check(self._lib.knh_bank_add_buffer(self._h, stage, a.ctypes.data_as(C.c_void_p), a.shape[0],
+                                                  float(buffer_sample_rate), C.byref(index)))
+        return int(index.value)
+
+    def assign_buffers(self, stage: int, voices, buffer_ids, ctor=None):
+        """Voice voices[i] reads pool entry buffer_ids[i]; ctor: None or [count, 3] = rate, looping, start_s
+        (knh_bank_assign_buffers).  After init ctor is required: the voice gets a new reader at the next process call."""
+        v = np.ascontiguousarray(voices, dtype=np.uint32)
+        ids = np.ascontiguousarray(np.broadcast_to(np.asarray(buffer_ids, dtype=np.uint32), v.shape))
+        c = None
+        if ctor is not None:
+            c = np.ascontiguousarray(np.asarray(ctor, dtype=np.float64))
+            if c.shape != (v.shape[0], 3):
+                raise ValueError(f"ctor must be [{v.shape[0]}, 3] (rate, looping, start_s), got {c.shape}")
+        self._check(self._lib.knh_bank_assign_buffers(self._h, stage, v.shape[0], v.ctypes.data_as(C.c_void_p),
+                                                      ids.ctypes.data_as(C.c_void_p),
+                                                      None if c is None else c.ctypes.data_as(C.c_void_p)))
+
+    def buffer_count(self, stage: int) -> int:
+        return int(self._lib.knh_bank_buffer_count(self._h, stage))
+
     def init(self, sample_rate: int, block_size: int):
         self._check(self._lib.knh_bank_init(self._h, sample_rate, block_size))
         self.sample_rate, self.block_size = sample_rate, block_size

@@ -443,6 +443,25 @@ int32_t knh_bank_set_buffer(knh_bank* bank, uint32_t stage, const void* samples,
     return bank->set_buffer(stage, samples, n_frames, buffer_sample_rate);
   });
 }
+int32_t knh_bank_add_buffer(knh_bank* bank, uint32_t stage, const void* samples, size_t n_frames, double buffer_sample_rate, uint32_t* out_index) {
+  return guarded(bank, [&]() -> int32_t {
+    if (!bank) return KNH_ERR_INVALID_ARGUMENT;
+    return bank->add_buffer(stage, samples, n_frames, buffer_sample_rate, out_index);
+  });
+}
+int32_t knh_bank_assign_buffers(knh_bank* bank, uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* buffer_ids, const double* ctor) {
+  return guarded(bank, [&]() -> int32_t {
+    if (!bank) return KNH_ERR_INVALID_ARGUMENT;
+    return bank->assign_buffers(stage, count, voices, buffer_ids, ctor);
+  });
+}
+uint32_t knh_bank_buffer_count(const knh_bank* bank, uint32_t stage) {
+  try {
+    return bank ? bank->buffer_count(stage) : 0u;
+  } catch (...) {
+    return 0u;
+  }
+}
 int32_t knh_bank_init(knh_bank* bank, uint32_t sample_rate, size_t block_size) {
   return guarded(bank, [&]() -> int32_t {
     if (!bank) return KNH_ERR_INVALID_ARGUMENT;

@@ -97,6 +97,15 @@ struct GalacticBank final : knh_bank {
     if (mine(stage)) return fail(KNH_ERR_INVALID_ARGUMENT, "stage is not a BufferReader");
     return adopt(inner->set_buffer(stage, samples, n_frames, sr));
   }
+  int add_buffer(uint32_t stage, const void* samples, size_t n_frames, double sr, uint32_t* out_index) override {
+    if (mine(stage)) return fail(KNH_ERR_INVALID_ARGUMENT, "stage is not a BufferReader");
+    return adopt(inner->add_buffer(stage, samples, n_frames, sr, out_index));
+  }
+  int assign_buffers(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* ids, const double* ctor) override {
+    if (mine(stage)) return fail(KNH_ERR_INVALID_ARGUMENT, "stage is not a BufferReader");
+    return adopt(inner->assign_buffers(stage, count, voices, ids, ctor));
+  }
+  uint32_t buffer_count(uint32_t stage) const override { return mine(stage) ? 0u : inner->buffer_count(stage); }
   int set_input(uint32_t n_blocks, const void* host, const void* dev) override {
     if (n_blocks > 1) return fail(KNH_ERR_INVALID_ARGUMENT, "a chain that ends in Galactic takes its bank inputs one block per call");
     return adopt(inner->set_input(n_blocks, host, dev));

@@ -92,6 +92,52 @@ struct ShardedBank final : knh_bank {
     }
     return KNH_OK;
   }
+  int add_buffer(uint32_t stage, const void* samples, size_t n_frames, double sr, uint32_t* out_index) override {  // every range holds the whole pool
+    // The ranges are alike, so what the first one refuses they all would; should a later one fail all the same (its copy of
+    // the samples does not fit in memory), the ranges before it drop the entry again: a refused call changes nothing.
+    uint32_t index = 0;
+    int done = 0;
+    auto undo = [&] { for (int j = 0; j < done; ++j) shard[j]->drop_last_buffer(stage); };
+    try {
+      for (; done < n(); ++done) {
+        int rc = shard[done]->add_buffer(stage, samples, n_frames, sr, &index);
+        if (rc != KNH_OK) { adopt(done, rc); undo(); return rc; }
+      }
+    } catch (...) {
+      undo();
+      throw;
+    }
+    if (out_index) *out_index = index;
+    return KNH_OK;
+  }
+  uint32_t buffer_count(uint32_t stage) const override { return shard[0]->buffer_count(stage); }
+  std::vector<uint32_t> asg_voices, asg_ids;
+  std::vector<double> asg_ctor;
+  int assign_buffers(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* ids, const double* ctor) override {
+    if (count && (!voices || !ids)) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
+    // checked as a whole first (a refused call changes nothing in any range): the stage, the chain and `ctor` by a range, on
+    // an empty call; the voices and the entries here
+    { int rc = shard[0]->assign_buffers(stage, 0, nullptr, nullptr, ctor); if (rc != KNH_OK) return adopt(0, rc); }
+    const uint32_t n_buffers = shard[0]->buffer_count(stage);
+    for (size_t i = 0; i < count; ++i) {
+      if (voices[i] >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
+      if (ids[i] >= n_buffers) return fail(KNH_ERR_OUT_OF_RANGE, "buffer index out of range");
+    }
+    if (initialised) flush_deferred();  // (earlier batched parameter calls come first, as they were made first)
+    for (int k = 0; k < n(); ++k) {
+      asg_voices.clear(); asg_ids.clear(); asg_ctor.clear();
+      for (size_t i = 0; i < count; ++i) {
+        if (voices[i] < base[k] || voices[i] >= base[k + 1]) continue;
+        asg_voices.push_back(voices[i] - base[k]);
+        asg_ids.push_back(ids[i]);
+        if (ctor) asg_ctor.insert(asg_ctor.end(), ctor + 3 * i, ctor + 3 * i + 3);
+      }
+      if (asg_voices.empty()) continue;
+      int rc = shard[k]->assign_buffers(stage, asg_voices.size(), asg_voices.data(), asg_ids.data(), ctor ? asg_ctor.data() : nullptr);
+      if (rc != KNH_OK) return adopt(k, rc);
+    }
+    return KNH_OK;
+  }
   int set_input(uint32_t n_blocks, const void* host, const void* dev) override {  // every range reads the same input block(s)
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (dev && multi_device()) return fail(KNH_ERR_INVALID_ARGUMENT, "a bank on several GPUs takes its input from host memory");

@@ -73,7 +73,54 @@ struct RankBank final : knh_bank {
     return adopt(local->set_ctor(stage, a - lo, b - a, args ? args + static_cast<size_t>(a - first) * n_args : nullptr, n_args));
   }
   int set_buffer(uint32_t stage, const void* samples, size_t n_frames, double sr) override {
-    return local ? adopt(local->set_buffer(stage, samples, n_frames, sr)) : KNH_OK;
+    if (local) return adopt(local->set_buffer(stage, samples, n_frames, sr));
+    int rc = check_buffer("knh_bank_set_buffer", stage, samples, n_frames, sr);
+    if (rc != KNH_OK) return rc;
+    if (pool_count == 0) pool_count = 1;  // (entry 0 exists from here on)
+    return KNH_OK;
+  }
+  // A rank without voices holds no pool, but refuses what the ranks with voices refuse and counts the entries, so that every
+  // rank hands out the same indices.
+  int check_buffer(const char* who, uint32_t stage, const void* samples, size_t n_frames, double sr) {
+    if (initialised) return fail(KNH_ERR_INVALID_ARGUMENT, std::string(who) + " comes before knh_bank_init");
+    if (stage >= stages.size() || stages[stage].kind != KNH_STAGE_BUFFER_READER) return fail(KNH_ERR_INVALID_ARGUMENT, "not a BufferReader stage");
+    if (!samples || n_frames == 0 || n_frames >= (1ull << 31) || !(sr > 0.0) || !std::isfinite(sr)) return fail(KNH_ERR_INVALID_ARGUMENT, "empty buffer or bad sample rate");
+    return KNH_OK;
+  }
+  // (every rank is handed the whole pool)
+  uint32_t pool_count = 0;
+  int add_buffer(uint32_t stage, const void* samples, size_t n_frames, double sr, uint32_t* out_index) override {
+    if (local) return adopt(local->add_buffer(stage, samples, n_frames, sr, out_index));
+    int rc = check_buffer("knh_bank_add_buffer", stage, samples, n_frames, sr);
+    if (rc != KNH_OK) return rc;
+    if (out_index) *out_index = pool_count;
+    pool_count += 1;
+    return KNH_OK;
+  }
+  uint32_t buffer_count(uint32_t stage) const override {
+    if (local) return local->buffer_count(stage);
+    return stage < stages.size() && stages[stage].kind == KNH_STAGE_BUFFER_READER ? pool_count : 0u;
+  }
+  std::vector<uint32_t> asg_voices, asg_ids;
+  std::vector<double> asg_ctor;
+  int assign_buffers(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* ids, const double* ctor) override {
+    if (stage >= stages.size() || stages[stage].kind != KNH_STAGE_BUFFER_READER) return fail(KNH_ERR_INVALID_ARGUMENT, "not a BufferReader stage");
+    if (count && (!voices || !ids)) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
+    const uint32_t n_buffers = buffer_count(stage);
+    for (size_t i = 0; i < count; ++i) {  // voice numbers are the whole bank's: checked here, on every rank alike
+      if (voices[i] >= total) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
+      if (ids[i] >= n_buffers) return fail(KNH_ERR_OUT_OF_RANGE, "buffer index out of range");
+    }
+    if (!local) return initialised && !ctor ? fail(KNH_ERR_INVALID_ARGUMENT, "after knh_bank_init knh_bank_assign_buffers needs the new reader's constructor arguments") : KNH_OK;
+    asg_voices.clear(); asg_ids.clear(); asg_ctor.clear();
+    for (size_t i = 0; i < count; ++i) {
+      if (!mine(voices[i])) continue;
+      asg_voices.push_back(voices[i] - lo);
+      asg_ids.push_back(ids[i]);
+      if (ctor) asg_ctor.insert(asg_ctor.end(), ctor + 3 * i, ctor + 3 * i + 3);
+    }
+    // (an empty share still goes to the local bank: its refusals -- no constructor arguments, an envelope in the chain -- are every rank's)
+    return adopt(local->assign_buffers(stage, asg_voices.size(), asg_voices.data(), asg_ids.data(), ctor ? (asg_ctor.empty() ? ctor : asg_ctor.data()) : nullptr));
   }
   int set_input(uint32_t n_blocks, const void* host, const void* dev) override {  // every rank is handed the same input block(s)
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");

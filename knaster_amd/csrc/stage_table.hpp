@@ -41,7 +41,7 @@ const KindInfo kKinds[KNH_STAGE_KIND_COUNT] = {
     /* POLYBLEP    */ {5, 3, 2, 1, 'B', {"freq", "pulse_width", "waveform"}},
     /* ALLPASS_DLY */ {7, 1, 1, 1, 'Y', {"delay_time"}},
     /* ALLPASS_FB  */ {8, 2, 1, 1, 'Z', {"delay_time", "feedback"}},
-    /* BUFFER_READ */ {10, 6, 3, 1, 'F', {"rate", "looping", "start_s", "duration_s", "end_s", "t_restart"}},
+    /* BUFFER_READ */ {12, 6, 3, 1, 'F', {"rate", "looping", "start_s", "duration_s", "end_s", "t_restart"}},
     /* WHITE_NOISE */ {2, 0, 1, 1, 'U', {nullptr}},
     /* PINK_NOISE  */ {14, 0, 1, 1, 'K', {nullptr}},
     /* BROWN_NOISE */ {3, 0, 1, 1, 'O', {nullptr}},

@@ -139,11 +139,50 @@ struct Bank final : knh_bank {
   float* d_sine = nullptr;
   double* d_seg_table = nullptr;  // segment Envelope: [voice][seg_max][3]
   uint32_t seg_max = 0;
-  F* d_buffer = nullptr;          // BufferReader's shared Buffer (device copy), staged in h_buffer until init
-  std::vector<F> h_buffer;
-  double buffer_sr = 0.0;
+  // BufferReader's pool of Buffers: one device allocation, entry k's samples from pool[k].off on (every start rounded up to
+  // 64 samples); the host copies are staged in the entries until init.  A voice plays the entry buf_id[voice] says.
+  F* d_buffer = nullptr;
+  struct PoolEntry { std::vector<F> samples; double sr = 0.0; uint32_t n_frames = 0, off = 0; };
+  std::vector<PoolEntry> pool;
+  std::vector<uint32_t> buf_id;                      // [voice], empty: every voice on entry 0
   std::vector<double> buf_start, buf_dur, buf_rate;  // BufferReader shadows per voice: start_frame, dur_frame, rate
-  double buf_base_rate = 0.0;
+  const PoolEntry& buf_of(uint32_t v) const { return pool[buf_id.empty() ? 0u : buf_id[v]]; }
+  // Seconds::from_secs_f64(secs).to_samples_f64(buffer_sr), time.rs:59-64,92-96
+  static double secs_to_frames(double secs, double buffer_sr) {
+    const double whole = std::floor(secs);
+    const uint32_t tes = sat_u32((secs - std::trunc(secs)) * 282240000.0);
+    return static_cast<double>(sat_u32(whole)) * buffer_sr + (static_cast<double>(tes) * buffer_sr) / 282240000.0;
+  }
+  // BufferReader::new(pool[buf_id[v]], rate, looping).start_at(start_s) and its init (buffer.rs:40-57, :106-115) for voice v,
+  // a = the three constructor arguments: the voice's shadows, and every slot of the stage handed to put(rel, word)
+  template <typename Put>
+  void reader_construct(uint32_t v, const double* a, Put&& put) {
+    const PoolEntry& e = buf_of(v);
+    const double base_rate = e.sr / static_cast<double>(sample_rate);  // Buffer::buf_rate_scale
+    const double length_seconds = static_cast<double>(e.n_frames) / e.sr;
+    const double start = secs_to_frames(a[2], e.sr), dur = secs_to_frames(length_seconds, e.sr);
+    buf_start[v] = start; buf_dur[v] = dur; buf_rate[v] = a[0];
+    auto put2 = [&](int rel, double d) {
+      const uint64_t b = to_bits(d);
+      put(rel, static_cast<uint32_t>(b));
+      put(rel + 1, static_cast<uint32_t>(b >> 32));
+    };
+    put2(0, start);             // jump_to(start_frame)
+    put2(2, base_rate * a[0]);  // base_rate * rate, the per-sample step
+    put2(4, start);
+    put2(6, start + dur);
+    put(8, 0u);                 // finished = false
+    put(9, a[1] != 0.0 ? 1u : 0u);
+    put(10, e.off);
+    put(11, e.n_frames);
+  }
+  // the pool's size in samples with `n_frames` in place of entry `at` (at == pool.size(): one more entry), every entry padded to 64
+  uint64_t pool_samples_with(size_t at, size_t n_frames) const {
+    uint64_t total = 0;
+    for (size_t k = 0; k < pool.size(); ++k) total += ((k == at ? n_frames : pool[k].n_frames) + 63ull) & ~63ull;
+    if (at == pool.size()) total += (n_frames + 63ull) & ~63ull;
+    return total;
+  }
   void* d_delay = nullptr;        // SampleDelay rings: [voice][delay_stride] of F
   uint32_t delay_stride = 0;
   std::vector<uint32_t> delay_len;  // ring length per voice (samples)
@@ -220,7 +259,6 @@ struct Bank final : knh_bank {
     a.delay_ring = d_delay;
     a.delay_stride = delay_stride;
     a.buffer = d_buffer;
-    a.buffer_frames = static_cast<uint32_t>(h_buffer.size());
     a.input = nullptr;
     a.in_channels = desc.in_channels;
     a.ev_start = nullptr;
@@ -279,12 +317,72 @@ struct Bank final : knh_bank {
     return KNH_OK;
   }
 
-  int set_buffer(uint32_t stage, const void* samples, size_t n_frames, double sr) override {
-    if (initialised) return fail(KNH_ERR_INVALID_ARGUMENT, "knh_bank_set_buffer comes before knh_bank_init");
+  // knh_bank_set_buffer (entry 0 of the pool, made or replaced) and knh_bank_add_buffer (one more entry)
+  int put_buffer(size_t at, const char* who, uint32_t stage, const void* samples, size_t n_frames, double sr) {
+    if (initialised) return fail(KNH_ERR_INVALID_ARGUMENT, std::string(who) + " comes before knh_bank_init");
     if (stage >= stages.size() || stages[stage].kind != KNH_STAGE_BUFFER_READER) return fail(KNH_ERR_INVALID_ARGUMENT, "not a BufferReader stage");
-    if (!samples || n_frames == 0 || n_frames >= (1ull << 31) || !(sr > 0.0)) return fail(KNH_ERR_INVALID_ARGUMENT, "empty buffer or bad sample rate");
-    h_buffer.assign(static_cast<const F*>(samples), static_cast<const F*>(samples) + n_frames);
-    buffer_sr = sr;
+    if (!samples || n_frames == 0 || n_frames >= (1ull << 31) || !(sr > 0.0) || !std::isfinite(sr)) return fail(KNH_ERR_INVALID_ARGUMENT, "empty buffer or bad sample rate");
+    // a voice's offset into the pool is one 32-bit slot word
+    if (pool_samples_with(at, n_frames) > 0xFFFFFFFFull) return fail(KNH_ERR_INVALID_ARGUMENT, "the pool of buffers would hold more than 2^32 - 1 samples");
+    std::vector<F> copy(static_cast<const F*>(samples), static_cast<const F*>(samples) + n_frames);  // (first: nothing changes if it does not fit)
+    if (at == pool.size()) pool.emplace_back();
+    PoolEntry& e = pool[at];
+    e.samples.swap(copy);
+    e.sr = sr;
+    e.n_frames = static_cast<uint32_t>(n_frames);
+    return KNH_OK;
+  }
+  int set_buffer(uint32_t stage, const void* samples, size_t n_frames, double sr) override {
+    return put_buffer(0, "knh_bank_set_buffer", stage, samples, n_frames, sr);
+  }
+  int add_buffer(uint32_t stage, const void* samples, size_t n_frames, double sr, uint32_t* out_index) override {
+    const size_t at = pool.size();
+    int rc = put_buffer(at, "knh_bank_add_buffer", stage, samples, n_frames, sr);
+    if (rc == KNH_OK && out_index) *out_index = static_cast<uint32_t>(at);
+    return rc;
+  }
+  void drop_last_buffer(uint32_t) override {
+    if (!initialised && !pool.empty()) pool.pop_back();
+  }
+  uint32_t buffer_count(uint32_t stage) const override {
+    return stage < stages.size() && stages[stage].kind == KNH_STAGE_BUFFER_READER ? static_cast<uint32_t>(pool.size()) : 0u;
+  }
+  // knh_bank_assign_buffers.  Before init: the entry each voice is constructed on (and, with `args`, its constructor
+  // arguments).  After init: the voice's reader becomes a new one on that entry -- every slot of the stage is patched at the
+  // first frame of the next launch, the way a parameter change is, and the shadows the seconds-valued setters read follow.
+  int assign_buffers(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* ids, const double* args) override {
+    if (stage >= stages.size() || stages[stage].kind != KNH_STAGE_BUFFER_READER) return fail(KNH_ERR_INVALID_ARGUMENT, "not a BufferReader stage");
+    if (count && (!voices || !ids)) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
+    const StageInfo& S = stages[stage];
+    if (initialised) {
+      if (!args) return fail(KNH_ERR_INVALID_ARGUMENT, "after knh_bank_init knh_bank_assign_buffers needs the new reader's constructor arguments");
+      if (S.flags & KNH_STAGE_FLAG_SMOOTH_PARAMS) return fail(KNH_ERR_UNSUPPORTED_CHAIN, "a BufferReader wrapped in WrSmoothParams keeps its buffer after knh_bank_init");
+      for (const StageInfo& T : stages)  // (the voice's single done frame could not be told apart from the old reader's end)
+        if (T.kind == KNH_STAGE_MUL_ENV_ASR || T.kind == KNH_STAGE_MUL_ENV_AR || T.kind == KNH_STAGE_MUL_ENVELOPE)
+          return fail(KNH_ERR_UNSUPPORTED_CHAIN, "a chain in which an envelope can mark a voice done keeps its buffers after knh_bank_init");
+    }
+    for (size_t k = 0; k < count; ++k) {
+      if (voices[k] >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
+      if (ids[k] >= pool.size()) return fail(KNH_ERR_OUT_OF_RANGE, "buffer index out of range");
+    }
+    if (count == 0) return KNH_OK;
+    if (buf_id.empty()) buf_id.assign(nv, 0u);
+    if (!initialised) {
+      for (size_t k = 0; k < count; ++k) {
+        buf_id[voices[k]] = ids[k];
+        if (args) std::copy(args + 3 * k, args + 3 * k + 3, ctor[stage].begin() + static_cast<size_t>(voices[k]) * 3);
+      }
+      return KNH_OK;
+    }
+    note_frame(frame_base);
+    pending.reserve(pending.size() + count * 12);
+    for (size_t k = 0; k < count; ++k) {
+      const uint32_t v = voices[k];
+      buf_id[v] = ids[k];
+      reader_construct(v, args + 3 * k, [&](int rel, uint32_t word) {
+        pending.push_back(HostEvent{v, frame_base, knh_dev::EV_SET, static_cast<uint32_t>(S.slot_base + rel), word});
+      });
+    }
     return KNH_OK;
   }
 
@@ -505,29 +603,14 @@ struct Bank final : knh_bank {
             }
           } break;
           case KNH_STAGE_BUFFER_READER: {  // buffer.rs:40-57 (new, start_at), :106-115 (init)
-            if (h_buffer.empty()) return fail(KNH_ERR_INVALID_ARGUMENT, "BufferReader stage without knh_bank_set_buffer");
+            if (pool.empty()) return fail(KNH_ERR_INVALID_ARGUMENT, "BufferReader stage without knh_bank_set_buffer or knh_bank_add_buffer");
             if (S.dcpb > 0) return fail(KNH_ERR_INVALID_ARGUMENT, "BufferReader cannot be wrapped in WrPreciseTiming here");
-            if (v == 0) { buf_start.assign(nv, 0.0); buf_dur.assign(nv, 0.0); buf_rate.assign(nv, 0.0); }
-            buf_base_rate = buffer_sr / static_cast<double>(sr);  // Buffer::buf_rate_scale
-            const double length_seconds = static_cast<double>(h_buffer.size()) / buffer_sr;
-            auto secs_to_frames = [&](double secs) {  // Seconds::from_secs_f64(secs).to_samples_f64(buffer_sr), time.rs:59-64,92-96
-              const double whole = std::floor(secs);
-              const uint32_t tes = sat_u32((secs - std::trunc(secs)) * 282240000.0);
-              return static_cast<double>(sat_u32(whole)) * buffer_sr + (static_cast<double>(tes) * buffer_sr) / 282240000.0;
-            };
-            const double start = secs_to_frames(a[2]), dur = secs_to_frames(length_seconds);
-            buf_start[v] = start; buf_dur[v] = dur; buf_rate[v] = a[0];
-            auto put2 = [&](int rel, double d) {
-              const uint64_t b = to_bits(d);
-              slot(S.slot_base + rel, v) = static_cast<W>(static_cast<uint32_t>(b));
-              slot(S.slot_base + rel + 1, v) = static_cast<W>(static_cast<uint32_t>(b >> 32));
-            };
-            put2(0, start);                   // jump_to(start_frame)
-            put2(2, buf_base_rate * a[0]);    // base_rate * rate, the per-sample step
-            put2(4, start);
-            put2(6, start + dur);
-            slot(S.slot_base + 8, v) = 0;
-            slot(S.slot_base + 9, v) = a[1] != 0.0 ? 1u : 0u;
+            if (v == 0) {
+              buf_start.assign(nv, 0.0); buf_dur.assign(nv, 0.0); buf_rate.assign(nv, 0.0);
+              uint64_t off = 0;  // (put_buffer has kept the sum within 32 bits)
+              for (PoolEntry& e : pool) { e.off = static_cast<uint32_t>(off); off += (e.n_frames + 63ull) & ~63ull; }
+            }
+            reader_construct(v, a, [&](int rel, uint32_t word) { slot(S.slot_base + rel, v) = static_cast<W>(word); });
           } break;
           case KNH_STAGE_PHASOR: {  // osc.rs:181-188 (new), :197-200 (init: step = freq * (1 / sample_rate))
             const double step = a[0] * (1.0 / static_cast<double>(sr));
@@ -653,9 +736,14 @@ struct Bank final : knh_bank {
       KNH_HIP(hipMalloc(&d_sine, 16384 * sizeof(float)));
       KNH_HIP(hipMemcpy(d_sine, table.data(), 16384 * sizeof(float), hipMemcpyHostToDevice));
     }
-    if (!h_buffer.empty()) {
-      KNH_HIP(hipMalloc(&d_buffer, h_buffer.size() * sizeof(F)));
-      KNH_HIP(hipMemcpy(d_buffer, h_buffer.data(), h_buffer.size() * sizeof(F), hipMemcpyHostToDevice));
+    if (!pool.empty()) {
+      const size_t total = static_cast<size_t>(pool_samples_with(pool.size(), 0));
+      KNH_HIP(hipMalloc(&d_buffer, total * sizeof(F)));
+      KNH_HIP(hipMemset(d_buffer, 0, total * sizeof(F)));
+      for (PoolEntry& e : pool) {
+        KNH_HIP(hipMemcpy(d_buffer + e.off, e.samples.data(), e.samples.size() * sizeof(F), hipMemcpyHostToDevice));
+        std::vector<F>().swap(e.samples);
+      }
     }
     if (!delay_len.empty()) {
       uint32_t mx = 0;
@@ -1158,17 +1246,13 @@ struct Bank final : knh_bank {
           set(rel, static_cast<uint32_t>(b));
           set(rel + 1, static_cast<uint32_t>(b >> 32));
         };
-        auto secs_to_frames = [&](double secs) {
-          const double whole = std::floor(secs);
-          const uint32_t tes = sat_u32((secs - std::trunc(secs)) * 282240000.0);
-          return static_cast<double>(sat_u32(whole)) * buffer_sr + (static_cast<double>(tes) * buffer_sr) / 282240000.0;
-        };
+        const double buffer_sr = buf_of(v).sr;  // the voice's own Buffer's: seconds become its frames, its rate scale
         switch (param) {
-          case 0: buf_rate[v] = f; set2(2, buf_base_rate * f); break;
+          case 0: buf_rate[v] = f; set2(2, (buffer_sr / static_cast<double>(sample_rate)) * f); break;
           case 1: set(9, iv != 0 ? 1u : 0u); break;
-          case 2: buf_start[v] = secs_to_frames(f); set2(4, buf_start[v]); set2(6, buf_start[v] + buf_dur[v]); break;
-          case 3: buf_dur[v] = secs_to_frames(f); set2(6, buf_start[v] + buf_dur[v]); break;
-          case 4: set2(6, secs_to_frames(f)); break;
+          case 2: buf_start[v] = secs_to_frames(f, buffer_sr); set2(4, buf_start[v]); set2(6, buf_start[v] + buf_dur[v]); break;
+          case 3: buf_dur[v] = secs_to_frames(f, buffer_sr); set2(6, buf_start[v] + buf_dur[v]); break;
+          case 4: set2(6, secs_to_frames(f, buffer_sr)); break;
           default: set2(0, buf_start[v]); set(8, 0); break;  // t_restart -> reset -> jump_to(start_frame)
         }
       } break;

@@ -491,8 +491,7 @@ struct VoiceKernelArgs {
   u32 seg_max;
   void* delay_ring;                 // SampleDelay rings [n_voices][delay_stride] of F, or null
   u32 delay_stride;
-  const void* buffer;               // BufferReader's shared Buffer (single channel, F), or null
-  u32 buffer_frames;
+  const void* buffer;               // BufferReader's pool of Buffers (single channel, F; a voice's offset and length are its slots), or null
   const void* input;                // the bank node's input channels, [n_blocks][in_channels][block_size] of F, or null
   u32 in_channels;
   const u32* ev_start;              // [n_voices + 1] or null when the block has no events
@@ -969,7 +968,6 @@ __global__ void __launch_bounds__(WAVES * 64) voice_kernel(VoiceKernelArgs<F> a)
   ctx.delay_stride = a.delay_stride;
   ctx.ring_sink_row = a.n_voices;
   ctx.buffer = a.buffer;
-  ctx.buffer_frames = a.buffer_frames;
   ctx.input_block = a.input;
   ctx.in_stride = a.block_size;
   ctx.sample_rate = a.sample_rate;

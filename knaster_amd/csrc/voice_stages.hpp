@@ -103,8 +103,7 @@ struct Ctx {
   u32 seg_max;
   void* delay_ring;         // SampleDelay: [voice][delay_stride] samples of F, each voice's ring contiguous
   u32 delay_stride;
-  const void* buffer;       // BufferReader: the bank's shared single-channel Buffer, samples of F
-  u32 buffer_frames;
+  const void* buffer;       // BufferReader: the bank's pool of single-channel Buffers, samples of F (each voice's offset and length: its slots)
   const void* input_block;  // the bank node's input channels for the block being processed: [in_channels][in_stride] of F
   u32 in_stride;            // = block_size
   u32 sample_rate;          // ctx.sample_rate(), for setters that run on the device (audio-rate parameters)
@@ -692,18 +691,22 @@ struct PolyBlepOsc : StageDefaults {
   }
 };
 
-// BufferReader<F, U1> -- buffer.rs:19-191: plays the bank's shared Buffer (dsp/buffer.rs) from an f64 read pointer with
+// BufferReader<F, U1> -- buffer.rs:19-191: plays one Buffer (dsp/buffer.rs) of the bank's pool -- the voice's own: its
+// first sample's offset in the pool and its length are two of the voice's slots -- from an f64 read pointer with
 // linear interpolation (Buffer::get_linear_interp_f64, :100-110), per-voice rate, start and end, looping or one-shot
-// (mark_done(i + 1) at the frame after the last one, then silence).  All positions are f64 for any F.
+// (mark_done(i + 1) at the frame after the last one, then silence).  All positions are f64 for any F.  The offset and the
+// length are read once per launch (load) and patched like any parameter (the host swaps a voice's buffer with EV_SETs of
+// every slot at a launch's first frame); no sample goes through a table of buffers.
 // slots: 0,1 read_pointer  2,3 step (= base_rate * rate)  4,5 start_frame  6,7 end_frame  8 finished  9 looping
+//        10 buffer offset (samples from the pool's start)  11 buffer length (frames)
 struct BufferReader : StageDefaults {
-  static constexpr int kSlots = 10;
-  static constexpr u32 kMutableMask = 0b0100000011u;
+  static constexpr int kSlots = 12;
+  static constexpr u32 kMutableMask = 0b000100000011u;
   static constexpr bool kUsesSine = false;
   static constexpr bool kIsEnv = true;  // it marks done and can be "stopped"
   static constexpr bool kNeedsBind = true;
   static constexpr bool kHasSeg = true;
-  template <typename F> struct Regs { double rp, step, start, end; u32 finished, looping, seg; const F* buf; u32 n; };
+  template <typename F> struct Regs { double rp, step, start, end; u32 finished, looping, seg; const F* buf; u32 n, off; };
   template <typename F> static __device__ __forceinline__ bool is_stopped(const Regs<F>& r) { return r.finished != 0u; }
   template <typename W> static __device__ __forceinline__ double ld2(const W* s, long st, int k) {
     const u64 lo = (u32)s[(long)k * st], hi = (u32)s[(long)(k + 1) * st];
@@ -713,12 +716,12 @@ struct BufferReader : StageDefaults {
   static __device__ __forceinline__ void load(Regs<F>& r, const W* s, long st) {
     r.rp = ld2(s, st, 0); r.step = ld2(s, st, 2); r.start = ld2(s, st, 4); r.end = ld2(s, st, 6);
     r.finished = (u32)s[8 * st]; r.looping = (u32)s[9 * st];
-    r.seg = 0; r.buf = nullptr; r.n = 0;
+    r.off = (u32)s[10 * st]; r.n = (u32)s[11 * st];
+    r.seg = 0; r.buf = nullptr;
   }
   template <typename F>
   static __device__ __forceinline__ void bind(Regs<F>& r, const Ctx& c) {
-    r.buf = reinterpret_cast<const F*>(c.buffer);
-    r.n = c.buffer_frames;
+    r.buf = reinterpret_cast<const F*>(c.buffer) + r.off;
   }
   template <typename F, typename W>
   static __device__ __forceinline__ void store(const Regs<F>& r, W* s, long st) {
@@ -762,7 +765,10 @@ struct BufferReader : StageDefaults {
       case 4: r.start = lo(r.start, w); break; case 5: r.start = hi(r.start, w); break;
       case 6: r.end = lo(r.end, w); break;    case 7: r.end = hi(r.end, w); break;
       case 8: r.finished = w; break;
-      default: r.looping = w; break;
+      case 9: r.looping = w; break;
+      case 10: r.off = w; break;
+      case 11: r.n = w; break;
+      default: break;
     }
   }
 };

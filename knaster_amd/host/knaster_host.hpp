@@ -98,6 +98,11 @@ struct UGenSpec {
   uint16_t precise_timing_ = 0;
   bool is_constant = false, is_env = false;
   uint16_t outputs = 1;              // UGen::Outputs (Pan2: 2)
+  // BufferReader: the Buffer the node is constructed on (the Arc<Buffer<F>> of buffer.rs:43, kept alive by the spec)
+  std::shared_ptr<const void> buffer;
+  const void* buffer_samples = nullptr;
+  size_t buffer_frames = 0, buffer_word = 0;  // buffer_word: sizeof(F) of its samples
+  double buffer_sample_rate = 0.0;
   // wrappers_core.rs:26-111
   UGenSpec wr_mul(double v) && { wrappers.emplace_back(KNH_STAGE_WR_MUL, v); return std::move(*this); }
   UGenSpec wr_add(double v) && { wrappers.emplace_back(KNH_STAGE_WR_ADD, v); return std::move(*this); }
@@ -148,6 +153,32 @@ inline UGenSpec Envelope(double start_value, const std::vector<EnvelopeSegment>&
   for (const EnvelopeSegment& sg : segments) { a.push_back(sg.duration); a.push_back(sg.value); }
   UGenSpec s(KNH_STAGE_MUL_ENVELOPE, std::move(a));
   s.is_env = true;
+  return s;
+}
+// Buffer::from_vec(samples, sample_rate) -- dsp/buffer.rs:58-66 (single channel); shared between the readers made on it
+template <typename F>
+struct Buffer {
+  std::vector<F> samples;
+  double sample_rate = 48000.0;
+  static std::shared_ptr<const Buffer<F>> from_vec(std::vector<F> samples, double sample_rate) {
+    auto b = std::make_shared<Buffer<F>>();
+    b->samples = std::move(samples);
+    b->sample_rate = sample_rate;
+    return b;
+  }
+};
+// BufferReader::<F, U1>::new(buffer, rate, looping).start_at(start_s) -- buffer.rs:43-57.  Voices of one chain shape share a
+// bank whatever Buffer each was made on: the bank's pool holds every distinct Buffer once (knh_bank_add_buffer) and each voice
+// reads its own (knh_bank_assign_buffers).
+template <typename F>
+inline UGenSpec BufferReader(std::shared_ptr<const Buffer<F>> buffer, double rate, bool looping, double start_s = 0.0) {
+  if (!buffer || buffer->samples.empty()) throw std::runtime_error("BufferReader needs a Buffer with samples");
+  UGenSpec s(KNH_STAGE_BUFFER_READER, {rate, looping ? 1.0 : 0.0, start_s});
+  s.buffer_samples = buffer->samples.data();
+  s.buffer_frames = buffer->samples.size();
+  s.buffer_word = sizeof(F);
+  s.buffer_sample_rate = buffer->sample_rate;
+  s.buffer = std::move(buffer);
   return s;
 }
 inline UGenSpec Constant(double value) { UGenSpec s(KNH_STAGE_MUL_CONST, {value}); s.is_constant = true; return s; }
@@ -491,6 +522,26 @@ class Graph {
           for (size_t vi = 0; vi < members.size(); ++vi)
             std::copy(voices[members[vi]].plan.stage_args[s].begin(), voices[members[vi]].plan.stage_args[s].end(), args.begin() + static_cast<long>(vi * n_args));
           check(b, knh_bank_set_ctor_args(b.h, static_cast<uint32_t>(s), 0, b.n_voices, args.data(), static_cast<uint32_t>(n_args)));
+        }
+        for (size_t s = 0; s < b.plan.stages.size(); ++s) {
+          // reader voices: every distinct Buffer once in the bank's pool, in order of first appearance; each voice on its own
+          if (b.plan.stages[s].kind != KNH_STAGE_BUFFER_READER) continue;
+          std::vector<const void*> pooled;
+          std::vector<uint32_t> vs, ids;
+          for (size_t vi = 0; vi < members.size(); ++vi) {
+            const UGenSpec& spec = nodes_[static_cast<size_t>(voices[members[vi]].plan.stage_node[s])].spec;
+            if (!spec.buffer_samples || spec.buffer_word != sizeof(F)) throw GraphError("BufferReader: its Buffer must hold samples of the graph's type");
+            size_t id = static_cast<size_t>(std::find(pooled.begin(), pooled.end(), spec.buffer_samples) - pooled.begin());
+            if (id == pooled.size()) {
+              uint32_t index = 0;
+              check(b, knh_bank_add_buffer(b.h, static_cast<uint32_t>(s), spec.buffer_samples, spec.buffer_frames, spec.buffer_sample_rate, &index));
+              pooled.push_back(spec.buffer_samples);
+              id = index;
+            }
+            vs.push_back(static_cast<uint32_t>(vi));
+            ids.push_back(static_cast<uint32_t>(id));
+          }
+          check(b, knh_bank_assign_buffers(b.h, static_cast<uint32_t>(s), vs.size(), vs.data(), ids.data(), nullptr));
         }
         // UGen::init runs at push time in the reference (graph.rs:462-475); the bank's voices all init here
         check(b, knh_bank_init(b.h, sample_rate_, block_size_));

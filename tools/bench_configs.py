@@ -81,7 +81,51 @@ def run(name, n_voices=None, launches=16, blocks=32, allow_fma=False, host_threa
     b.close()
 
 
+def run_sampler(case, n_voices=16384, block_size=512, launches=16, blocks=32, repeats=3):
+    """The sampler workload, BufferReader -> x const in f32, every voice looping at a rate and from a start of its own.
+    case "shared": one Buffer of 1 s for every voice (knh_bank_set_buffer alone -- also what a build without the pool runs);
+    case "pool": 64 Buffers of about 1 s each (knh_bank_add_buffer), voice v on entry v % 64.
+    One JSON line per repeat: the kernel time per block from the bank's own device events."""
+    from knaster_amd.bank import Stage
+    stages = [Stage(L.STAGE_BUFFER_READER), Stage(L.STAGE_MUL_CONST)]
+    rng = np.random.default_rng(7)
+    v = np.arange(n_voices, dtype=np.uint32)
+    u = v.astype(np.int64)
+    ctor = np.stack([0.5 + 1.5 * ((u * 2654435761) % 1000) / 1000.0, np.ones(n_voices), 0.9 * ((u * 40503) % 997) / 997.0], axis=1)
+    n_buffers = 64 if case == "pool" else 1
+    for rep in range(repeats):
+        b = knaster_amd.VoiceBank(stages, n_voices, L.F32, 2, L.MIX_TREE)
+        b.set_ctor_args(0, ctor)
+        b.set_ctor_args(1, np.full((n_voices, 1), 1.0 / n_voices))
+        if case == "pool":
+            for k in range(n_buffers):
+                b.add_buffer(0, rng.uniform(-1, 1, 48000 + 37 * k).astype(np.float32), 48000.0)
+            b.assign_buffers(0, v, v % n_buffers)
+        else:
+            b.set_buffer(0, rng.uniform(-1, 1, 48000).astype(np.float32), 48000.0)
+        b.init(configs.SAMPLE_RATE, block_size)
+        for _ in range(3):
+            b.process_blocks_device(blocks)
+        b.synchronize()
+        b.timing_reset(True)
+        t0 = time.perf_counter()
+        for _ in range(launches):
+            b.process_blocks_device(blocks)
+        b.synchronize()
+        dt = time.perf_counter() - t0
+        kms, n = b.timing_read()
+        print(json.dumps({"config": "sampler", "case": case, "buffers": n_buffers, "voices": n_voices, "block_size": block_size, "sample_type": "f32",
+                          "signature": b.debug_signature(), "repeat": rep, "us_per_block_kernel": kms * 1e3 / (n * blocks),
+                          "us_per_block_wall": dt * 1e6 / (launches * blocks),
+                          "kernel_only_voice_samples_per_s": float(n_voices) * block_size * blocks * n / (kms * 1e-3)}), flush=True)
+        b.close()
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "sampler":  # tools/bench_configs.py sampler shared|pool: BASELINE.md section 4, the sampler rows
+        for case in sys.argv[2:] or ["shared", "pool"]:
+            run_sampler(case)
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "ab":  # the configs that run on kernels other than the headline one
         run("C3", n_voices=65536)
         run("C3", n_voices=262144, launches=4)
