@@ -111,7 +111,14 @@ pub const KNH_STAGE_MATH_DIV: u16 = 36;
 pub const KNH_STAGE_MATH_POW: u16 = 37;
 pub const KNH_STAGE_INPUT: u16 = 38;
 pub const KNH_STAGE_GALACTIC: u16 = 39;
-pub const KNH_STAGE_KIND_COUNT: u16 = 40;
+// Math1UGen<F, Op> (knaster_core_dsp/src/ugens/math.rs:167-305), in the reference's declaration order
+pub const KNH_STAGE_MATH1_CEIL: u16 = 40;
+pub const KNH_STAGE_MATH1_SQRT: u16 = 41;
+pub const KNH_STAGE_MATH1_FLOOR: u16 = 42;
+pub const KNH_STAGE_MATH1_TRUNC: u16 = 43;
+pub const KNH_STAGE_MATH1_FRACT: u16 = 44;
+pub const KNH_STAGE_MATH1_EXP: u16 = 45;
+pub const KNH_STAGE_KIND_COUNT: u16 = 46;
 
 // knh_svf_type = SvfFilterType, knaster_core_dsp/src/ugens/svf.rs:19-39
 pub const KNH_SVF_LOW: u32 = 0;
@@ -133,6 +140,14 @@ pub const KNH_MIX_LEFT_FOLD: u32 = 1;
 
 pub const KNH_FLAG_ANY_DONE: u32 = 1 << 0;
 pub const KNH_FLAG_ALL_DONE: u32 = 1 << 1;
+// KNH_DEBUG_FORM_*: word 2 of knh_bank_debug_words, the kernel form the bank's launches take
+pub const KNH_DEBUG_FORM_WHOLE_CHAIN: u32 = 0;
+pub const KNH_DEBUG_FORM_PIPELINE: u32 = 1;
+pub const KNH_DEBUG_FORM_MANY_WAVE: u32 = 2;
+pub const KNH_DEBUG_FORM_WHOLE_CHAIN_FUSED: u32 = 3;
+pub const KNH_DEBUG_FORM_PIPELINE_FUSED: u32 = 4;
+pub const KNH_DEBUG_FORM_FRAME_INTERP: u32 = 5;
+pub const KNH_DEBUG_FORM_FRAME_JIT: u32 = 6;
 
 #[link(name = "knaster_hip")]
 unsafe extern "C" {

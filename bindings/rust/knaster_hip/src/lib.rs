@@ -82,6 +82,26 @@ pub fn stage(kind: u16) -> Stage {
 pub fn galactic(replace: f64, detune: f64, brightness: f64, bigness: f64, wet: f64, fpd_l: u32, fpd_r: u32) -> (Stage, [f64; 7]) {
     (stage(KNH_STAGE_GALACTIC), [replace, detune, brightness, bigness, wet, fpd_l as f64, fpd_r as f64])
 }
+/// The six `Math1UGen` stages, named as the reference's factories are (knaster/src/math_ugens.rs): `x >> sqrt()` is
+/// `[.., sqrt()]` in the stage list.  No constructor arguments, no parameters.
+pub fn fract() -> Stage {
+    stage(KNH_STAGE_MATH1_FRACT)
+}
+pub fn ceil() -> Stage {
+    stage(KNH_STAGE_MATH1_CEIL)
+}
+pub fn exp() -> Stage {
+    stage(KNH_STAGE_MATH1_EXP)
+}
+pub fn trunc() -> Stage {
+    stage(KNH_STAGE_MATH1_TRUNC)
+}
+pub fn floor() -> Stage {
+    stage(KNH_STAGE_MATH1_FLOOR)
+}
+pub fn sqrt() -> Stage {
+    stage(KNH_STAGE_MATH1_SQRT)
+}
 pub trait StageExt {
     /// `.precise_timing::<N>()` on the stage's node (wrappers_core.rs:106-111)
     fn precise_timing(self, max_changes_per_block: u16) -> Self;

@@ -151,10 +151,24 @@ typedef enum knh_value_kind {
  *     reference's "256 FM cascade" shape (knaster_benchmarks/benches/graph_dsp_performance.rs:37-72) is one.  Such voices
  *     run in the single-wave kernel form, fused at knh_bank_init time: every stage unrolls into the one kernel, so a fused
  *     voice may hold at most 512 stages (KNH_ERR_UNSUPPORTED_CHAIN beyond; 91 stages fuse in 2 s, 379 in a minute).
- *     A voice made of SIN_WT sources, the *_CONST / WR_* arithmetic and MATH_ADD/_SUB/_MUL/_DIV only (nothing wrapped in
+ *     A voice made of SIN_WT sources, the *_CONST / WR_* arithmetic, MATH_ADD/_SUB/_MUL/_DIV and MATH1_* only (nothing wrapped in
  *     WrPreciseTiming or WrSmoothParams) is parallel in time -- every such stage is a pure function of the frame index --
  *     and runs a lane per FRAME instead of a lane per voice, up to 4 096 stages, with the same results (the 256-oscillator
  *     cascade itself: 1 531 stages in ONE voice, 11 us per 128-frame block).
+ * KNH_STAGE_MATH1_CEIL / _SQRT / _FLOOR / _TRUNC / _FRACT / _EXP    x >> g.push(ceil()), sqrt(), floor(), trunc(), fract(), exp()
+ *                           (Math1UGen<F, Op>, math.rs:167-305; the factories of knaster/src/math_ugens.rs)      1   (none)
+ *     op(x) of ONE signal: the output of stage `input` (0: the stage before it), like any other non-source stage.  No
+ *     parameters, no state, no constructor arguments: ar_param, input2, delayed_changes_per_block and
+ *     KNH_STAGE_FLAG_SMOOTH_PARAMS must be 0 (KNH_ERR_INVALID_ARGUMENT), and every parameter call that names such a stage
+ *     (knh_bank_param_apply, _apply_range, _apply_many[_at], knh_bank_set_delay_within_block_for_param; any kind of bank) is
+ *     KNH_ERR_INVALID_ARGUMENT -- before knh_bank_init too: the mistake is about the chain, which is known from knh_bank_create
+ *     on, so it is named ahead of KNH_ERR_NOT_INITIALISED (which a call on any other stage gets there).  Its output may drive any supported ar_param of another stage (exp of a ramp on SIN_WT freq).
+ *     What Rust's std does for F:  ceil, floor, trunc: IEEE round-to-integral, the sign of zero kept (ceil(-0.5) = -0.0),
+ *     +-inf and NaN pass.  fract: x - trunc(x), NOT x - floor(x): fract(-1.25) = -0.25, fract(-0.0) = +0.0, fract(+-inf) = NaN.
+ *     sqrt: correctly rounded, subnormal inputs included; sqrt(-0.0) = -0.0, a negative input gives NaN.  All five bit-exact
+ *     (a NaN result is a NaN; its sign and payload are the device's).  exp: the device library's exp (tolerance only, like
+ *     powf: DESIGN.md section 2).  In every kernel form: chains, pipelines, graph voices, and -- being pure functions of their
+ *     input sample -- the lane-per-frame voices below, beside SIN_WT and the arithmetic.
  * KNH_STAGE_INPUT           (graph input) >> ...   the bank NODE's input channel `channel`: UGen::Inputs > 0,
  *                           `input.read(channel, frame)` in process_block (ugen.rs:263-284)               0    channel
  *     a source whose signal is the same for every voice: whatever the host graph connected to that input of the bank
@@ -235,7 +249,13 @@ typedef enum knh_stage_kind {
   KNH_STAGE_MATH_POW = 37,
   KNH_STAGE_INPUT = 38,
   KNH_STAGE_GALACTIC = 39,
-  KNH_STAGE_KIND_COUNT = 40
+  KNH_STAGE_MATH1_CEIL = 40,
+  KNH_STAGE_MATH1_SQRT = 41,
+  KNH_STAGE_MATH1_FLOOR = 42,
+  KNH_STAGE_MATH1_TRUNC = 43,
+  KNH_STAGE_MATH1_FRACT = 44,
+  KNH_STAGE_MATH1_EXP = 45,
+  KNH_STAGE_KIND_COUNT = 46
 } knh_stage_kind;
 
 /* SvfFilterType: knaster_core_dsp/src/ugens/svf.rs:19-39 (out-of-range -> Low,
@@ -535,7 +555,17 @@ int32_t knh_bank_param_apply_many_at(knh_bank* bank, uint32_t block_offset, size
  * ugen.rs:169-175): done_frames[v] = frame in block, or UINT32_MAX. */
 int32_t knh_bank_read_done_frames(knh_bank* bank, uint32_t* done_frames);
 /* Diagnostics: 16 device words of the last launch (0,1: the done/running summary; 4..8: per-role busy
- * cycles per tile when the library was built with -DKNH_DAG_STAMPS, zero otherwise). */
+ * cycles per tile when the library was built with -DKNH_DAG_STAMPS, zero otherwise).  Word 2 is filled in by the host: the
+ * kernel form the bank's launches take (KNH_DEBUG_FORM_*; a bank cut into voice ranges reports its first range's). */
+enum {
+  KNH_DEBUG_FORM_WHOLE_CHAIN = 0,       /* pre-built kernel, a wavefront runs a voice group's whole chain */
+  KNH_DEBUG_FORM_PIPELINE = 1,          /* pre-built wave pipeline */
+  KNH_DEBUG_FORM_MANY_WAVE = 2,         /* pre-built, 4 / 8 / 16 whole-chain wavefronts per workgroup */
+  KNH_DEBUG_FORM_WHOLE_CHAIN_FUSED = 3, /* fused at knh_bank_init (chains without a pre-built kernel, graph voices) */
+  KNH_DEBUG_FORM_PIPELINE_FUSED = 4,    /* wave pipeline built at knh_bank_init */
+  KNH_DEBUG_FORM_FRAME_INTERP = 5,      /* a lane per frame, interpreted (KNH_FRAME_JIT=0) */
+  KNH_DEBUG_FORM_FRAME_JIT = 6          /* a lane per frame, straight-line kernel built at knh_bank_init */
+};
 int32_t knh_bank_debug_words(knh_bank* bank, uint32_t* out16);
 /* Diagnostics: the chain as the device code names it (one character per stage, "@a,b,o" signal slots and "#R" for a
  * voice that is a graph, "%P" for an audio-rate parameter): what a chain without a pre-built kernel is fused from at

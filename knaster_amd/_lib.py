@@ -27,7 +27,8 @@ VALUE_FLOAT, VALUE_TRIGGER, VALUE_INTEGER, VALUE_BOOL, VALUE_SMOOTHING = 0, 1, 2
  STAGE_WR_ADD, STAGE_WR_SUB, STAGE_MUL_ENVELOPE, STAGE_WR_VSUB, STAGE_WR_DIV, STAGE_WR_VDIV, STAGE_WR_POWF,
  STAGE_WR_POWI, STAGE_POW_CONST, STAGE_SAMPLE_DELAY, STAGE_PHASOR, STAGE_SAFETY_LIMITER, STAGE_POLYBLEP, STAGE_ALLPASS_DELAY, STAGE_ALLPASS_FB_DELAY, STAGE_BUFFER_READER,
  STAGE_WHITE_NOISE, STAGE_PINK_NOISE, STAGE_BROWN_NOISE, STAGE_RANDOM_LIN, STAGE_PAN2,
- STAGE_MATH_ADD, STAGE_MATH_SUB, STAGE_MATH_MUL, STAGE_MATH_DIV, STAGE_MATH_POW, STAGE_INPUT, STAGE_GALACTIC) = range(40)
+ STAGE_MATH_ADD, STAGE_MATH_SUB, STAGE_MATH_MUL, STAGE_MATH_DIV, STAGE_MATH_POW, STAGE_INPUT, STAGE_GALACTIC,
+ STAGE_MATH1_CEIL, STAGE_MATH1_SQRT, STAGE_MATH1_FLOOR, STAGE_MATH1_TRUNC, STAGE_MATH1_FRACT, STAGE_MATH1_EXP) = range(46)
 STAGE_FLAG_AR_FREQ = 1
 STAGE_FLAG_SMOOTH_PARAMS = 2
 # knh_svf_type
@@ -35,6 +36,9 @@ SVF_LOW, SVF_HIGH, SVF_BAND, SVF_NOTCH, SVF_PEAK, SVF_ALL, SVF_BELL, SVF_LOW_SHE
 # knh_mix_mode
 MIX_TREE, MIX_LEFT_FOLD = 0, 1
 FLAG_ANY_DONE, FLAG_ALL_DONE = 1, 2
+# KNH_DEBUG_FORM_*: word 2 of knh_bank_debug_words
+(DEBUG_FORM_WHOLE_CHAIN, DEBUG_FORM_PIPELINE, DEBUG_FORM_MANY_WAVE, DEBUG_FORM_WHOLE_CHAIN_FUSED, DEBUG_FORM_PIPELINE_FUSED,
+ DEBUG_FORM_FRAME_INTERP, DEBUG_FORM_FRAME_JIT) = range(7)
 
 # constructor-argument count per stage kind (table in knaster_hip.h)
 STAGE_CTOR_ARGS = {  # STAGE_MUL_ENVELOPE takes 4 + 2 * n_max (variable)
@@ -45,6 +49,7 @@ STAGE_CTOR_ARGS = {  # STAGE_MUL_ENVELOPE takes 4 + 2 * n_max (variable)
     STAGE_WHITE_NOISE: 1, STAGE_PINK_NOISE: 1, STAGE_BROWN_NOISE: 1, STAGE_RANDOM_LIN: 2, STAGE_PAN2: 1,
     STAGE_MATH_ADD: 0, STAGE_MATH_SUB: 0, STAGE_MATH_MUL: 0, STAGE_MATH_DIV: 0, STAGE_MATH_POW: 0, STAGE_INPUT: 1,
     STAGE_GALACTIC: 7,  # replace, detune, brightness, bigness, wet, fpd_l, fpd_r
+    STAGE_MATH1_CEIL: 0, STAGE_MATH1_SQRT: 0, STAGE_MATH1_FLOOR: 0, STAGE_MATH1_TRUNC: 0, STAGE_MATH1_FRACT: 0, STAGE_MATH1_EXP: 0,
 }
 
 

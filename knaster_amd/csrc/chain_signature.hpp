@@ -28,6 +28,11 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     if (math2 && (st[i].input == 0 || st[i].input2 == 0)) { *why = "a KNH_STAGE_MATH_* stage names both of its operands (input, input2)"; return KNH_ERR_INVALID_ARGUMENT; }
     if (!math2 && st[i].input2 != 0 && st[i].ar_param == 0) { *why = "input2 is the second operand of the KNH_STAGE_MATH_* stages and the driver of an audio-rate parameter (ar_param)"; return KNH_ERR_INVALID_ARGUMENT; }
     if (math2 && st[i].ar_param != 0) { *why = "a KNH_STAGE_MATH_* stage has no parameters"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (is_math1_kind(st[i].kind)) {  // Math1UGen (math.rs:167-305): one operand (`input`), no parameters -- nothing an audio-rate link, WrPreciseTiming or WrSmoothParams could act on
+      if (st[i].ar_param != 0 || st[i].input2 != 0) { *why = "a KNH_STAGE_MATH1_* stage has no parameters (ar_param = 0, input2 = 0)"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (st[i].delayed_changes_per_block != 0) { *why = "a KNH_STAGE_MATH1_* stage has no parameters: delayed_changes_per_block must be 0"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (st[i].flags & KNH_STAGE_FLAG_SMOOTH_PARAMS) { *why = "a KNH_STAGE_MATH1_* stage has no parameters: SMOOTH_PARAMS does not apply"; return KNH_ERR_INVALID_ARGUMENT; }
+    }
     if (is_wrapper_kind(st[i].kind) && st[i].input != 0) { *why = "a wrapper stage wraps the stage before it (input = 0)"; return KNH_ERR_INVALID_ARGUMENT; }
     if (source && !ar && st[i].input != 0) { *why = "a source stage reads no signal"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((!source || ar) && !have_x) { *why = "stage needs a preceding signal"; return KNH_ERR_INVALID_ARGUMENT; }
@@ -121,7 +126,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
   return KNH_OK;
 }
 
-// The signature of a voice made of SinWt oscillators and arithmetic alone (interp_can_run) -> the program of the
+// The signature of a voice made of SinWt oscillators and arithmetic alone, Math1UGen's functions included (interp_can_run) -> the program of the
 // frame-parallel interpreter (kernels_interp.hip), one op per stage; *n_sigs its signal slots, *out the slot of the voice's
 // output.  False: the signature is malformed.
 bool parse_frame_program(const std::string& signature, const std::vector<StageInfo>& stages, std::vector<knh_dev::InterpOp>* prog, unsigned* n_sigs, unsigned* out) {
@@ -151,6 +156,12 @@ bool parse_frame_program(const std::string& signature, const std::vector<StageIn
       case '*': op.kind = knh_dev::INTERP_MATH_MUL; break;
       case '+': op.kind = knh_dev::INTERP_MATH_ADD; break;
       case '-': op.kind = knh_dev::INTERP_MATH_SUB; break;
+      case 'c': op.kind = knh_dev::INTERP_MATH1_CEIL; break;
+      case 'r': op.kind = knh_dev::INTERP_MATH1_SQRT; break;
+      case 'f': op.kind = knh_dev::INTERP_MATH1_FLOOR; break;
+      case 't': op.kind = knh_dev::INTERP_MATH1_TRUNC; break;
+      case 'w': op.kind = knh_dev::INTERP_MATH1_FRACT; break;
+      case 'e': op.kind = knh_dev::INTERP_MATH1_EXP; break;
       default: op.kind = knh_dev::INTERP_MATH_DIV; break;
     }
     if (!graph) {  // a plain chain: one signal, every stage works on it in place

@@ -8,6 +8,7 @@
 //   J Pan2 (last stage only: two output channels)   I an input channel of the bank node (a source shared by all voices)
 //   + - * / ^  MathUGen of two signals; "@a" / "@a,b" after a stage: the stage(s) whose output it reads, when not the one before it
 //   m x*value   a x+value   s x-value   d x/value   v value-x   q value/x   p x.powf(value)   i x.powi(n)
+//   c x.ceil()   r x.sqrt()   f x.floor()   t x.trunc()   w x.fract()   e x.exp()   (Math1UGen: one operand, no state)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,7 +18,8 @@ namespace knh_dev {
 // One stage of a voice evaluated by the frame-parallel interpreter (kernels_interp.hip): what it computes, the signal
 // slots it reads and writes, and the first of its state words (the stage's slot base).
 enum { INTERP_VAL_MUL = 0, INTERP_VAL_ADD, INTERP_VAL_SUB, INTERP_VAL_DIV, INTERP_VAL_VSUB, INTERP_VAL_VDIV, INTERP_VAL_LAST = INTERP_VAL_VDIV,
-       INTERP_MATH_MUL, INTERP_MATH_ADD, INTERP_MATH_SUB, INTERP_MATH_DIV, INTERP_SIN_WT };
+       INTERP_MATH_MUL, INTERP_MATH_ADD, INTERP_MATH_SUB, INTERP_MATH_DIV, INTERP_SIN_WT,
+       INTERP_MATH1_CEIL, INTERP_MATH1_SQRT, INTERP_MATH1_FLOOR, INTERP_MATH1_TRUNC, INTERP_MATH1_FRACT, INTERP_MATH1_EXP };  // Math1<kind - INTERP_MATH1_CEIL>
 struct InterpOp { u32 kind; unsigned short a, b, o, pad; u32 slot; };  // 16 bytes
 static_assert(sizeof(InterpOp) == 16, "one 16-byte LDS read per stage");
 // Device-side resolution of WrPreciseTiming change queues (kernels_events.hip).  DevRec is the host's 24-byte record of one

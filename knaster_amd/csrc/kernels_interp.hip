@@ -8,7 +8,8 @@
 // a pure function of the frame index --
 //   SinWt (osc.rs:97-168): the phase is a u32 that advances by a constant increment, so frame j of the block reads
 //                          table[((phase0 + j * inc + offset) >> 16) & 16383]: no sample depends on the one before;
-//   x (op) value, a (op) b (math.rs:22-85, wrappers_core/math.rs): element-wise.
+//   x (op) value, a (op) b (math.rs:22-85, wrappers_core/math.rs): element-wise;
+//   op(x) (Math1UGen, math.rs:167-305: ceil sqrt floor trunc fract exp): element-wise, no state.
 // So: one workgroup per voice, a lane per FRAME, and the stages in order, each reading and writing whole rows of signal
 // slots in LDS (the host hands the slots out like registers: bank.hip build_signature).  The operations per sample are the
 // same as in the fused kernel and in the reference, in the same order: results are bit-identical.
@@ -93,6 +94,16 @@ __global__ void __launch_bounds__(1024) voice_interp_kernel(VoiceKernelArgs<F> a
             case INTERP_VAL_DIV: r = x / v; break;
             case INTERP_VAL_VSUB: r = v - x; break;
             default: r = v / x; break;  // INTERP_VAL_VDIV
+          }
+        } else if (kind >= INTERP_MATH1_CEIL) {  // Math1UGen (math.rs:167-305): op(x), the stage the fused kernels run (voice_stages.hpp, Math1)
+          const F x = row[(u32)op.a * n_frames];
+          switch (kind) {
+            case INTERP_MATH1_CEIL: r = Math1Ceil::apply(x); break;
+            case INTERP_MATH1_SQRT: r = Math1Sqrt::apply(x); break;
+            case INTERP_MATH1_FLOOR: r = Math1Floor::apply(x); break;
+            case INTERP_MATH1_TRUNC: r = Math1Trunc::apply(x); break;
+            case INTERP_MATH1_FRACT: r = Math1Fract::apply(x); break;
+            default: r = Math1Exp::apply(x); break;  // INTERP_MATH1_EXP
           }
         } else {
           const F x = row[(u32)op.a * n_frames], y = row[(u32)op.b * n_frames];

@@ -54,8 +54,15 @@ const KindInfo kKinds[KNH_STAGE_KIND_COUNT] = {
     /* MATH_POW    */ {0, 0, 0, 1, '^', {nullptr}},
     /* INPUT       */ {1, 0, 1, 0, 'I', {nullptr}},
     /* GALACTIC    */ {0, 5, 7, 1, 'Q', {"replace", "detune", "brightness", "bigness", "wet"}},  // state and rings: galactic_bank.hpp
+    /* MATH1_CEIL  */ {0, 0, 0, 1, 'c', {nullptr}},  // Math1UGen<F, Op>, math.rs:167-305: one operand, no state, no parameters
+    /* MATH1_SQRT  */ {0, 0, 0, 1, 'r', {nullptr}},
+    /* MATH1_FLOOR */ {0, 0, 0, 1, 'f', {nullptr}},
+    /* MATH1_TRUNC */ {0, 0, 0, 1, 't', {nullptr}},
+    /* MATH1_FRACT */ {0, 0, 0, 1, 'w', {nullptr}},
+    /* MATH1_EXP   */ {0, 0, 0, 1, 'e', {nullptr}},
 };
 inline bool is_math2_kind(uint16_t kind) { return kind >= KNH_STAGE_MATH_ADD && kind <= KNH_STAGE_MATH_POW; }
+inline bool is_math1_kind(uint16_t kind) { return kind >= KNH_STAGE_MATH1_CEIL && kind <= KNH_STAGE_MATH1_EXP; }
 // A voice that is a graph rather than a chain: explicit operands, a MathUGen of two signals, or a second source.
 inline bool signature_is_dag(const std::string& sig) { return sig.find('@') != std::string::npos; }
 
@@ -63,12 +70,14 @@ inline bool is_wrapper_kind(uint16_t kind) {
   return kind == KNH_STAGE_WR_MUL || kind == KNH_STAGE_WR_ADD || kind == KNH_STAGE_WR_SUB || (kind >= KNH_STAGE_WR_VSUB && kind <= KNH_STAGE_WR_POWI);
 }
 // A graph-shaped voice the frame-parallel interpreter can run (kernels_interp.hip): free-running SinWt oscillators and
-// arithmetic only, nothing wrapped in WrPreciseTiming or WrSmoothParams.
+// arithmetic (Math1UGen's single-operand functions included) only, nothing wrapped in WrPreciseTiming or WrSmoothParams.
+const char kFrameSigs[] = "Wmasdvq*+-/crftwe";  // the signature characters of the stage kinds that are pure functions of the frame index
+inline bool frame_eligible(uint16_t kind, uint16_t flags, uint16_t dcpb, uint16_t ar_param) {
+  return flags == 0 && dcpb == 0 && ar_param == 0 && std::strchr(kFrameSigs, kKinds[kind].sig) != nullptr;
+}
 bool interp_can_run(const knh_stage_desc* st, uint32_t n) {
-  for (uint32_t i = 0; i < n; ++i) {
-    if (st[i].flags != 0 || st[i].delayed_changes_per_block != 0 || st[i].ar_param != 0) return false;
-    if (std::strchr("Wmasdvq*+-/", kKinds[st[i].kind].sig) == nullptr) return false;
-  }
+  for (uint32_t i = 0; i < n; ++i)
+    if (!frame_eligible(st[i].kind, st[i].flags, st[i].delayed_changes_per_block, st[i].ar_param)) return false;
   return true;
 }
 
@@ -79,6 +88,7 @@ inline int stage_cost(char c) {
     case 'W': return 7;  case 'R': return 10; case 'N': return 25; case 'S': return 10; case 'L': return 3;
     case 'H': return 4;  case 'A': return 5;  case 'E': return 5;  case 'V': return 14; case 'D': return 12;
     case 'd': case 'q': return 8;  case 'p': return 40; case 'i': return 10; case 'P': return 6; case 'U': return 14; case 'O': return 19; case 'K': return 50; case 'G': return 10; case 'X': return 4; case 'B': return 45; case 'Y': return 14; case 'Z': return 18; case 'F': return 16;
+    case 'r': return 12; case 'e': return 20;  // Math1: the correctly rounded sqrt sequence, the device library's exp (ceil floor trunc fract: 1-2)
     default: return 1;
   }
 }

@@ -447,7 +447,7 @@ struct Bank final : knh_bank {
        // form that takes the reference's 1 531-stage cascade.  KNH_INTERP=0: never (the lane-per-voice form, A/B runs).
       const char* ie = std::getenv("KNH_INTERP");
       bool can = !entry && bs <= 1024 && stages.size() <= 4096;
-      for (const StageInfo& S : stages) can = can && S.flags == 0 && S.dcpb == 0 && S.ar_param == 0 && std::strchr("Wmasdvq*+-/", kKinds[S.kind].sig) != nullptr;
+      for (const StageInfo& S : stages) can = can && frame_eligible(S.kind, S.flags, S.dcpb, S.ar_param);
       if (can && !(ie && ie[0] == '0')) {
         if (!parse_frame_program(signature, stages, &h_prog, &interp_sigs, &interp_out)) return fail(KNH_ERR_UNSUPPORTED_CHAIN, "interpreter: malformed graph signature");
         if (knh::interp_lds_bytes(static_cast<unsigned>(h_prog.size()), static_cast<unsigned>(n_slots), interp_sigs, static_cast<unsigned>(bs), sizeof(F) == 8) <= 158u * 1024u)
@@ -627,6 +627,8 @@ struct Bank final : knh_bank {
             slot(S.slot_base, v) = static_cast<W>(static_cast<uint32_t>(a[0]));
           } break;
           case KNH_STAGE_MATH_ADD: case KNH_STAGE_MATH_SUB: case KNH_STAGE_MATH_MUL: case KNH_STAGE_MATH_DIV: case KNH_STAGE_MATH_POW: break;  // no state
+          case KNH_STAGE_MATH1_CEIL: case KNH_STAGE_MATH1_SQRT: case KNH_STAGE_MATH1_FLOOR: case KNH_STAGE_MATH1_TRUNC: case KNH_STAGE_MATH1_FRACT:
+          case KNH_STAGE_MATH1_EXP: break;  // Math1UGen (math.rs:167-305): no constructor arguments, no state
           case KNH_STAGE_WHITE_NOISE: case KNH_STAGE_PINK_NOISE: case KNH_STAGE_BROWN_NOISE: {
             // fastrand::Rng::with_seed(next_randomness_seed()) (noise.rs:34,66,134): the state is the seed
             const uint64_t seed = a[0] >= 0.0 ? static_cast<uint64_t>(a[0]) : 0u;
@@ -868,6 +870,10 @@ struct Bank final : knh_bank {
 
   // ---- parameter changes ----------------------------------------------------------------
   int check_target(uint32_t voice, uint32_t stage, uint32_t param) {
+    // a Math1UGen has no parameters at all (math.rs:167-305): a call that names one is a mistake about the stage, not an index a
+    // little too large -- every parameter entry point comes through here (or through RankBank's copy of these checks).  Ahead of
+    // the initialised check on purpose: the chain is known from knh_bank_create on (knaster_hip.h says so)
+    if (stage < stages.size() && is_math1_kind(stages[stage].kind)) return fail(KNH_ERR_INVALID_ARGUMENT, "a KNH_STAGE_MATH1_* stage has no parameters");
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (voice >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
     if (stage >= stages.size()) return fail(KNH_ERR_OUT_OF_RANGE, "stage out of range");
@@ -1905,6 +1911,10 @@ struct Bank final : knh_bank {
     KNH_HIP(hipSetDevice(device));
     KNH_HIP(hipDeviceSynchronize());
     KNH_HIP(hipMemcpy(out16, flags_last ? flags_last : d_flags, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    // word 2 (no kernel writes it): the kernel form the bank's launches take, in the order launch_interp / launch_voice decide it
+    out16[2] = interp ? (frame_jit ? KNH_DEBUG_FORM_FRAME_JIT : KNH_DEBUG_FORM_FRAME_INTERP)
+             : jit ? (jit_pipe ? KNH_DEBUG_FORM_PIPELINE_FUSED : KNH_DEBUG_FORM_WHOLE_CHAIN_FUSED)
+             : wide_waves != 0 ? KNH_DEBUG_FORM_MANY_WAVE : pipe ? KNH_DEBUG_FORM_PIPELINE : KNH_DEBUG_FORM_WHOLE_CHAIN;
     return KNH_OK;
   }
   int synchronize() override {

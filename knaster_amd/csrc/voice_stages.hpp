@@ -493,6 +493,58 @@ struct SafetyLimiter : StageDefaults {
   template <typename F> static __device__ __forceinline__ void on_event(Regs<F>&, u32, u32, u64, u32) {}
 };
 
+// Math1UGen<F, Op> -- math.rs:167-305: out = op(in), the six single-operand nodes of the prelude (math_ugens.rs), with
+// what Rust's std does for F (num_traits::Float forwards to it).  No state, no parameters.
+//   OP 0 ceil, 2 floor, 3 trunc: IEEE round-to-integral, one instruction each: the sign of zero is kept, inf and NaN pass;
+//   OP 1 sqrt: the builtin, which both build paths (hipcc, hiprtc) lower to the correctly rounded sequence -- subnormal
+//        inputs included -- because neither is given a fast-math or an approximate-sqrt flag; sqrt(-0.0) = -0.0;
+//   OP 4 fract: x - trunc(x) as Rust spells it (f32::fract), NOT x - floor(x), which is what v_fract_f32 / v_fract_f64
+//        compute: fract(-1.25) = -0.25, fract(-0.0) = +0.0, fract(+-inf) = NaN;
+//   OP 5 exp: the device library's exp (tolerance only, like powf and SinNumeric's sine).
+// (the numbering is the reference's declaration order, as KNH_STAGE_MATH1_* - KNH_STAGE_MATH1_CEIL)
+template <int OP>
+struct Math1 : StageDefaults {
+  static constexpr int kSlots = 0;
+  static constexpr u32 kMutableMask = 0u;
+  static constexpr bool kUsesSine = false;
+  static constexpr bool kIsEnv = false;
+  static constexpr bool kNeedsBind = false;
+  static constexpr bool kHasSeg = false;
+  template <typename F> struct Regs {};
+  template <typename F, typename W> static __device__ __forceinline__ void load(Regs<F>&, const W*, long) {}
+  template <typename F, typename W> static __device__ __forceinline__ void store(const Regs<F>&, W*, long) {}
+  static __device__ __forceinline__ float apply(float x) {
+    if (OP == 0) return __builtin_ceilf(x);
+    if (OP == 1) return __builtin_sqrtf(x);
+    if (OP == 2) return __builtin_floorf(x);
+    if (OP == 3) return __builtin_truncf(x);
+    if (OP == 4) return x - __builtin_truncf(x);
+    return __ocml_exp_f32(x);
+  }
+  static __device__ __forceinline__ double apply(double x) {
+    if (OP == 0) return __builtin_ceil(x);
+    if (OP == 1) return __builtin_sqrt(x);
+    if (OP == 2) return __builtin_floor(x);
+    if (OP == 3) return __builtin_trunc(x);
+    if (OP == 4) return x - __builtin_trunc(x);
+    return __ocml_exp_f64(x);
+  }
+  template <typename F, bool FMA>
+  static __device__ __forceinline__ F tick(Regs<F>&, F x, const Ctx&, u32, u32&) { return apply(x); }
+  template <typename F, bool FMA, int T>
+  static __device__ __forceinline__ void tick_tile(Regs<F>&, F (&x)[T], const Ctx&, u32, u32&) {
+#pragma unroll
+    for (int j = 0; j < T; ++j) x[j] = apply(x[j]);
+  }
+  template <typename F> static __device__ __forceinline__ void on_event(Regs<F>&, u32, u32, u64, u32) {}
+};
+typedef Math1<0> Math1Ceil;
+typedef Math1<1> Math1Sqrt;
+typedef Math1<2> Math1Floor;
+typedef Math1<3> Math1Trunc;
+typedef Math1<4> Math1Fract;
+typedef Math1<5> Math1Exp;
+
 // PolyBlep -- polyblep.rs:123-508: fourteen waveforms with polynomial band-limiting of their steps (blep) and corners
 // (blamp).  Every waveform is + - * / and comparisons in the reference's order, except the four that call sin
 // (Sine, Cosine, Half/FullWaveRectifiedSine, and every waveform above sample_rate / 4): device libm, tolerance only.

@@ -122,6 +122,15 @@ inline UGenSpec SinNumeric(double freq) { return UGenSpec(KNH_STAGE_SIN_NUMERIC,
 inline UGenSpec PolyBlep(int waveform, double freq) { return UGenSpec(KNH_STAGE_POLYBLEP, {static_cast<double>(waveform), freq}); }
 inline UGenSpec Phasor(double freq) { return UGenSpec(KNH_STAGE_PHASOR, {freq}); }        // osc.rs:172-214
 inline UGenSpec SafetyLimiter() { return UGenSpec(KNH_STAGE_SAFETY_LIMITER, {}); }        // dynamics.rs:9-31
+// The Math1UGen factories of knaster/src/math_ugens.rs, under the reference's names: `x >> g.push(sqrt())`.  They take no
+// arguments, so they overload beside <cmath>'s functions of one argument instead of colliding with them (`knaster::sqrt()`
+// against `sqrt(2.0)`); inside this namespace the library functions are spelled std::.
+inline UGenSpec fract() { return UGenSpec(KNH_STAGE_MATH1_FRACT, {}); }  // math.rs:167-305: Math1UGen<F, Op>, one input, no parameters
+inline UGenSpec ceil() { return UGenSpec(KNH_STAGE_MATH1_CEIL, {}); }
+inline UGenSpec exp() { return UGenSpec(KNH_STAGE_MATH1_EXP, {}); }
+inline UGenSpec trunc() { return UGenSpec(KNH_STAGE_MATH1_TRUNC, {}); }
+inline UGenSpec floor() { return UGenSpec(KNH_STAGE_MATH1_FLOOR, {}); }
+inline UGenSpec sqrt() { return UGenSpec(KNH_STAGE_MATH1_SQRT, {}); }
 // Pan2::new(pan) -- pan.rs:18-23: one input, two outputs; `(voice >> pan).to_graph_out()` sends them to graph outputs 0 and 1
 inline UGenSpec Pan2(double pan) { UGenSpec s(KNH_STAGE_PAN2, {pan}); s.outputs = 2; return s; }
 // noise.rs:11-22: every randomness UGen takes its seed from one process-wide counter, in construction order, so a
@@ -303,6 +312,8 @@ inline const char* const* stage_param_names(uint16_t kind, int* n) {
     case KNH_STAGE_PAN2: { static const char* pan[] = {"pan"}; *n = 1; return pan; }
     case KNH_STAGE_POLYBLEP: { static const char* pb[] = {"freq", "pulse_width", "waveform"}; *n = 3; return pb; }
     case KNH_STAGE_SAFETY_LIMITER: case KNH_STAGE_WHITE_NOISE: case KNH_STAGE_PINK_NOISE: case KNH_STAGE_BROWN_NOISE: *n = 0; return frq;
+    case KNH_STAGE_MATH1_CEIL: case KNH_STAGE_MATH1_SQRT: case KNH_STAGE_MATH1_FLOOR: case KNH_STAGE_MATH1_TRUNC: case KNH_STAGE_MATH1_FRACT:
+    case KNH_STAGE_MATH1_EXP: *n = 0; return frq;
     case KNH_STAGE_SAMPLE_DELAY: case KNH_STAGE_ALLPASS_DELAY: *n = 1; return dly;
     case KNH_STAGE_ALLPASS_FB_DELAY: { static const char* fbd[] = {"delay_time", "feedback"}; *n = 2; return fbd; }
     case KNH_STAGE_MUL_ENVELOPE: *n = 4; return seg;
