@@ -35,6 +35,9 @@ struct Chain<F, FMA, BASE> {
   template <typename W> __device__ __forceinline__ void store(W*, long) const {}
   __device__ __forceinline__ F tick(F x, const Ctx&, u32) { return x; }
   template <int T> __device__ __forceinline__ void tick_tile(F (&)[T], const Ctx&, u32) {}
+  struct RunPrep {};
+  __device__ __forceinline__ RunPrep prepare_run() const { return RunPrep(); }
+  template <int T> __device__ __forceinline__ void tick_tile_run(F (&)[T], const Ctx&, u32, const RunPrep&) {}
 #ifdef KNH_DAG_STAMPS
   template <int T> __device__ __forceinline__ void tick_tile_stamped(F (&)[T], const Ctx&, u32, u64*, u64&) {}
 #endif
@@ -79,6 +82,21 @@ struct Chain<F, FMA, BASE, S0, Rest...> {
   template <int T> __device__ __forceinline__ void tick_tile(F (&x)[T], const Ctx& c, u32 frame0) {
     S0::template tick_tile<F, FMA, T>(r, x, c, frame0, mark);
     rest.template tick_tile<T>(x, c, frame0);
+  }
+  // The tiles of a quiet run (voice_pipe.hpp): what a stage decides per tile from state that only an event or a load can
+  // change (StageDefaults::kHasRunPrep) is decided once, in front of the run, and every tile of the run is given it.
+  struct RunPrep { bool mine; typename RestT::RunPrep rest; };
+  __device__ __forceinline__ RunPrep prepare_run() const {
+    RunPrep p;
+    if constexpr (S0::kHasRunPrep) p.mine = S0::template prepare_run<F>(r);
+    else p.mine = false;
+    p.rest = rest.prepare_run();
+    return p;
+  }
+  template <int T> __device__ __forceinline__ void tick_tile_run(F (&x)[T], const Ctx& c, u32 frame0, const RunPrep& p) {
+    if constexpr (S0::kHasRunPrep) S0::template tick_tile_prepared<F, FMA, T>(r, x, c, frame0, mark, p.mine);
+    else S0::template tick_tile<F, FMA, T>(r, x, c, frame0, mark);
+    rest.template tick_tile_run<T>(x, c, frame0, p.rest);
   }
 #ifdef KNH_DAG_STAMPS  // diagnostic build only: the same walk with the clock read behind every stage (tools/wide_stamps.py)
   template <int T> __device__ __forceinline__ void tick_tile_stamped(F (&x)[T], const Ctx& c, u32 frame0, u64* acc, u64& t_prev) {

@@ -88,6 +88,15 @@ template <int MODE, int NG> struct EdgeMap {
   }
   static __device__ __forceinline__ int in_tile(int I, int g) { return I > 0 ? out_tile(I - 1, g) : 0; }
   static __device__ __forceinline__ int mixer_tile(int g) { return out_tile(NG - 1, g); }
+  // ... and, given the buffer of its tile g, that of its tile g + 1: the loops carry the buffer from tile to tile with these (a
+  // flipped bit -- I * 2 is even -- or a count that wraps at three) instead of dividing g
+  static __device__ __forceinline__ int next_out(int I, int t) {
+    if (MODE == PIPE_FOLD && I == NG - 1) return t;
+    if (MODE == PIPE_INPLACE && I >= NG - 2) return t == (NG - 2) * 2 + 2 ? (NG - 2) * 2 : t + 1;
+    return t ^ 1;
+  }
+  static __device__ __forceinline__ int next_in(int I, int t) { return I > 0 ? next_out(I - 1, t) : 0; }
+  static __device__ __forceinline__ int next_mixer(int t) { return next_out(NG - 1, t); }
 };
 // The pipeline's step barrier.  Its wavefronts run different code (one role each) and reach the barrier from different call
 // sites; what is relied on is the HARDWARE barrier of gfx950 -- s_barrier counts the wavefronts of the workgroup that have
@@ -250,67 +259,81 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
   take_next();
   base = 0;
 
-  // The pipeline runs continuously over all blocks of the launch: global tile g = (block, tile in block).
+  // The pipeline runs continuously over all blocks of the launch: global tile g = (block, tile in block).  Group I is I steps
+  // behind group 0: it waits I steps while the pipeline fills, takes its n_tiles tiles, one per step, and waits out the rest
+  // while the pipeline drains.
+  // EVERY WAVEFRONT OF THE WORKGROUP ARRIVES AT EXACTLY n_steps STEP BARRIERS PER CALL.  Here that is: I in the loop in front,
+  // one per tile -- a tile of a quiet run meets its barrier inside the run, except the run's last tile when the run ends with
+  // the supply of whole tiles, whose barrier (like that of every tile of the general paths) is the one at the end of the tile
+  // loop, `step_open` saying which -- and n_steps - I - n_tiles in the loop behind.  A Fan group's wavefronts each make the
+  // same steps (their tiles are windows of the same tiles); a folding group (PIPE_FOLD) folds inside its step; the mixer
+  // (pipe_run_mixer) and the dead group of the two-group form (voice_pipe_kernel) count the same n_steps.
   const u32 n_frames = fend - fbeg;
   const int tpb = (int)((n_frames + T - 1) / T);           // tiles per block
   const int n_tiles = tpb * (int)a.n_blocks;
   const int n_steps = n_tiles + NG - (MODE == PIPE_FOLD ? 1 : 0);
   const u32 n_waves_total = (a.n_voices + 63u) / 64u;
-  int blk = 0, ti = 0;                                      // position of this group's next tile
+  // the first `full` tiles of a block are those this wavefront's window lies wholly inside (m == TW below)
+  const int full = n_frames >= fo + (u32)TW ? (int)((n_frames - fo - (u32)TW) / (u32)T) + 1 : 0;
+  // the buffers of this group's next tile, carried from tile to tile (EdgeMap::next_*) instead of worked out from g
+  int in_t = Map::in_tile(I, 0), out_t = Map::out_tile(I, 0);
 #ifdef KNH_DAG_STAMPS  // diagnostic build only: cycles this wavefront is busy per tile (tools/pipe_stamps.py)
   u64 busy = 0, busy_in = 0, busy_out = 0, busy_tick = 0, busy_fold = 0;
 #endif
-  for (int s = 0; s < n_steps; ++s) {
-    const int g = s - I;
-    if (g >= 0 && g < n_tiles) {
+  for (int s = 0; s < I; ++s) pipe_barrier();
+  for (int blk = 0, ti = 0; blk < (tpb > 0 ? (int)a.n_blocks : 0); ++blk) {
+    ctx.input_block = reinterpret_cast<const F*>(a.input) + (long)blk * a.in_channels * a.block_size;
+    chain.begin_block(fbeg, ctx);
+    for (ti = 0;;) {  // the block's tiles; left at the block's end
+      typedef typename EdgeLayout<F, T>::Vec Vec;
+      constexpr int VW = EdgeLayout<F, T>::VW;
 #ifdef KNH_DAG_STAMPS
       const u64 t0 = __builtin_amdgcn_s_memtime();
 #endif
-      // the tile's LDS reads go out first, so that their latency runs under the block/event bookkeeping below
-      F x[TW];
-      if (I > 0) {
-        typedef typename EdgeLayout<F, T>::Vec Vec;
-        constexpr int VW = EdgeLayout<F, T>::VW;
-        const Vec* in = reinterpret_cast<const Vec*>(sh.edge + (long)Map::in_tile(I, g) * EdgeLayout<F, T>::tile +
-                                                     (long)lane * EdgeLayout<F, T>::stride + fo);
-#pragma unroll
-        for (int j = 0; j < TW / VW; ++j) {
-          const Vec v = in[j];
-#pragma unroll
-          for (int k = 0; k < VW; ++k) x[j * VW + k] = v[k];
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < TW; ++j) x[j] = (F)0;
-      }
-      if (ti == 0) {
-        ctx.input_block = reinterpret_cast<const F*>(a.input) + (long)blk * a.in_channels * a.block_size;
-        chain.begin_block(fbeg, ctx);
-      }
       const u32 n_tile = fbeg + (u32)ti * T;
-      const u32 m_tile = fend - n_tile < (u32)T ? fend - n_tile : (u32)T;
       const u32 n = n_tile + fo;                                                            // the window's first frame
-      const u32 m = m_tile > fo ? (m_tile - fo < (u32)TW ? m_tile - fo : (u32)TW) : 0u;     // frames of it inside the block
       apply_events_upto(base + n);  // (a Fan wavefront: also the changes inside the part of the tile before its window)
       const bool ev_inside = next_frame < base + n + TW;
+      bool step_open = true;  // this step's barrier is still to come
+      if (__builtin_expect(ti < full && !__builtin_amdgcn_ballot_w64(ev_inside), 1)) {  // (the cold paths out of line: one instruction cache for all roles)
+        // A QUIET RUN: consecutive tiles of this block that are whole and have no event of any lane inside them.  No event is
+        // applied between them, so what the stages choose per tile from their parameters is chosen once (Chain::prepare_run),
+        // and a tile is nothing but: its LDS reads, the stages, its LDS stores, the step barrier, the advance.  This is the only
+        // place the fast tile body exists, a run of one tile included.
+        const typename ChainT::RunPrep prep = chain.prepare_run();
+        u32 nq = n;
+        for (;;) {
+#ifdef KNH_DAG_STAMPS
+          const u64 q0 = __builtin_amdgcn_s_memtime();
+#endif
+          F x[TW];
+          if (I > 0) {
+            const Vec* in = reinterpret_cast<const Vec*>(sh.edge + (long)in_t * EdgeLayout<F, T>::tile + (long)lane * EdgeLayout<F, T>::stride + fo);
+#pragma unroll
+            for (int j = 0; j < TW / VW; ++j) {
+              const Vec v = in[j];
+#pragma unroll
+              for (int k = 0; k < VW; ++k) x[j * VW + k] = v[k];
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < TW; ++j) x[j] = (F)0;
+          }
 #if defined(KNH_DAG_STAMPS) || defined(KNH_TILE_FENCES)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
 #ifdef KNH_DAG_STAMPS
-      const u64 t1 = __builtin_amdgcn_s_memtime();
-      busy_in += t1 - t0;
+          const u64 q1 = __builtin_amdgcn_s_memtime();
+          busy_in += q1 - q0;
 #endif
-      {  // every group, the last one included, hands its tile on as 64 rows of T samples
-        typedef typename EdgeLayout<F, T>::Vec Vec;
-        constexpr int VW = EdgeLayout<F, T>::VW;
-        F* out_tile = sh.edge + (long)Map::out_tile(I, g) * EdgeLayout<F, T>::tile;
-        F* out_row = out_tile + (long)lane * EdgeLayout<F, T>::stride + fo;
-        if (__builtin_expect(m == (u32)TW && !__builtin_amdgcn_ballot_w64(ev_inside), 1)) {  // (the cold paths out of line: one instruction cache for all roles)
-          chain.template tick_tile<TW>(x, ctx, n);
+          chain.template tick_tile_run<TW>(x, ctx, nq, prep);
 #ifdef KNH_DAG_STAMPS
           asm volatile("" ::: "memory");
-          busy_tick += __builtin_amdgcn_s_memtime() - t1;
+          const u64 q2 = __builtin_amdgcn_s_memtime();
+          busy_tick += q2 - q1;
 #endif
+          F* const out_tile = sh.edge + (long)out_t * EdgeLayout<F, T>::tile;
+          F* const out_row = out_tile + (long)lane * EdgeLayout<F, T>::stride + fo;
           Vec* out = reinterpret_cast<Vec*>(out_row);  // 16-byte LDS stores
 #pragma unroll
           for (int j = 0; j < TW / VW; ++j) {
@@ -319,10 +342,49 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
             for (int k = 0; k < VW; ++k) v[k] = x[j * VW + k];
             out[j] = v;
           }
+          if constexpr (GroupInfo<G>::pan) {  // (as below)
+            F gl = (F)0, gr = (F)0;
+            chain.pan_gains(gl, gr);
+            out_row[T] = gl;
+            out_row[T + 1] = gr;
+          }
+#ifdef KNH_DAG_STAMPS
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          const u64 qf = __builtin_amdgcn_s_memtime();
+#endif
+          if constexpr (FOLDS) pipe_fold_tile<F, FMA, T, GroupInfo<G>::pan>(out_tile, a, lane, wave_global, n_waves_total, blk, nq, (u32)T, v0, nv);  // (fo == 0)
+#ifdef KNH_DAG_STAMPS
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          const u64 qe = __builtin_amdgcn_s_memtime();
+          busy_fold += qe - qf;
+#endif
+          in_t = Map::next_in(I, in_t);
+          out_t = Map::next_out(I, out_t);
+          nq += (u32)T;
+          ++ti;
+#if defined(KNH_DAG_STAMPS) || defined(KNH_TILE_FENCES)
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#endif
+#ifdef KNH_DAG_STAMPS
+          const u64 q3 = __builtin_amdgcn_s_memtime();
+          busy_out += q3 - qe;
+          busy += q3 - q0;
+#endif
+          if (ti >= full) break;  // no whole tile left in the block: the step's barrier is the tile loop's
+          pipe_barrier();
+          if (__builtin_amdgcn_ballot_w64(next_frame < base + nq + TW)) { step_open = false; break; }
+        }
+      } else {
+        const u32 m_tile = fend - n_tile < (u32)T ? fend - n_tile : (u32)T;
+        const u32 m = m_tile > fo ? (m_tile - fo < (u32)TW ? m_tile - fo : (u32)TW) : 0u;     // frames of the window inside the block
+        // every group, the last one included, hands its tile on as 64 rows of T samples
+        F* const out_tile = sh.edge + (long)out_t * EdgeLayout<F, T>::tile;
+        F* const out_row = out_tile + (long)lane * EdgeLayout<F, T>::stride + fo;
+        const F* const in_row = sh.edge + (long)in_t * EdgeLayout<F, T>::tile + (long)lane * EdgeLayout<F, T>::stride + fo;
 #ifdef KNH_AB_NO_SW
-        } else if (false && [&]() -> bool {
+        if (false && [&]() -> bool {
 #else
-        } else if (m == (u32)TW && ChainT::kParamBits != 0ull && !ChainT::kBinds && [&]() -> bool {
+        if (m == (u32)TW && ChainT::kParamBits != 0ull && !ChainT::kBinds && [&]() -> bool {
 #endif
           // (groups that hold a delay line, a segment table or a buffer reader keep to the general path: their registers --
           // a prefetched tile of the ring among them -- are not worth copying for this)
@@ -364,7 +426,6 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
           }
           // eight samples at a time, row to row in LDS (a run-time loop, like the general path: keeps this rare path small
           // and the register tile of the fast path out of it)
-          const F* in_row = sh.edge + (long)Map::in_tile(I, g) * EdgeLayout<F, T>::tile + (long)lane * EdgeLayout<F, T>::stride + fo;
           for (u32 j0 = 0; j0 < (u32)TW; j0 += 8u) {
             F sub[8];
             if (I > 0) {
@@ -392,9 +453,8 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
         } else {
           // Some voice of the wave has a change inside this tile (sample-accurate parameter changes, WrPreciseTiming), or
           // the tile is a partial one at the end of a block: it is walked eight samples at a time, row to row in LDS (a
-          // run-time loop: the register tile above is never indexed by a run-time value, which would put all of it, the
-          // fast path's too, in scratch memory), sample by sample with the changes applied in front of their frame.
-          const F* in_row = sh.edge + (long)Map::in_tile(I, g) * EdgeLayout<F, T>::tile + (long)lane * EdgeLayout<F, T>::stride + fo;
+          // run-time loop: a register tile indexed by a run-time value would sit in scratch memory), sample by sample with
+          // the changes applied in front of their frame.
           for (u32 j0 = 0; j0 < m; j0 += 8u) {
             const u32 cnt = m - j0 < 8u ? m - j0 : 8u;
             F sub[8];
@@ -437,38 +497,33 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
         const u64 tf0 = __builtin_amdgcn_s_memtime();
 #endif
         if constexpr (FOLDS) pipe_fold_tile<F, FMA, T, GroupInfo<G>::pan>(out_tile, a, lane, wave_global, n_waves_total, blk, n_tile, m_tile, v0, nv);
+        in_t = Map::next_in(I, in_t);
+        out_t = Map::next_out(I, out_t);
+        ++ti;
 #ifdef KNH_DAG_STAMPS
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        busy_fold += __builtin_amdgcn_s_memtime() - tf0;
+        const u64 t3 = __builtin_amdgcn_s_memtime();
+        busy_fold += t3 - tf0;
+        busy += t3 - t0;
 #endif
       }
-#if defined(KNH_DAG_STAMPS) || defined(KNH_TILE_FENCES)
-      asm volatile("" ::: "memory");
-#endif
-#ifdef KNH_DAG_STAMPS
-      const u64 t2 = __builtin_amdgcn_s_memtime();
-#endif
-      if (++ti == tpb) {  // block finished for this group
+      if (ti == tpb) {  // block finished for this group
         apply_events_upto(base + fend);  // changes due exactly at the end (precise_timing.rs:85-103)
-        ti = 0;
-        ++blk;
         base += a.block_size;
         if (resident) {  // what the mixer wavefront reports for this call (it folds this tile one or more steps from now)
           sh.res_marks[wave_all * 64 + lane] = chain.collect_done(0xFFFFFFFFu);
           if (GroupInfo<G>::has_env && I == LAST_ENV) sh.res_marks[15 * 64 + lane] = live && !chain.last_env_stopped(false) ? 1u : 0u;
         }
-      }
 #if defined(KNH_DAG_STAMPS) || defined(KNH_TILE_FENCES)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
-#ifdef KNH_DAG_STAMPS
-      const u64 t3 = __builtin_amdgcn_s_memtime();
-      busy += t3 - t0;
-      busy_out += t3 - t2;
-#endif
+        pipe_barrier();
+        break;
+      }
+      if (step_open) pipe_barrier();
     }
-    pipe_barrier();
   }
+  for (int s = I + n_tiles; s < n_steps; ++s) pipe_barrier();
 #ifdef KNH_DAG_STAMPS
   if (wave_global == 0u && lane == 0) {
     const u64 d = (u64)(n_tiles > 0 ? n_tiles : 1);
@@ -555,20 +610,27 @@ __device__ __forceinline__ void pipe_run_mixer(const PipeShared<F>& sh, const Vo
   const u32 n_frames = fend - fbeg;
   const int tpb = (int)((n_frames + T - 1) / T);
   const int n_tiles = tpb * (int)a.n_blocks;
-  const int n_steps = n_tiles + NG;
-  int blk = 0, ti = 0;
 #ifdef KNH_DAG_STAMPS
   u64 busy = 0;
 #endif
-  for (int s = 0; s < n_steps; ++s) {
-    const int g = s - NG;  // the tile the last chain group finished in the previous step
-    if (g >= 0 && g < n_tiles) {
+  // (a resident launch: the mixer's granules are write-through stores nobody in the workgroup waits for; the step barrier only
+  // has to order its LDS reads -- the workgroup-scope release of pipe_barrier would also wait for those stores to be acknowledged)
+  auto step_barrier = [&]() {
+    if (resident) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    else pipe_barrier();
+  };
+  // The mixer is NG steps behind group 0: NG steps of waiting while the pipeline fills, then the launch's tiles block by block,
+  // one per step -- fold, advance, barrier: n_tiles + NG = n_steps barriers, the stage groups' count (pipe_run_group).
+  for (int s = 0; s < NG; ++s) step_barrier();
+  int mix_t = EdgeMap<MODE, NG>::mixer_tile(0);  // the buffer of the next tile, carried from tile to tile
+  int g = 0;                                      // the tile the last chain group finished in the previous step
+  for (int blk = 0; blk < (tpb > 0 ? (int)a.n_blocks : 0); ++blk) {
+    for (u32 rel = 0; rel < n_frames; rel += (u32)T) {
 #ifdef KNH_DAG_STAMPS
       const u64 t0 = __builtin_amdgcn_s_memtime();
 #endif
-      const u32 rel = (u32)ti * T;
       const u32 len = n_frames - rel < (u32)T ? n_frames - rel : (u32)T;
-      const F* tile = sh.edge + (long)EdgeMap<MODE, NG>::mixer_tile(g) * EdgeLayout<F, T>::tile;
+      const F* tile = sh.edge + (long)mix_t * EdgeLayout<F, T>::tile;
       pipe_fold_tile<F, FMA, T, PAN>(tile, a, lane, wave_global, n_waves_total, blk, fbeg + rel, len, v0, nv, (u32)g, call.epoch);
       if (resident && g == n_tiles - 1) {
         // the call's last tile: every stage group is through with the call (its marks are in LDS since its last step's
@@ -585,16 +647,14 @@ __device__ __forceinline__ void pipe_run_mixer(const PipeShared<F>& sh, const Vo
         }
         if (lane == 0) res_put(a.res.wg_flags + wave_global, n_done | (n_run << 8), res_tag(call.epoch, 255u));
       }
-      if (++ti == tpb) { ti = 0; ++blk; }
+      mix_t = EdgeMap<MODE, NG>::next_mixer(mix_t);
+      ++g;
 #ifdef KNH_DAG_STAMPS
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       busy += __builtin_amdgcn_s_memtime() - t0;
 #endif
+      step_barrier();
     }
-    // (a resident launch: the mixer's granules are write-through stores nobody in the workgroup waits for; the step barrier only
-    // has to order its LDS reads -- the workgroup-scope release of pipe_barrier would also wait for those stores to be acknowledged)
-    if (resident) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else pipe_barrier();
   }
 #ifdef KNH_DAG_STAMPS
   if (wave_global == 0u && lane == 0) a.flags[4 + NG] = (u32)(busy / (u64)(n_tiles > 0 ? n_tiles : 1));

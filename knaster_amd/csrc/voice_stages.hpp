@@ -76,6 +76,10 @@ struct StageDefaults {
   // (WrArParams, audio_rate.rs:11-85: every sample `param_apply(p, buf[i])`, then one sample of the node): ArP<S, P> below
   static constexpr int kArParam = -1;
   static constexpr bool kUsesRing = false;  // a delay: the stage moves tiles of a per-voice ring in HBM (RingLines)
+  // A stage that chooses between forms of its tile code by something only an event or a load can change says so here: the
+  // pipeline evaluates prepare_run once per quiet run of tiles (voice_pipe.hpp: consecutive tiles with no event applied
+  // between them) and hands the result to tick_tile_prepared for each tile of the run.  Only Svf has one.
+  static constexpr bool kHasRunPrep = false;
 };
 // A stage whose parameter P is driven at audio rate by another signal of the voice (graph-shaped voices: DagChain reads the
 // driver through the stage's second operand and calls S::ar_set<F, P> in front of every sample).  What the setter of each
@@ -1076,7 +1080,14 @@ struct Svf : StageDefaults {
       x[j] = y0; x[j + 1] = y1; x[j + 2] = y2; x[j + 3] = y3; x[j + 4] = y4; x[j + 5] = y5; x[j + 6] = y6; x[j + 7] = y7;
     }
 #undef KNH_SVF_STEP
-    r.ic1 = ic1; r.ic2 = ic2;
+    // The state leaves the fixed registers inside an asm statement, into registers of the compiler's choice.  Left to the
+    // compiler (r.ic1 = ic1; r.ic2 = ic2), the copy out of v101 went missing where a loop carries the state from tile to tile
+    // (the pipeline's quiet runs, a filter group with a stage in front of the filter: ic2 then never advanced from tile to
+    // tile).  The guards against its coming back with another compiler: tests/test_gpu_parity.py::test_noise_sources and
+    // tests/test_gpu_pipe_quiet_runs.py::test_a_filter_behind_a_gain_in_its_group, chains cut into Group<MulVal, Svf>.
+    float o1, o2;
+    asm volatile("v_mov_b32 %0, v100\n\tv_mov_b32 %1, v101" : "=&v"(o1), "=&v"(o2) : "{v100}"(ic1), "{v101}"(ic2));
+    r.ic1 = o1; r.ic2 = o2;
   }
   // The low-pass output (svf.rs:148-157: m0 = 0, m1 = 0, m2 = 1) without its three multiplies and two adds, bit for bit:
   //   (0*x + 0*v1) + 1*v2 = z + v2 with z = +-0 while x and v1 are finite, and z + v2 = v2 unless v2 = -0;
@@ -1130,7 +1141,14 @@ struct Svf : StageDefaults {
       x[j] = y0; x[j + 1] = y1; x[j + 2] = y2; x[j + 3] = y3; x[j + 4] = y4; x[j + 5] = y5; x[j + 6] = y6; x[j + 7] = y7;
     }
 #undef KNH_SVF_LOW
-    r.ic1 = ic1; r.ic2 = ic2;
+    // The state leaves the fixed registers inside an asm statement, into registers of the compiler's choice.  Left to the
+    // compiler (r.ic1 = ic1; r.ic2 = ic2), the copy out of v101 went missing where a loop carries the state from tile to tile
+    // (the pipeline's quiet runs, a filter group with a stage in front of the filter: ic2 then never advanced from tile to
+    // tile).  The guards against its coming back with another compiler: tests/test_gpu_parity.py::test_noise_sources and
+    // tests/test_gpu_pipe_quiet_runs.py::test_a_filter_behind_a_gain_in_its_group, chains cut into Group<MulVal, Svf>.
+    float o1, o2;
+    asm volatile("v_mov_b32 %0, v100\n\tv_mov_b32 %1, v101" : "=&v"(o1), "=&v"(o2) : "{v100}"(ic1), "{v101}"(ic2));
+    r.ic1 = o1; r.ic2 = o2;
   }
   // the same in f64: eleven instructions for the general step's fifteen, every operand at least two instructions old
   template <int T>
@@ -1200,16 +1218,26 @@ struct Svf : StageDefaults {
 #undef KNH_STEP
     r.ic1 = ic1; r.ic2 = ic2;
   }
+  // The choice of the step holds for a whole quiet run of tiles (voice_pipe.hpp), not only for one tile: nl changes with an
+  // event only, and no step -- the low-pass one or the general one -- ever leaves ic2 = -0 behind (above), so `low` stays
+  // true from tile to tile; a run that starts with ic2 = -0 (right after a load or a SET) evaluates false and takes the
+  // general step, which is right for any state, until the run ends.
+  static constexpr bool kHasRunPrep = true;
+  template <typename F> static __device__ __forceinline__ bool prepare_run(const Regs<F>& r) { return low_pass(r); }
   template <typename F, bool FMA, int T>
-  static __device__ __forceinline__ void tick_tile(Regs<F>& r, F (&x)[T], const Ctx& c, u32 frame0, u32& done_frame) {
+  static __device__ __forceinline__ void tick_tile_prepared(Regs<F>& r, F (&x)[T], const Ctx& c, u32 frame0, u32& done_frame, bool low) {
     if constexpr (sizeof(F) == 4 && !FMA) {
-      if (low_pass(r)) tick_tile_low<T>(r, x); else tick_tile_packed<T>(r, x);
+      if (low) tick_tile_low<T>(r, x); else tick_tile_packed<T>(r, x);
     } else if constexpr (sizeof(F) == 8 && !FMA) {
-      if (low_pass(r)) tick_tile_low_f64<T>(r, x); else tick_tile_f64<T>(r, x);
+      if (low) tick_tile_low_f64<T>(r, x); else tick_tile_f64<T>(r, x);
     } else {
 #pragma unroll
       for (int j = 0; j < T; ++j) x[j] = tick<F, FMA>(r, x[j], c, frame0 + j, done_frame);
     }
+  }
+  template <typename F, bool FMA, int T>
+  static __device__ __forceinline__ void tick_tile(Regs<F>& r, F (&x)[T], const Ctx& c, u32 frame0, u32& done_frame) {
+    tick_tile_prepared<F, FMA, T>(r, x, c, frame0, done_frame, low_pass(r));
   }
   template <typename F>
   static __device__ __forceinline__ void on_event(Regs<F>& r, u32 op, u32 rel, u64 bits, u32 /*frame*/) {
@@ -1233,6 +1261,7 @@ static __device__ __forceinline__ double dev_pow(double a, double b) { return __
 struct SvfP : Svf {
   static constexpr int kSlots = 12;
   static constexpr u32 kParamMask = 0u;  // (graph-shaped voices only: no mid-tile parameter switching there)
+  static constexpr bool kHasRunPrep = false;  // (its tick_tile is the per-sample loop below, not Svf's choice of step)
   template <typename F> struct Regs : Svf::Regs<F> { F cutoff, q, gain; u32 ty; };
   template <typename F, typename W>
   static __device__ __forceinline__ void load(Regs<F>& r, const W* s, long st) {
