@@ -289,9 +289,15 @@ typedef struct knh_stage_desc {
    * signal's sample, then the node renders one sample (the wrapper forces frame-by-frame processing, as in the reference);
    * an ordinary param_apply to that parameter is ignored while the link stands (audio_rate.rs:70-74).  Supported:
    *     SIN_WT 0 freq, 1 phase_offset      SIN_NUMERIC 0 freq, 1 phase_offset      *_CONST / POW_CONST 0 value
-   *     WR_MUL 0 "wr_mul"                  MUL_ENV_ASR / MUL_ENV_AR 0 attack_time, 1 release_time      -- all bit-exact --
+   *     WR_MUL 0 "wr_mul"                  MUL_ENV_ASR / MUL_ENV_AR 0 attack_time, 1 release_time
+   *     POLYBLEP 0 freq, 1 pulse_width     RANDOM_LIN 0 freq      BUFFER_READER 0 rate
+   *     MUL_ENVELOPE 0 time_scale          -- all of these setters are bit-exact (the PolyBlep waveforms that call sin stay
+   *     within the node's own tolerance) --
    *     SVF 0 cutoff_freq, 1 q, 2 gain     ONEPOLE_LPF / _HPF 0 cutoff_freq      -- the setter's tan / pow / sqrt / exp run in
    *     the device library: within a tolerance of the reference, not bit for bit.
+   * Not supported (KNH_ERR_UNSUPPORTED_CHAIN): delay_time of SAMPLE_DELAY / ALLPASS_DELAY / ALLPASS_FB_DELAY, PHASOR freq.
+   * A BUFFER_READER whose rate is linked stays linked to the same signal when knh_bank_assign_buffers moves its voice to
+   * another pool entry; under the wrapper a one-shot reader, like an envelope, marks done at frame 0 (buffer.rs:143).
    * A voice with such a stage is a graph (explicit operands): it runs in the single-wave kernel form, fused at init.
    * (KNH_STAGE_FLAG_AR_FREQ is the older spelling of "SIN_WT, ar_param = 1, driven by the running signal".)
    * An envelope under the wrapper marks done at frame 0, as the reference's does (envelopes.rs:153-156). */

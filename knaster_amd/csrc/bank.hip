@@ -114,6 +114,8 @@ knh_bank* make_bank(const knh_bank_desc& d, const knh::KernelEntry* entry, const
                 d.stages[i].input, d.stages[i].input2, d.stages[i].ar_param};
     // an SvfFilter with a parameter at audio rate keeps cutoff, q, gain and type on the device too (knh_dev::SvfP)
     if (s.kind == KNH_STAGE_SVF && s.ar_param != 0) s.n_slots = 12;
+    // a BufferReader whose rate is driven at audio rate keeps its Buffer's base rate there as well (knh_dev::BufferReaderP)
+    if (s.kind == KNH_STAGE_BUFFER_READER && s.ar_param != 0) s.n_slots = 14;
     b->stages.push_back(s);
     b->ctor.emplace_back(static_cast<size_t>(d.n_voices) * (k.n_ctor > 0 ? k.n_ctor : 0), 0.0);
     slot += s.n_slots;

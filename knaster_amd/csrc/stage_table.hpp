@@ -231,7 +231,11 @@ inline bool ar_param_supported(uint16_t kind, uint32_t param) {
     case KNH_STAGE_MUL_ENV_ASR: case KNH_STAGE_MUL_ENV_AR: return param <= 1;
     case KNH_STAGE_SVF: return param <= 2;
     case KNH_STAGE_ONEPOLE_LPF: case KNH_STAGE_ONEPOLE_HPF: return param == 0;
-    default: return false;
+    case KNH_STAGE_POLYBLEP: return param <= 1;  // freq, pulse_width
+    case KNH_STAGE_RANDOM_LIN: return param == 0;  // freq
+    case KNH_STAGE_BUFFER_READER: return param == 0;  // rate (start_s, duration_s, end_s are not: they need the Buffer's rate and the time arithmetic of the host)
+    case KNH_STAGE_MUL_ENVELOPE: return param == 0;  // time_scale
+    default: return false;  // the delays' delay_time among them (a modulated tap on the rings in HBM), and Phasor's freq
   }
 }
 

@@ -154,9 +154,11 @@ struct Bank final : knh_bank {
     return static_cast<double>(sat_u32(whole)) * buffer_sr + (static_cast<double>(tes) * buffer_sr) / 282240000.0;
   }
   // BufferReader::new(pool[buf_id[v]], rate, looping).start_at(start_s) and its init (buffer.rs:40-57, :106-115) for voice v,
-  // a = the three constructor arguments: the voice's shadows, and every slot of the stage handed to put(rel, word)
+  // a = the three constructor arguments: the voice's shadows, and every slot of the stage handed to put(rel, word).
+  // linked: `rate` is driven at audio rate (knh_dev::BufferReaderP) -- the device multiplies base_rate by every sample of the
+  // driver, so the entry's base_rate is a slot pair of its own, and follows the voice to another entry like the rest.
   template <typename Put>
-  void reader_construct(uint32_t v, const double* a, Put&& put) {
+  void reader_construct(uint32_t v, const double* a, bool linked, Put&& put) {
     const PoolEntry& e = buf_of(v);
     const double base_rate = e.sr / static_cast<double>(sample_rate);  // Buffer::buf_rate_scale
     const double length_seconds = static_cast<double>(e.n_frames) / e.sr;
@@ -175,6 +177,7 @@ struct Bank final : knh_bank {
     put(9, a[1] != 0.0 ? 1u : 0u);
     put(10, e.off);
     put(11, e.n_frames);
+    if (linked) put2(12, base_rate);
   }
   // the pool's size in samples with `n_frames` in place of entry `at` (at == pool.size(): one more entry), every entry padded to 64
   uint64_t pool_samples_with(size_t at, size_t n_frames) const {
@@ -375,11 +378,11 @@ struct Bank final : knh_bank {
       return KNH_OK;
     }
     note_frame(frame_base);
-    pending.reserve(pending.size() + count * 12);
+    pending.reserve(pending.size() + count * static_cast<size_t>(S.n_slots));
     for (size_t k = 0; k < count; ++k) {
       const uint32_t v = voices[k];
       buf_id[v] = ids[k];
-      reader_construct(v, args + 3 * k, [&](int rel, uint32_t word) {
+      reader_construct(v, args + 3 * k, S.ar_param != 0, [&](int rel, uint32_t word) {
         pending.push_back(HostEvent{v, frame_base, knh_dev::EV_SET, static_cast<uint32_t>(S.slot_base + rel), word});
       });
     }
@@ -614,7 +617,7 @@ struct Bank final : knh_bank {
               uint64_t off = 0;  // (put_buffer has kept the sum within 32 bits)
               for (PoolEntry& e : pool) { e.off = static_cast<uint32_t>(off); off += (e.n_frames + 63ull) & ~63ull; }
             }
-            reader_construct(v, a, [&](int rel, uint32_t word) { slot(S.slot_base + rel, v) = static_cast<W>(word); });
+            reader_construct(v, a, S.ar_param != 0, [&](int rel, uint32_t word) { slot(S.slot_base + rel, v) = static_cast<W>(word); });
           } break;
           case KNH_STAGE_PHASOR: {  // osc.rs:181-188 (new), :197-200 (init: step = freq * (1 / sample_rate))
             const double step = a[0] * (1.0 / static_cast<double>(sr));

@@ -356,6 +356,11 @@ struct RandomLin : StageDefaults {
     r.rng.store(s, st);
     s[2 * st] = f_to_word(r.value); s[3 * st] = f_to_word(r.width); s[4 * st] = f_to_word(r.phase);
   }
+  // RandomLin::freq (noise.rs:209-216): phase_step = F::new(value) * freq_to_phase_inc, which init made F::ONE / F::from(sample_rate) (:193)
+  template <typename F, int P>
+  static __device__ __forceinline__ void ar_set(Regs<F>& r, F v, const Ctx& c) {
+    r.step = v * ((F)1 / (F)c.sample_rate);
+  }
   template <typename F, bool FMA>
   static __device__ __forceinline__ F tick(Regs<F>& r, F, const Ctx&, u32, u32&) {
     const F out = mad<FMA>(r.phase, r.width, r.value);  // current_value + phase * current_change_width
@@ -568,6 +573,18 @@ struct PolyBlepOsc : StageDefaults {
   }
   template <typename F, typename W>
   static __device__ __forceinline__ void store(const Regs<F>& r, W* s, long) { s[0] = f_to_word(r.t); }
+  // PolyBlep::freq (polyblep.rs:163-165 -> set_freq :181-184: dt = F::new(freq) / sample_rate) / ::pulse_width (:168-170).
+  // next_sample's choice of a sine at or above sample_rate / 4 (:210, get_freq_in_hz() = dt * sample_rate) follows the new dt.
+  template <typename F, int P>
+  static __device__ __forceinline__ void ar_set(Regs<F>& r, F v, const Ctx& c) {
+    if (P == 0) {
+      const F sr = (F)c.sample_rate;  // F::from(sample_rate)
+      r.dt = v / sr;
+      r.fast = r.dt * sr >= sr / (F)4 ? 1u : 0u;
+    } else {
+      r.pw = v;
+    }
+  }
   static __device__ __forceinline__ float trunc_f(float v) { return __builtin_truncf(v); }
   static __device__ __forceinline__ double trunc_f(double v) { return __builtin_trunc(v); }
   static __device__ __forceinline__ float sin_f(float v) { return __ocml_sin_f32(v); }
@@ -826,6 +843,42 @@ struct BufferReader : StageDefaults {
       case 11: r.n = w; break;
       default: break;
     }
+  }
+};
+// BufferReader with `rate` driven at audio rate (ArP<BufferReaderP, 0>): BufferReader::rate (buffer.rs:76-78) stores the
+// value, and every sample steps by base_rate * rate (:137) -- so base_rate (Buffer::buf_rate_scale of the voice's own Buffer)
+// is device state too, written by the host with the other slots of a reader (init, and a swap to another pool entry).
+// Under the wrapper the reader runs through UGen::process, one sample at a time: a one-shot voice marks done at frame 0
+// of that sample's "block" (:143), not at i + 1 as process_block does (:172).
+// slots: 0..11 as BufferReader, 12,13 base_rate
+struct BufferReaderP : BufferReader {
+  static constexpr int kSlots = 14;
+  template <typename F> struct Regs : BufferReader::Regs<F> { double base; };
+  template <typename F, typename W>
+  static __device__ __forceinline__ void load(Regs<F>& r, const W* s, long st) {
+    BufferReader::load<F, W>(r, s, st);
+    r.base = ld2(s, st, 12);
+  }
+  template <typename F, int P>
+  static __device__ __forceinline__ void ar_set(Regs<F>& r, F v, const Ctx&) { r.step = r.base * (double)v; }
+  template <typename F, bool FMA>
+  static __device__ __forceinline__ F tick(Regs<F>& r, F x, const Ctx& c, u32 frame, u32& done_frame) {
+    u32 mark = 0xFFFFFFFFu;
+    const F y = BufferReader::tick<F, FMA>(r, x, c, frame, mark);
+    if (mark != 0xFFFFFFFFu) done_frame = mark - 1u;  // mark_done(0): the frame the wrapper's caller handed in, not the one after it
+    return y;
+  }
+  template <typename F, bool FMA, int T>
+  static __device__ __forceinline__ void tick_tile(Regs<F>& r, F (&x)[T], const Ctx& c, u32 frame0, u32& done_frame) {
+#pragma unroll
+    for (int j = 0; j < T; ++j) x[j] = tick<F, FMA>(r, x[j], c, frame0 + j, done_frame);
+  }
+  template <typename F>
+  static __device__ __forceinline__ void on_event(Regs<F>& r, u32 op, u32 rel, u64 bits, u32 frame) {
+    if (rel < 12u) { BufferReader::on_event<F>(r, op, rel, bits, frame); return; }
+    if ((op & 0x7Fu) != EV_SET) return;
+    const u64 b = __builtin_bit_cast(u64, r.base), w = (u64)(u32)bits;
+    r.base = __builtin_bit_cast(double, rel == 12u ? ((b & 0xFFFFFFFF00000000ull) | w) : ((b & 0x00000000FFFFFFFFull) | (w << 32)));
   }
 };
 
@@ -1713,6 +1766,12 @@ struct MulSegEnv : StageDefaults {
   static __device__ __forceinline__ void store(const Regs<F>& r, W* s, long st) {
     s[0] = (W)r.running; s[st] = (W)r.cur;
     st2(s, st, 2, r.time); st2(s, st, 4, r.from);
+  }
+  // Envelope's time_scale (envelopes.rs:479: F::new(value).to_f64()); a sample's increment is time_scale * base_scale (:432),
+  // base_scale the f64 reciprocal of the sample rate (:404)
+  template <typename F, int P>
+  static __device__ __forceinline__ void ar_set(Regs<F>& r, F v, const Ctx& c) {
+    r.dt = (double)v * (1.0 / (double)c.sample_rate);
   }
   template <typename F, bool FMA>
   static __device__ __forceinline__ F tick(Regs<F>& r, F x, const Ctx& c, u32, u32& done_frame) {
