@@ -356,7 +356,9 @@ typedef struct knh_bank knh_bank;
 /* Flags returned by process (summary of UGenFlags, knaster_core/src/ugen.rs:121-219) */
 enum {
   KNH_FLAG_ANY_DONE = 1u << 0, /* some voice's envelope called mark_done this block */
-  KNH_FLAG_ALL_DONE = 1u << 1  /* every voice's last envelope is Stopped            */
+  KNH_FLAG_ALL_DONE = 1u << 1  /* every voice's last envelope is Stopped: the last in the stage LIST (a one-shot
+                                * BufferReader counts as one), in a voice that is a graph too -- not the last in the
+                                * reference's task order, which names the done frame when several finish in one block */
 };
 
 /* Library / device discovery. */

@@ -38,6 +38,7 @@ struct ShardedBank final : knh_bank {
   F* d_parts = nullptr;          // [K][cap_blocks][channels][block_size]: each shard's mix
   F* d_out = nullptr;            // used when the caller gives no device buffer
   F* h_out = nullptr;            // pinned
+  std::vector<F> pan_rows;       // per-voice output of a chain that ends in Pan2: every range's two planes, range after range
   uint32_t cap_blocks = 0;
   std::vector<int> rcs;
   std::vector<uint32_t> shard_flags;
@@ -331,12 +332,18 @@ struct ShardedBank final : knh_bank {
     const size_t elems = static_cast<size_t>(cap_blocks) * desc.out_channels * block_size;  // per shard
     const bool pending = sum_pending;
     const size_t n_out_elems = static_cast<size_t>(n_blocks) * desc.out_channels * block_size;
+    // A chain that ends in Pan2 hands out two planes, [2][voices][block_size]: a range's right plane belongs behind the whole
+    // bank's left plane, not behind its own.  Each range renders its [2][count][block_size] into rows of its own (range k from
+    // 2 * base[k] rows on: the ranges do not overlap), and the planes are put in place below.
+    const bool pan_planes = voices_host && n() > 1 && !stages.empty() && stages.back().kind == KNH_STAGE_PAN2;
+    if (pan_planes) pan_rows.resize(2 * static_cast<size_t>(nv) * block_size);
     workers->run([&](int k) {
       if (hipSetDevice(dev_of(k)) != hipSuccess) { rcs[k] = KNH_ERR_DEVICE; return; }
       apply_deferred(k);
       // the previous launch's sum must be done with this shard's mix before the shard overwrites it
       if (pending && hipStreamWaitEvent(streams[k], sum_done, 0) != hipSuccess) { rcs[k] = KNH_ERR_DEVICE; return; }
       void* vh = voices_host ? static_cast<void*>(static_cast<F*>(voices_host) + static_cast<size_t>(base[k]) * block_size) : nullptr;
+      if (pan_planes) vh = pan_rows.data() + 2 * static_cast<size_t>(base[k]) * block_size;
       // with a host destination the shard also waits for its stream (per-voice rows, flags); its mix stays on the device
       shard_flags[k] = 0;
       F* slot = d_parts + k * elems;                     // on the bank's (first) device
@@ -353,6 +360,13 @@ struct ShardedBank final : knh_bank {
       if (rcs[k] == KNH_ERR_DEVICE && shard[k]->err.empty()) return fail(KNH_ERR_DEVICE, "HIP error in a shard worker");
       if (rcs[k] != KNH_OK) return adopt(k, rcs[k]);
     }
+    if (pan_planes)  // (a call for per-voice rows is a blocking one: every range has waited for its rows)
+      for (int k = 0; k < n(); ++k) {
+        const size_t first = static_cast<size_t>(base[k]) * block_size, rows = static_cast<size_t>(base[k + 1] - base[k]) * block_size;
+        const F* src = pan_rows.data() + 2 * first;
+        std::memcpy(static_cast<F*>(voices_host) + first, src, rows * sizeof(F));
+        std::memcpy(static_cast<F*>(voices_host) + static_cast<size_t>(nv) * block_size + first, src + rows, rows * sizeof(F));
+      }
     for (int k = 0; k < n(); ++k) KNH_HIP(hipStreamWaitEvent(s, shard_done[k], 0));
     F* dst = out_device ? static_cast<F*>(out_device) : d_out;
     const size_t n_out = static_cast<size_t>(n_blocks) * desc.out_channels * block_size;

@@ -145,7 +145,18 @@ struct Bank final : knh_bank {
   struct PoolEntry { std::vector<F> samples; double sr = 0.0; uint32_t n_frames = 0, off = 0; };
   std::vector<PoolEntry> pool;
   std::vector<uint32_t> buf_id;                      // [voice], empty: every voice on entry 0
-  std::vector<double> buf_start, buf_dur, buf_rate;  // BufferReader shadows per voice: start_frame, dur_frame, rate
+  // BufferReader shadows, [reader][voice]: start_frame, dur_frame, rate.  A chain may hold several readers (a graph voice
+  // that sums two): each has a start, a length and a rate of its own, so a seconds-valued setter or a restart of one reads
+  // its own shadows and not the ones the reader constructed last left behind.
+  std::vector<double> buf_start, buf_dur, buf_rate;
+  size_t reader_at(const StageInfo& S, uint32_t v) const {  // S: a BufferReader stage of `stages`
+    size_t k = 0;
+    for (const StageInfo& T : stages) {
+      if (&T == &S) break;
+      k += T.kind == KNH_STAGE_BUFFER_READER;
+    }
+    return k * nv + v;
+  }
   const PoolEntry& buf_of(uint32_t v) const { return pool[buf_id.empty() ? 0u : buf_id[v]]; }
   // Seconds::from_secs_f64(secs).to_samples_f64(buffer_sr), time.rs:59-64,92-96
   static double secs_to_frames(double secs, double buffer_sr) {
@@ -158,12 +169,14 @@ struct Bank final : knh_bank {
   // linked: `rate` is driven at audio rate (knh_dev::BufferReaderP) -- the device multiplies base_rate by every sample of the
   // driver, so the entry's base_rate is a slot pair of its own, and follows the voice to another entry like the rest.
   template <typename Put>
-  void reader_construct(uint32_t v, const double* a, bool linked, Put&& put) {
+  void reader_construct(const StageInfo& S, uint32_t v, const double* a, Put&& put) {
+    const bool linked = S.ar_param != 0;
+    const size_t r = reader_at(S, v);
     const PoolEntry& e = buf_of(v);
     const double base_rate = e.sr / static_cast<double>(sample_rate);  // Buffer::buf_rate_scale
     const double length_seconds = static_cast<double>(e.n_frames) / e.sr;
     const double start = secs_to_frames(a[2], e.sr), dur = secs_to_frames(length_seconds, e.sr);
-    buf_start[v] = start; buf_dur[v] = dur; buf_rate[v] = a[0];
+    buf_start[r] = start; buf_dur[r] = dur; buf_rate[r] = a[0];
     auto put2 = [&](int rel, double d) {
       const uint64_t b = to_bits(d);
       put(rel, static_cast<uint32_t>(b));
@@ -382,7 +395,7 @@ struct Bank final : knh_bank {
     for (size_t k = 0; k < count; ++k) {
       const uint32_t v = voices[k];
       buf_id[v] = ids[k];
-      reader_construct(v, args + 3 * k, S.ar_param != 0, [&](int rel, uint32_t word) {
+      reader_construct(S, v, args + 3 * k, [&](int rel, uint32_t word) {
         pending.push_back(HostEvent{v, frame_base, knh_dev::EV_SET, static_cast<uint32_t>(S.slot_base + rel), word});
       });
     }
@@ -612,12 +625,14 @@ struct Bank final : knh_bank {
           case KNH_STAGE_BUFFER_READER: {  // buffer.rs:40-57 (new, start_at), :106-115 (init)
             if (pool.empty()) return fail(KNH_ERR_INVALID_ARGUMENT, "BufferReader stage without knh_bank_set_buffer or knh_bank_add_buffer");
             if (S.dcpb > 0) return fail(KNH_ERR_INVALID_ARGUMENT, "BufferReader cannot be wrapped in WrPreciseTiming here");
-            if (v == 0) {
-              buf_start.assign(nv, 0.0); buf_dur.assign(nv, 0.0); buf_rate.assign(nv, 0.0);
+            if (v == 0 && reader_at(S, 0) == 0) {  // the chain's first reader: the shadows of all of them, the pool's layout
+              size_t readers = 0;
+              for (const StageInfo& T : stages) readers += T.kind == KNH_STAGE_BUFFER_READER;
+              buf_start.assign(readers * nv, 0.0); buf_dur.assign(readers * nv, 0.0); buf_rate.assign(readers * nv, 0.0);
               uint64_t off = 0;  // (put_buffer has kept the sum within 32 bits)
               for (PoolEntry& e : pool) { e.off = static_cast<uint32_t>(off); off += (e.n_frames + 63ull) & ~63ull; }
             }
-            reader_construct(v, a, S.ar_param != 0, [&](int rel, uint32_t word) { slot(S.slot_base + rel, v) = static_cast<W>(word); });
+            reader_construct(S, v, a, [&](int rel, uint32_t word) { slot(S.slot_base + rel, v) = static_cast<W>(word); });
           } break;
           case KNH_STAGE_PHASOR: {  // osc.rs:181-188 (new), :197-200 (init: step = freq * (1 / sample_rate))
             const double step = a[0] * (1.0 / static_cast<double>(sr));
@@ -1260,13 +1275,14 @@ struct Bank final : knh_bank {
           set(rel + 1, static_cast<uint32_t>(b >> 32));
         };
         const double buffer_sr = buf_of(v).sr;  // the voice's own Buffer's: seconds become its frames, its rate scale
+        const size_t r = reader_at(S, v);
         switch (param) {
-          case 0: buf_rate[v] = f; set2(2, (buffer_sr / static_cast<double>(sample_rate)) * f); break;
+          case 0: buf_rate[r] = f; set2(2, (buffer_sr / static_cast<double>(sample_rate)) * f); break;
           case 1: set(9, iv != 0 ? 1u : 0u); break;
-          case 2: buf_start[v] = secs_to_frames(f, buffer_sr); set2(4, buf_start[v]); set2(6, buf_start[v] + buf_dur[v]); break;
-          case 3: buf_dur[v] = secs_to_frames(f, buffer_sr); set2(6, buf_start[v] + buf_dur[v]); break;
+          case 2: buf_start[r] = secs_to_frames(f, buffer_sr); set2(4, buf_start[r]); set2(6, buf_start[r] + buf_dur[r]); break;
+          case 3: buf_dur[r] = secs_to_frames(f, buffer_sr); set2(6, buf_start[r] + buf_dur[r]); break;
           case 4: set2(6, secs_to_frames(f, buffer_sr)); break;
-          default: set2(0, buf_start[v]); set(8, 0); break;  // t_restart -> reset -> jump_to(start_frame)
+          default: set2(0, buf_start[r]); set(8, 0); break;  // t_restart -> reset -> jump_to(start_frame)
         }
       } break;
       case KNH_STAGE_POLYBLEP: {  // polyblep.rs:158-182
