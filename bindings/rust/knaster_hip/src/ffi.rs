@@ -162,6 +162,8 @@ unsafe extern "C" {
     pub fn knh_bank_set_buffer(bank: *mut knh_bank, stage: u32, samples: *const c_void, n_frames: usize, buffer_sample_rate: f64) -> i32;
     pub fn knh_bank_add_buffer(bank: *mut knh_bank, stage: u32, samples: *const c_void, n_frames: usize, buffer_sample_rate: f64, out_index: *mut u32) -> i32;
     pub fn knh_bank_assign_buffers(bank: *mut knh_bank, stage: u32, count: usize, voices: *const u32, buffer_ids: *const u32, ctor: *const f64) -> i32;
+    pub fn knh_bank_set_voice_ctor_args(bank: *mut knh_bank, stage: u32, count: usize, voices: *const u32, args: *const f64, n_args: u32) -> i32;
+    pub fn knh_bank_restart_voices(bank: *mut knh_bank, count: usize, voices: *const u32) -> i32;
     pub fn knh_bank_buffer_count(bank: *const knh_bank, stage: u32) -> u32;
     pub fn knh_bank_init(bank: *mut knh_bank, sample_rate: u32, block_size: usize) -> i32;
     pub fn knh_bank_destroy(bank: *mut knh_bank);

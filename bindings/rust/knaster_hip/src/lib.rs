@@ -257,6 +257,21 @@ impl<F: Float, I: Size> GpuVoiceBank<F, I> {
         let rc = unsafe { knh_bank_assign_buffers(self.h, stage as u32, voices.len(), voices.as_ptr(), buffer_ids.as_ptr(), c) };
         if rc != KNH_OK { Err(last_error(self.h)) } else { Ok(()) }
     }
+    /// New constructor arguments for `stage` of the listed voices of a running bank (`args`: `n_args` per voice, row after
+    /// row): kept until the next `restart_voices` that names the voice.
+    pub fn set_voice_ctor_args(&mut self, stage: usize, voices: &[u32], args: &[f64], n_args: usize) -> Result<(), BankError> {
+        if args.len() != voices.len() * n_args {
+            return Err(BankError("set_voice_ctor_args: args must hold n_args values per voice".into()));
+        }
+        let rc = unsafe { knh_bank_set_voice_ctor_args(self.h, stage as u32, voices.len(), voices.as_ptr(), args.as_ptr(), n_args as u32) };
+        if rc != KNH_OK { Err(last_error(self.h)) } else { Ok(()) }
+    }
+    /// The listed voices become freshly constructed nodes at frame 0 of the next block: what the reference has after a
+    /// voice's nodes are freed (its envelope reported done) and the same chain is pushed again for the next note.
+    pub fn restart_voices(&mut self, voices: &[u32]) -> Result<(), BankError> {
+        let rc = unsafe { knh_bank_restart_voices(self.h, voices.len(), voices.as_ptr()) };
+        if rc != KNH_OK { Err(last_error(self.h)) } else { Ok(()) }
+    }
     /// Entries in the pool of the `BufferReader` stage.
     pub fn buffer_count(&self, stage: usize) -> u32 {
         unsafe { knh_bank_buffer_count(self.h, stage as u32) }

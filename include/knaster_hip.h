@@ -425,6 +425,43 @@ int32_t knh_bank_assign_buffers(knh_bank* bank, uint32_t stage, size_t count, co
 /* Entries in the pool of BufferReader stage `stage` (0 for any other stage). */
 uint32_t knh_bank_buffer_count(const knh_bank* bank, uint32_t stage);
 int32_t knh_bank_init(knh_bank* bank, uint32_t sample_rate, size_t block_size);
+/* ---- Restarting voices of a running bank ----------------------------------------------------------------------------
+ * A polyphonic host frees a voice's nodes when its envelope reports done (free_node_when_done, graph.rs:2483-2513) and
+ * pushes the same chain again for the next note.  KNH_FLAG_ANY_DONE and knh_bank_read_done_frames say when; these two
+ * calls are the second half: the voice becomes freshly constructed nodes without the bank being destroyed and created again.
+ *
+ * New constructor arguments for stage `stage` of the listed voices, allowed after knh_bank_init: kept on the host and used
+ * by the next knh_bank_restart_voices that names the voice.  args = [count][n_args], n_args as knh_bank_set_ctor_args. */
+int32_t knh_bank_set_voice_ctor_args(knh_bank* bank, uint32_t stage, size_t count, const uint32_t* voices,
+                                     const double* args, uint32_t n_args);
+/* The listed voices become what the reference has after the voice's nodes are freed and the same chain is pushed and
+ * initialised again: every node constructed from the voice's current constructor arguments (the latest given by either
+ * ctor call) and UGen::init(sample_rate, block_size) run on it.  Takes effect at frame 0 of the next process call.
+ *
+ * What "fresh" covers: after the restart a listed voice is, bit for bit, the voice of a bank initialised at that block with
+ * those constructor arguments -- every state slot of every stage (phases, filter memories and coefficients, envelope state,
+ * noise seeds, RandomLin's draws, the AllpassInterpolator's ones, a BufferReader's extra slots), its segment-table rows, its
+ * delay ring zeroed, its done frame back to UINT32_MAX, its WrPreciseTiming armed delays back to 0 and its queues empty
+ * (those the host resolves and those the device resolves), its WrSmoothParams state back to "no smoothing selected", and
+ * every value the parameter setters read back later (an SvfFilter's cutoff / q / gain / type, the envelope times, a
+ * BufferReader's start / length / rate, the ring length).  A BufferReader is constructed on the voice's current pool entry.
+ * Other voices are untouched, to the bit.
+ *
+ * Ordering: parameter calls for a listed voice made BEFORE this call are dropped -- knh_bank_param_apply_many_at calls for
+ * later blocks of the coming launch and changes waiting in a queue included: they addressed nodes that no longer exist.
+ * Calls made AFTER it address the new nodes and apply from frame 0 of the next block.
+ *
+ * A refused call changes nothing.  Both calls refuse with
+ *   KNH_ERR_NOT_INITIALISED    before knh_bank_init,
+ *   KNH_ERR_OUT_OF_RANGE       a voice or stage index out of range,
+ *   KNH_ERR_INVALID_ARGUMENT   a wrong n_args, a null array with count > 0,
+ *   KNH_ERR_INVALID_ARGUMENT   while a block is partly processed (the last process call ended inside a block): graph edits
+ *                              land between blocks in the reference,
+ *   KNH_ERR_OUT_OF_RANGE       delay constructor arguments whose ring would be longer than the rings allocated at init,
+ *   KNH_ERR_UNSUPPORTED_CHAIN  a chain that ends in KNH_STAGE_GALACTIC (its rings and state are the reverb's own).
+ * count == 0 is KNH_OK; a voice listed twice is restarted once.  Host-sharded and multi-device banks route by global voice
+ * index; a rank bank checks and otherwise ignores other ranks' voices, as it does for parameter calls. */
+int32_t knh_bank_restart_voices(knh_bank* bank, size_t count, const uint32_t* voices);
 void knh_bank_destroy(knh_bank* bank);
 
 /* UGen::inputs()/outputs()/parameters() of the bank node -- dynugen.rs:23-63 */

@@ -159,6 +159,23 @@ class VoiceBank:
                                                       ids.ctypes.data_as(C.c_void_p),
                                                       None if c is None else c.ctypes.data_as(C.c_void_p)))
 
+    def set_voice_ctor_args(self, stage: int, voices, args):
+        """New constructor arguments [count, n_args] for `stage` of the listed voices of a running bank: kept until the next
+        restart_voices that names the voice (knh_bank_set_voice_ctor_args)."""
+        v = np.ascontiguousarray(voices, dtype=np.uint32)
+        a = np.ascontiguousarray(np.asarray(args, dtype=np.float64))
+        if a.ndim == 1:
+            a = a.reshape(v.shape[0], -1) if v.shape[0] else a.reshape(0, 0)
+        if a.shape[0] != v.shape[0]:
+            raise ValueError(f"args must hold one row per voice, got {a.shape} for {v.shape[0]} voices")
+        self._check(self._lib.knh_bank_set_voice_ctor_args(self._h, stage, v.shape[0], v.ctypes.data_as(C.c_void_p),
+                                                           a.ctypes.data_as(C.c_void_p), a.shape[1]))
+
+    def restart_voices(self, voices):
+        """The listed voices become freshly constructed nodes at frame 0 of the next block (knh_bank_restart_voices)."""
+        v = np.ascontiguousarray(voices, dtype=np.uint32)
+        self._check(self._lib.knh_bank_restart_voices(self._h, v.shape[0], v.ctypes.data_as(C.c_void_p)))
+
     def buffer_count(self, stage: int) -> int:
         return int(self._lib.knh_bank_buffer_count(self._h, stage))
 

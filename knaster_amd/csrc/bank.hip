@@ -457,6 +457,18 @@ int32_t knh_bank_assign_buffers(knh_bank* bank, uint32_t stage, size_t count, co
     return bank->assign_buffers(stage, count, voices, buffer_ids, ctor);
   });
 }
+int32_t knh_bank_set_voice_ctor_args(knh_bank* bank, uint32_t stage, size_t count, const uint32_t* voices, const double* args, uint32_t n_args) {
+  return guarded(bank, [&]() -> int32_t {
+    if (!bank) return KNH_ERR_INVALID_ARGUMENT;
+    return bank->set_voice_ctor(stage, count, voices, args, n_args);
+  });
+}
+int32_t knh_bank_restart_voices(knh_bank* bank, size_t count, const uint32_t* voices) {
+  return guarded(bank, [&]() -> int32_t {
+    if (!bank) return KNH_ERR_INVALID_ARGUMENT;
+    return bank->restart_voices(count, voices);
+  });
+}
 uint32_t knh_bank_buffer_count(const knh_bank* bank, uint32_t stage) {
   try {
     return bank ? bank->buffer_count(stage) : 0u;

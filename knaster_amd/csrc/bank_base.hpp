@@ -43,6 +43,10 @@ struct knh_bank {
   virtual int assign_buffers(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* buffer_ids, const double* ctor) = 0;
   virtual uint32_t buffer_count(uint32_t stage) const = 0;
   virtual int init(uint32_t sr, size_t bs) = 0;
+  // knh_bank_set_voice_ctor_args / knh_bank_restart_voices: voices of a running bank become freshly constructed nodes
+  // (keep = false: the call is checked and nothing is kept -- a bank of several ranges asks every range before any keeps its share)
+  virtual int set_voice_ctor(uint32_t stage, size_t count, const uint32_t* voices, const double* args, uint32_t n_args, bool keep = true) = 0;
+  virtual int restart_voices(size_t count, const uint32_t* voices) = 0;
   virtual int param_apply(uint32_t voice, uint32_t stage, uint32_t param, uint32_t kind, double f, int64_t i) = 0;
   virtual int set_delay(uint32_t voice, uint32_t stage, uint32_t param, uint16_t delay) = 0;
   virtual int call_at(uint32_t block_offset, bool is_delay, uint32_t voice, uint32_t stage, uint32_t param, uint32_t kind, double f,

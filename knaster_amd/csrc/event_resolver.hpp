@@ -201,6 +201,7 @@ struct DevEventResolver {
     KNH_HIP(knh::launch_resolve_events(ra, ev_stream));
     KNH_HIP(hipEventRecord(recs_done[b], ev_stream));  // the records are read, and the lists complete: one event says both
     recs_busy[b] = true;
+    last_resolve = static_cast<int>(b);
     KNH_HIP(hipStreamWaitEvent(s, recs_done[b], 0));  // the voice kernel reads this set
     out_in_use = static_cast<int>(set);
     // the host goes on filling the other buffer
@@ -209,6 +210,31 @@ struct DevEventResolver {
     h_recs = h_recs2[recs_parity];
     out->ev_start = d_out_start[set];
     out->events = d_out_events[set];
+    return KNH_OK;
+  }
+  // knh_bank_restart_voices.  The calls already recorded for the marked voices addressed nodes that no longer exist: dropped
+  // (the buffer being filled is not one a kernel reads).
+  void drop_voices(const std::vector<uint8_t>& marked) {
+    size_t w = 0;
+    uint32_t mx = 0;
+    for (size_t i = 0; i < n_recs; ++i) {
+      if (marked[h_recs[i].voice]) continue;
+      mx = std::max<uint32_t>(mx, h_recs[i].block);
+      h_recs[w++] = h_recs[i];
+    }
+    n_recs = w;
+    recs_max_block = mx;
+  }
+  // The armed delays are the resolver's persistent device state; the restart kernel clears the restarted voices' on `s`, the
+  // stream of the coming launch.  Ordered by events against the resolver's own stream, which runs beside the voice kernels:
+  // the kernel starts after the resolver's last pass (restart_may_write), the next pass after the kernel (restart_written).
+  unsigned short* armed() const { return d_armed; }
+  int restart_may_write(hipStream_t s) {
+    if (last_resolve >= 0) KNH_HIP(hipStreamWaitEvent(s, recs_done[last_resolve], 0));
+    return KNH_OK;
+  }
+  int restart_written(hipEvent_t done) {
+    KNH_HIP(hipStreamWaitEvent(ev_stream, done, 0));
     return KNH_OK;
   }
   // The voice kernel of the launch is enqueued on `s`: the resolver may rewrite the set of lists it reads once it has.
@@ -228,7 +254,8 @@ struct DevEventResolver {
   hipEvent_t recs_done[2] = {nullptr, nullptr};
   bool recs_busy[2] = {false, false};
   unsigned recs_parity = 0;
-  QRec* h_recs = nullptr;                     // = h_recs2[recs_parity]
+  int last_resolve = -1;                      // the buffer whose recs_done marks the end of the resolver's last pass
+  QRec* h_recs = nullptr;                    // = h_recs2[recs_parity]
   size_t n_recs = 0;
   uint32_t recs_max_block = 0;
   knh_dev::DevStage* d_stages = nullptr;

@@ -106,6 +106,15 @@ struct GalacticBank final : knh_bank {
     return adopt(inner->assign_buffers(stage, count, voices, ids, ctor));
   }
   uint32_t buffer_count(uint32_t stage) const override { return mine(stage) ? 0u : inner->buffer_count(stage); }
+  // The reverb's 24 rings and its state live here, not in the inner bank, and have no restart yet
+  int set_voice_ctor(uint32_t, size_t, const uint32_t*, const double*, uint32_t, bool) override {
+    if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
+    return fail(KNH_ERR_UNSUPPORTED_CHAIN, "the voices of a chain that ends in Galactic cannot be restarted");
+  }
+  int restart_voices(size_t, const uint32_t*) override {
+    if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
+    return fail(KNH_ERR_UNSUPPORTED_CHAIN, "the voices of a chain that ends in Galactic cannot be restarted");
+  }
   int set_input(uint32_t n_blocks, const void* host, const void* dev) override {
     if (n_blocks > 1) return fail(KNH_ERR_INVALID_ARGUMENT, "a chain that ends in Galactic takes its bank inputs one block per call");
     return adopt(inner->set_input(n_blocks, host, dev));

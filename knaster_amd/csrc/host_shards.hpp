@@ -139,6 +139,50 @@ struct ShardedBank final : knh_bank {
     }
     return KNH_OK;
   }
+  // knh_bank_set_voice_ctor_args / knh_bank_restart_voices: by global voice index, each range its own voices.  Checked as a whole
+  // first -- the ranges are alike, so what one refuses for a voice of its own the bank refuses here -- then handed out.
+  std::vector<uint32_t> rs_voices;
+  int set_voice_ctor(uint32_t stage, size_t count, const uint32_t* voices, const double* args, uint32_t n_args, bool keep) override {
+    if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
+    { int rc = shard[0]->set_voice_ctor(stage, 0, nullptr, nullptr, n_args, false); if (rc != KNH_OK) return adopt(0, rc); }  // the stage, n_args
+    if (count && (!voices || (n_args && !args))) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
+    for (size_t i = 0; i < count; ++i)
+      if (voices[i] >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
+    std::vector<std::vector<uint32_t>> vs(static_cast<size_t>(n()));
+    std::vector<std::vector<double>> as(static_cast<size_t>(n()));
+    for (size_t i = 0; i < count; ++i) {
+      const int k = of_voice(voices[i]);
+      vs[k].push_back(voices[i] - base[k]);
+      if (n_args) as[k].insert(as[k].end(), args + i * n_args, args + (i + 1) * n_args);
+    }
+    // (a refused call changes nothing in any range: every range checks its share before any range keeps it)
+    for (int pass = 0; pass < (keep ? 2 : 1); ++pass)
+      for (int k = 0; k < n(); ++k) {
+        if (vs[k].empty()) continue;
+        int rc = shard[k]->set_voice_ctor(stage, vs[k].size(), vs[k].data(), as[k].data(), n_args, pass == 1);
+        if (rc != KNH_OK) return adopt(k, rc);
+      }
+    return KNH_OK;
+  }
+  int restart_voices(size_t count, const uint32_t* voices) override {
+    if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
+    if (count && !voices) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
+    for (size_t i = 0; i < count; ++i)
+      if (voices[i] >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
+    { int rc = shard[0]->restart_voices(0, nullptr); if (rc != KNH_OK) return adopt(0, rc); }  // (a block partly processed: every range alike)
+    flush_deferred();  // batched calls made before this one reach their ranges first, and are dropped there
+    for (int k = 0; k < n(); ++k) {
+      rs_voices.clear();
+      for (size_t i = 0; i < count; ++i)
+        if (voices[i] >= base[k] && voices[i] < base[k + 1]) rs_voices.push_back(voices[i] - base[k]);
+      if (rs_voices.empty()) continue;
+      if (multi_device()) KNH_HIP(hipSetDevice(dev_of(k)));
+      int rc = shard[k]->restart_voices(rs_voices.size(), rs_voices.data());
+      if (rc != KNH_OK) return adopt(k, rc);
+    }
+    if (multi_device()) KNH_HIP(hipSetDevice(device));
+    return KNH_OK;
+  }
   int set_input(uint32_t n_blocks, const void* host, const void* dev) override {  // every range reads the same input block(s)
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (dev && multi_device()) return fail(KNH_ERR_INVALID_ARGUMENT, "a bank on several GPUs takes its input from host memory");

@@ -58,10 +58,27 @@ struct EventResolveArgs {
   u32* overflow;            // mapped pinned host word: set when a change found its node's WrPreciseTiming queue full and was dropped
                             // (the reference logs "Not enough space for scheduled changes", precise_timing.rs:129-134; so does the host)
 };
+// knh_bank_restart_voices (kernels_restart.hip): one workgroup per restarted voice writes the voice's freshly constructed state.
+struct RestartArgs {
+  const u32* voices;        // pinned host memory, [count]: the voices, each once
+  const void* words;        // pinned, [count][n_slots]: the state words (u32; f64 banks: u64)
+  const double* seg_rows;   // pinned, [count][seg_max][3]: the segment Envelope's rows (seg_table null: none)
+  void* state;              // device, [n_slots][stride]
+  long stride;
+  u32 n_slots, n_voices, f64;
+  u32* done_frames;         // device, [n_voices]
+  unsigned short* armed;    // device, [n_params_total][n_voices] (EventResolveArgs::armed), or null
+  u32 n_params_total;
+  double* seg_table;        // device, [n_voices][seg_max][3], or null
+  u32 seg_max;
+  void* delay_ring;         // device, [n_voices + 1][delay_stride] samples, or null
+  u32 delay_stride;         // samples, a multiple of four
+};
 }  // namespace knh_dev
 
 namespace knh {
 hipError_t launch_resolve_events(const knh_dev::EventResolveArgs& a, hipStream_t s);
+hipError_t launch_restart_voices(const knh_dev::RestartArgs& a, unsigned count, hipStream_t s);
 
 template <typename F>
 using VoiceLaunchFn = hipError_t (*)(const knh_dev::VoiceKernelArgs<F>& args, unsigned n_wavefronts, hipStream_t stream);

@@ -122,6 +122,40 @@ struct RankBank final : knh_bank {
     // (an empty share still goes to the local bank: its refusals -- no constructor arguments, an envelope in the chain -- are every rank's)
     return adopt(local->assign_buffers(stage, asg_voices.size(), asg_voices.data(), asg_ids.data(), ctor ? (asg_ctor.empty() ? ctor : asg_ctor.data()) : nullptr));
   }
+  // knh_bank_set_voice_ctor_args / knh_bank_restart_voices: global voice indices, checked on every rank alike; the voices of
+  // other ranks are their business, as with parameter calls
+  std::vector<uint32_t> rs_voices;
+  std::vector<double> rs_args;
+  int set_voice_ctor(uint32_t stage, size_t count, const uint32_t* voices, const double* args, uint32_t n_args, bool keep) override {
+    if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
+    if (stage >= stages.size()) return fail(KNH_ERR_OUT_OF_RANGE, "stage out of range");
+    if (count && (!voices || (n_args && !args))) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
+    for (size_t i = 0; i < count; ++i)
+      if (voices[i] >= total) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
+    if (!local) return KNH_OK;
+    rs_voices.clear(); rs_args.clear();
+    for (size_t i = 0; i < count; ++i) {
+      if (!mine(voices[i])) continue;
+      rs_voices.push_back(voices[i] - lo);
+      if (n_args) rs_args.insert(rs_args.end(), args + i * n_args, args + (i + 1) * n_args);
+    }
+    // (an empty share still goes to the local bank: its refusals -- n_args, a block partly processed -- are every rank's)
+    return adopt(local->set_voice_ctor(stage, rs_voices.size(), rs_voices.data(), rs_args.data(), n_args, keep));
+  }
+  int restart_voices(size_t count, const uint32_t* voices) override {
+    if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
+    if (count && !voices) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
+    for (size_t i = 0; i < count; ++i)
+      if (voices[i] >= total) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
+    if (!local) return KNH_OK;
+    { int rc = local->restart_voices(0, nullptr); if (rc != KNH_OK) return adopt(rc); }  // (a block partly processed: refused whoever owns the voices)
+    rs_voices.clear();
+    for (size_t i = 0; i < count; ++i)
+      if (mine(voices[i])) rs_voices.push_back(voices[i] - lo);
+    if (rs_voices.empty()) return KNH_OK;
+    KNH_HIP(hipSetDevice(device));
+    return adopt(local->restart_voices(rs_voices.size(), rs_voices.data()));
+  }
   int set_input(uint32_t n_blocks, const void* host, const void* dev) override {  // every rank is handed the same input block(s)
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     return local ? adopt(local->set_input(n_blocks, host, dev)) : KNH_OK;

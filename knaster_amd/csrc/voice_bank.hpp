@@ -304,12 +304,13 @@ struct Bank final : knh_bank {
     void* dev_ptrs[] = {d_state, d_sine, d_seg_table, d_delay, d_buffer, d_partials, d_out, d_voices, d_done, d_flags, d_input, d_prog, d_sin_slots, d_fold_count};
     for (void* p : dev_ptrs)
       if (p) (void)hipFree(p);
-    void* host_ptrs[] = {h_ev_start2[0], h_ev_start2[1], h_events2[0], h_events2[1], h_out, h_input, h_done};
+    void* host_ptrs[] = {h_ev_start2[0], h_ev_start2[1], h_events2[0], h_events2[1], h_out, h_input, h_done, h_rs_voices, h_rs_words, h_rs_seg};
     for (void* p : host_ptrs)
       if (p) (void)hipHostFree(p);
     for (hipEvent_t e : list_done)
       if (e) (void)hipEventDestroy(e);
     if (in_copied) (void)hipEventDestroy(in_copied);
+    if (rs_done) (void)hipEventDestroy(rs_done);
     for (auto& p : timing_pool) {
       (void)hipEventDestroy(p.first);
       (void)hipEventDestroy(p.second);
@@ -440,6 +441,256 @@ struct Bank final : knh_bank {
     return KNH_OK;
   }
 
+  // ---- construction: UGen::new + UGen::init of one node ------------------------------------
+  // knh_bank_init runs prepare_stage and then construct_stage for every voice; knh_bank_restart_voices runs construct_stage
+  // again for the voices it names.  This is the one statement of how each stage kind is constructed.
+  bool svf_ic2_neg0 = false;     // KNH_DEBUG_SVF_IC2_NEG0=1 (tests only), read at init
+  std::vector<double> seg_rows;  // segment Envelope: the host's copy of d_seg_table, [voice][seg_max][3]
+  static W fw(F x) { return static_cast<W>(to_bits(x)); }
+  // The ring a delay stage constructed with `a` allocates, in samples (delay.rs:24-31, :107-123).
+  int delay_ring_len(const StageInfo& S, const double* a, uint32_t* out) {
+    const uint32_t sr = sample_rate;
+    if (S.kind == KNH_STAGE_SAMPLE_DELAY) {
+      // Seconds::from_secs_f64 / to_secs_f64 (knaster_primitives/src/time.rs:59-74), then `as usize`
+      const double secs_in = a[0];
+      if (!(secs_in >= 0.0) || secs_in >= 4294967296.0) return fail(KNH_ERR_INVALID_ARGUMENT, "SampleDelay: max delay out of range");
+      const uint32_t whole = static_cast<uint32_t>(std::floor(secs_in));
+      const uint32_t tes = sat_u32((secs_in - std::floor(secs_in)) * 282240000.0);
+      const double secs = static_cast<double>(whole) + static_cast<double>(tes) / 282240000.0;
+      const double nf = secs * static_cast<double>(sr);
+      if (!(nf >= 1.0)) return fail(KNH_ERR_INVALID_ARGUMENT, "SampleDelay: the ring would be empty (the reference divides by zero)");
+      if (nf >= 1073741824.0) return fail(KNH_ERR_INVALID_ARGUMENT, "SampleDelay: max delay too long");
+      *out = static_cast<uint32_t>(nf);
+      return KNH_OK;
+    }
+    const double secs_in = a[0];
+    if (!(secs_in >= 0.0) || secs_in >= 4294967296.0) return fail(KNH_ERR_INVALID_ARGUMENT, "AllpassDelay: max delay out of range");
+    const uint64_t whole = static_cast<uint64_t>(std::floor(secs_in));
+    const uint64_t tes = sat_u32((secs_in - std::floor(secs_in)) * 282240000.0);
+    const uint64_t nsamp = whole * sr + tes * static_cast<uint64_t>(sr) / 282240000ull;  // Seconds::to_samples, time.rs:86-90
+    if (nsamp == 0) return fail(KNH_ERR_INVALID_ARGUMENT, "AllpassDelay: the ring would be empty (the reference takes a remainder by zero)");
+    if (nsamp >= (1ull << 30)) return fail(KNH_ERR_INVALID_ARGUMENT, "AllpassDelay: max delay too long");
+    *out = static_cast<uint32_t>(nsamp);
+    return KNH_OK;
+  }
+  // What does not depend on the voice: the stage's shadows and tables are sized, the chain-wide refusals made.
+  int prepare_stage(size_t si) {
+    const StageInfo& S = stages[si];
+    Shadow& sh = shadow[si];
+    switch (S.kind) {
+      case KNH_STAGE_SIN_WT: sh.a.resize(nv); break;
+      case KNH_STAGE_SVF: sh.a.resize(nv); sh.b.resize(nv); sh.c.resize(nv); sh.ty.resize(nv); break;
+      case KNH_STAGE_MUL_ENV_ASR: case KNH_STAGE_MUL_ENV_AR: sh.a.resize(nv); sh.b.resize(nv); break;
+      case KNH_STAGE_MUL_ENVELOPE: {
+        if (S.n_ctor < 0) return fail(KNH_ERR_INVALID_ARGUMENT, "Envelope stage without constructor arguments");
+        const uint32_t n_max = static_cast<uint32_t>((S.n_ctor - 4) / 2);
+        env_start.assign(nv, 0.0); env_nseg.assign(nv, 0); seg_max = n_max; seg_rows.assign(static_cast<size_t>(nv) * n_max * 3, 0.0);
+      } break;
+      case KNH_STAGE_BUFFER_READER: {
+        if (pool.empty()) return fail(KNH_ERR_INVALID_ARGUMENT, "BufferReader stage without knh_bank_set_buffer or knh_bank_add_buffer");
+        if (S.dcpb > 0) return fail(KNH_ERR_INVALID_ARGUMENT, "BufferReader cannot be wrapped in WrPreciseTiming here");
+        if (reader_at(S, 0) == 0) {  // the chain's first reader: the shadows of all of them, the pool's layout
+          size_t readers = 0;
+          for (const StageInfo& T : stages) readers += T.kind == KNH_STAGE_BUFFER_READER;
+          buf_start.assign(readers * nv, 0.0); buf_dur.assign(readers * nv, 0.0); buf_rate.assign(readers * nv, 0.0);
+          uint64_t off = 0;  // (put_buffer has kept the sum within 32 bits)
+          for (PoolEntry& e : pool) { e.off = static_cast<uint32_t>(off); off += (e.n_frames + 63ull) & ~63ull; }
+        }
+      } break;
+      case KNH_STAGE_INPUT: uses_input = true; break;
+      case KNH_STAGE_ALLPASS_FB_DELAY: case KNH_STAGE_ALLPASS_DELAY: case KNH_STAGE_SAMPLE_DELAY: delay_len.assign(nv, 0u); break;
+      default: break;
+    }
+    return KNH_OK;
+  }
+  // Node `si` of voice v from its constructor arguments `a`: every slot of the stage through put(rel, word) (a slot not put is
+  // zero), the shadows the setters read, the voice's segment rows.
+  template <typename Put>
+  int construct_stage(size_t si, uint32_t v, const double* a, Put&& put) {
+    const StageInfo& S = stages[si];
+    Shadow& sh = shadow[si];
+    const uint32_t sr = sample_rate;
+    const F sr_as_f32 = static_cast<F>(static_cast<float>(sr));  // F::new(sample_rate as f32)
+    switch (S.kind) {
+      case KNH_STAGE_SIN_WT: {  // osc.rs:110-123,142-147
+        F freq = static_cast<F>(a[0]);
+        sh.a[v] = freq;
+        put(0, 0);
+        put(1, 0);
+        put(2, sat_u32(static_cast<double>(freq) * f2pi));
+      } break;
+      case KNH_STAGE_SIN_NUMERIC: {  // osc.rs:231-236,253-261
+        F freq = static_cast<F>(a[0]);
+        put(0, fw(F(0)));
+        put(1, fw(F(0)));
+        put(2, fw(freq / sr_as_f32));
+      } break;
+      case KNH_STAGE_SVF: {  // svf.rs:64-79,134-141
+        double tyd = a[0];
+        uint32_t ty = (tyd >= 0 && tyd <= 8) ? static_cast<uint32_t>(tyd) : 0u;
+        sh.ty[v] = static_cast<uint8_t>(ty);
+        sh.a[v] = static_cast<F>(a[1]); sh.b[v] = static_cast<F>(a[2]); sh.c[v] = static_cast<F>(a[3]);
+        F co[6];
+        svf_coeffs<F>(ty, sh.a[v], sh.b[v], sh.c[v], sr_as_f32, co);
+        put(0, fw(F(0)));
+        put(1, fw(svf_ic2_neg0 && v % 3 == 0 ? F(-0.0) : F(0)));
+        for (int k = 0; k < 6; ++k) put(2 + k, fw(co[k]));
+        if (S.n_slots == 12) {  // a parameter driven at audio rate: the setter runs on the device and needs the other values
+          put(8, fw(sh.a[v])); put(9, fw(sh.b[v])); put(10, fw(sh.c[v]));
+          put(11, ty);
+        }
+      } break;
+      case KNH_STAGE_ONEPOLE_LPF:    // onepole.rs:118-129
+      case KNH_STAGE_ONEPOLE_HPF: {  // onepole.rs:157-167 (b1 = 0 -> exp(0) = 1)
+        F freq = S.kind == KNH_STAGE_ONEPOLE_LPF ? static_cast<F>(a[0]) : F(0);
+        F f = freq / sr_as_f32;
+        F b1 = std::exp(F(-2.0) * Consts<F>::PI * f);
+        F a0 = F(1.0) - b1;
+        put(0, fw(F(0)));
+        put(1, fw(a0));
+        put(2, fw(b1));
+      } break;
+      case KNH_STAGE_MUL_ENV_ASR:
+      case KNH_STAGE_MUL_ENV_AR: {  // envelopes.rs:33-43,135-151 / :187-197,268-284
+        F atk = static_cast<F>(a[0]), rel = static_cast<F>(a[1]);
+        sh.a[v] = atk; sh.b[v] = rel;
+        F ar = atk == F(0) ? F(1) : F(1) / (atk * static_cast<F>(sr));
+        F rr = rel == F(0) ? F(1) : F(1) / (rel * static_cast<F>(sr));
+        put(0, 0);          // Stopped
+        put(1, fw(F(0)));   // t
+        put(2, fw(ar));
+        put(3, fw(rr));
+        put(4, fw(F(1)));   // release_scale
+      } break;
+      case KNH_STAGE_MUL_ENVELOPE: {  // envelopes.rs:373-400 (+ builder methods), init :404-406
+        const uint32_t n_max = static_cast<uint32_t>((S.n_ctor - 4) / 2);
+        uint32_t n_seg = a[3] >= 1 ? static_cast<uint32_t>(a[3]) : 1u;
+        if (n_seg > n_max) n_seg = n_max;
+        env_start[v] = a[0];
+        env_nseg[v] = n_seg;
+        const double dt = a[1] * (1.0 / static_cast<double>(sr));  // time_scale * base_scale
+        auto put2 = [&](int rel, double d) {
+          uint64_t b = to_bits(d);
+          put(rel, static_cast<W>(static_cast<uint32_t>(b)));
+          put(rel + 1, static_cast<W>(static_cast<uint32_t>(b >> 32)));
+        };
+        put(0, 0);  // Stopped
+        put(1, 0);
+        put2(2, 0.0);
+        put2(4, a[0]);  // from_value = start_value
+        put2(6, dt);
+        put(8, n_seg);
+        put(9, a[2] != 0.0 ? 1u : 0u);
+        put(10, v);
+        for (uint32_t k = 0; k < n_max; ++k) {
+          const double dur = a[4 + 2 * k], val = a[5 + 2 * k];
+          double* row = &seg_rows[(static_cast<size_t>(v) * n_max + k) * 3];
+          row[0] = dur; row[1] = 1.0 / dur; row[2] = val;  // EnvelopeSegment::new, envelopes.rs:327-333
+        }
+      } break;
+      case KNH_STAGE_BUFFER_READER: {  // buffer.rs:40-57 (new, start_at), :106-115 (init)
+        reader_construct(S, v, a, [&](int rel, uint32_t word) { put(rel, static_cast<W>(word)); });
+      } break;
+      case KNH_STAGE_PHASOR: {  // osc.rs:181-188 (new), :197-200 (init: step = freq * (1 / sample_rate))
+        const double step = a[0] * (1.0 / static_cast<double>(sr));
+        const uint64_t sb = to_bits(step);
+        put(0, 0);
+        put(1, 0);
+        put(2, static_cast<W>(static_cast<uint32_t>(sb)));
+        put(3, static_cast<W>(static_cast<uint32_t>(sb >> 32)));
+      } break;
+      case KNH_STAGE_SAFETY_LIMITER: break;
+      case KNH_STAGE_INPUT: {
+        if (!(a[0] >= 0.0) || a[0] >= static_cast<double>(desc.in_channels)) return fail(KNH_ERR_INVALID_ARGUMENT, "KNH_STAGE_INPUT: channel is not below knh_bank_desc.in_channels");
+        put(0, static_cast<W>(static_cast<uint32_t>(a[0])));
+      } break;
+      case KNH_STAGE_MATH_ADD: case KNH_STAGE_MATH_SUB: case KNH_STAGE_MATH_MUL: case KNH_STAGE_MATH_DIV: case KNH_STAGE_MATH_POW: break;  // no state
+      case KNH_STAGE_MATH1_CEIL: case KNH_STAGE_MATH1_SQRT: case KNH_STAGE_MATH1_FLOOR: case KNH_STAGE_MATH1_TRUNC: case KNH_STAGE_MATH1_FRACT:
+      case KNH_STAGE_MATH1_EXP: break;  // Math1UGen (math.rs:167-305): no constructor arguments, no state
+      case KNH_STAGE_WHITE_NOISE: case KNH_STAGE_PINK_NOISE: case KNH_STAGE_BROWN_NOISE: {
+        // fastrand::Rng::with_seed(next_randomness_seed()) (noise.rs:34,66,134): the state is the seed
+        const uint64_t seed = a[0] >= 0.0 ? static_cast<uint64_t>(a[0]) : 0u;
+        put(0, static_cast<W>(static_cast<uint32_t>(seed)));
+        put(1, static_cast<W>(static_cast<uint32_t>(seed >> 32)));
+        if (S.kind == KNH_STAGE_BROWN_NOISE) put(2, to_bits(F(0)));
+        if (S.kind == KNH_STAGE_PINK_NOISE) {  // noise.rs:64-75: counter 1, everything else zero
+          put(2, 1u);
+          for (int k = 3; k < 14; ++k) put(k, to_bits(F(0)));
+        }
+      } break;
+      case KNH_STAGE_RANDOM_LIN: {  // noise.rs:172-200: new() draws the first value, init() turns freq into a step and draws the second
+        uint64_t rng = (a[0] >= 0.0 ? static_cast<uint64_t>(a[0]) : 0u) * 94u + 53u;
+        auto draw = [&rng]() {  // fastrand 2.3.0 Rng::f32 (wyrand), restated: voice_stages.hpp NoiseRng
+          rng += 0x2d358dccaa6c78a5ull;
+          const unsigned __int128 t = static_cast<unsigned __int128>(rng) * static_cast<unsigned __int128>(rng ^ 0x8bb84b93962eacc9ull);
+          const uint32_t r = static_cast<uint32_t>(static_cast<uint64_t>(t) ^ static_cast<uint64_t>(t >> 64));
+          const uint32_t bits = 0x3F800000u + (r >> 9);
+          float f;
+          std::memcpy(&f, &bits, 4);
+          return f - 1.0f;
+        };
+        const F first = static_cast<F>(draw());              // current_value: F::new(rng.f32())
+        const F inc = F(1) / static_cast<F>(sr);             // freq_to_phase_inc = F::ONE / F::from(sample_rate)
+        const F step = static_cast<F>(a[1]) * inc;           // phase_step *= freq_to_phase_inc
+        const F old_target = first + F(0);                   // new_value(): current_value + current_change_width
+        const F second = static_cast<F>(draw());
+        put(0, static_cast<W>(static_cast<uint32_t>(rng)));
+        put(1, static_cast<W>(static_cast<uint32_t>(rng >> 32)));
+        put(2, to_bits(old_target));
+        put(3, to_bits(static_cast<F>(second - old_target)));
+        put(4, to_bits(F(0)));
+        put(5, to_bits(step));
+      } break;
+      case KNH_STAGE_POLYBLEP: {  // polyblep.rs:136-153: new(waveform, freq), init -> set_freq: dt = freq / sample_rate
+        const F srf = static_cast<F>(sr);  // F::from(sample_rate)
+        const F freq = static_cast<F>(a[1]);
+        const F dt = freq != F(0) ? freq / srf : F(0);
+        const uint64_t wf = a[0] >= 0.0 && a[0] < 14.0 ? static_cast<uint64_t>(a[0]) : 0u;
+        put(0, fw(F(0)));
+        put(1, fw(dt));
+        put(2, fw(F(0.5)));
+        put(3, static_cast<W>(wf));
+        put(4, (dt * srf >= srf / F(4)) ? 1u : 0u);  // get_freq_in_hz() >= sample_rate / 4, :210
+      } break;
+      case KNH_STAGE_ALLPASS_FB_DELAY:  // delay.rs:221-229: an AllpassDelay and feedback = 0
+      case KNH_STAGE_ALLPASS_DELAY: {  // delay.rs:107-123: buffer = max_delay_seconds.to_samples(sample_rate) zeros
+        uint32_t nsamp = 0;
+        { int rc = delay_ring_len(S, a, &nsamp); if (rc != KNH_OK) return rc; }
+        delay_len[v] = nsamp;
+        put(0, 0);  // write_frame
+        put(1, 0);  // read_frame
+        put(2, static_cast<W>(nsamp));
+        put(3, v);
+        put(4, fw(F(1)));  // AllpassInterpolator::new: coeff, prev_input, prev_output all ONE (:61-67)
+        put(5, fw(F(1)));
+        put(6, fw(F(1)));
+        if (S.kind == KNH_STAGE_ALLPASS_FB_DELAY) put(7, fw(F(0)));
+      } break;
+      case KNH_STAGE_SAMPLE_DELAY: {  // delay.rs:24-31 (new), :45-49 (init)
+        uint32_t len = 0;
+        { int rc = delay_ring_len(S, a, &len); if (rc != KNH_OK) return rc; }
+        delay_len[v] = len;
+        put(0, 0);    // write_position
+        put(1, len);  // len - delay_samples, delay_samples = 0
+        put(2, len);
+        put(3, v);
+      } break;
+      case KNH_STAGE_WR_POWI:  // WrPowi::new(ugen, value: i32), wrappers_core/math.rs:591-595
+        put(0, static_cast<W>(static_cast<uint32_t>(static_cast<int32_t>(a[0]))));
+        break;
+      case KNH_STAGE_PAN2: {  // Pan2::new(pan: f32), pan.rs:18-23; the gains of process(), :33-35, as F::new(..)
+        float gl, gr;
+        pan2_gains(static_cast<float>(a[0]), &gl, &gr);
+        put(0, fw(static_cast<F>(gl)));
+        put(1, fw(static_cast<F>(gr)));
+      } break;
+      default:  // Constant / wrapper value: util.rs:43-45, wrappers_core/math.rs:21-23
+        put(0, fw(static_cast<F>(a[0])));
+        break;
+    }
+    return KNH_OK;
+  }
+
   // ---- UGen::init for every node of every voice --------------------------------------
   int init(uint32_t sr, size_t bs) override {
     if (initialised) return fail(KNH_ERR_INVALID_ARGUMENT, "already initialised");
@@ -523,230 +774,21 @@ struct Bank final : knh_bank {
     stride = (static_cast<long>(nv) + 63) / 64 * 64;
     // osc.rs:144-145
     f2pi = 16384.0 * 65536.0 * (1.0 / static_cast<double>(sr));
-    const F sr_as_f32 = static_cast<F>(static_cast<float>(sr));  // F::new(sample_rate as f32)
 
     std::vector<W> st(static_cast<size_t>(n_slots) * stride, W(0));
-    std::vector<double> seg_rows;
-    auto slot = [&](int s, uint32_t v) -> W& { return st[static_cast<size_t>(s) * stride + v]; };
-    auto fw = [](F x) { return static_cast<W>(to_bits(x)); };
     shadow.assign(stages.size(), Shadow{});
     // KNH_DEBUG_SVF_IC2_NEG0=1, tests only: every third voice's SvfFilter starts with ic2eq = -0.0, the one state no call of the
     // reference can produce and the one in which the low-pass tiles must take the general step (Svf::low_pass)
     const char* const neg0_env = std::getenv("KNH_DEBUG_SVF_IC2_NEG0");
-    const bool svf_ic2_neg0 = neg0_env && neg0_env[0] == '1';
+    svf_ic2_neg0 = neg0_env && neg0_env[0] == '1';
     for (size_t si = 0; si < stages.size(); ++si) {
       const StageInfo& S = stages[si];
       const double* ca = ctor[si].data();
-      Shadow& sh = shadow[si];
+      { int rc = prepare_stage(si); if (rc != KNH_OK) return rc; }
       for (uint32_t v = 0; v < nv; ++v) {
-        const double* a = ca + static_cast<size_t>(v) * S.n_ctor;
-        switch (S.kind) {
-          case KNH_STAGE_SIN_WT: {  // osc.rs:110-123,142-147
-            if (v == 0) sh.a.resize(nv);
-            F freq = static_cast<F>(a[0]);
-            sh.a[v] = freq;
-            slot(S.slot_base + 0, v) = 0;
-            slot(S.slot_base + 1, v) = 0;
-            slot(S.slot_base + 2, v) = sat_u32(static_cast<double>(freq) * f2pi);
-          } break;
-          case KNH_STAGE_SIN_NUMERIC: {  // osc.rs:231-236,253-261
-            F freq = static_cast<F>(a[0]);
-            slot(S.slot_base + 0, v) = fw(F(0));
-            slot(S.slot_base + 1, v) = fw(F(0));
-            slot(S.slot_base + 2, v) = fw(freq / sr_as_f32);
-          } break;
-          case KNH_STAGE_SVF: {  // svf.rs:64-79,134-141
-            if (v == 0) { sh.a.resize(nv); sh.b.resize(nv); sh.c.resize(nv); sh.ty.resize(nv); }
-            double tyd = a[0];
-            uint32_t ty = (tyd >= 0 && tyd <= 8) ? static_cast<uint32_t>(tyd) : 0u;
-            sh.ty[v] = static_cast<uint8_t>(ty);
-            sh.a[v] = static_cast<F>(a[1]); sh.b[v] = static_cast<F>(a[2]); sh.c[v] = static_cast<F>(a[3]);
-            F co[6];
-            svf_coeffs<F>(ty, sh.a[v], sh.b[v], sh.c[v], sr_as_f32, co);
-            slot(S.slot_base + 0, v) = fw(F(0));
-            slot(S.slot_base + 1, v) = fw(svf_ic2_neg0 && v % 3 == 0 ? F(-0.0) : F(0));
-            for (int k = 0; k < 6; ++k) slot(S.slot_base + 2 + k, v) = fw(co[k]);
-            if (S.n_slots == 12) {  // a parameter driven at audio rate: the setter runs on the device and needs the other values
-              slot(S.slot_base + 8, v) = fw(sh.a[v]); slot(S.slot_base + 9, v) = fw(sh.b[v]); slot(S.slot_base + 10, v) = fw(sh.c[v]);
-              slot(S.slot_base + 11, v) = ty;
-            }
-          } break;
-          case KNH_STAGE_ONEPOLE_LPF:    // onepole.rs:118-129
-          case KNH_STAGE_ONEPOLE_HPF: {  // onepole.rs:157-167 (b1 = 0 -> exp(0) = 1)
-            F freq = S.kind == KNH_STAGE_ONEPOLE_LPF ? static_cast<F>(a[0]) : F(0);
-            F f = freq / sr_as_f32;
-            F b1 = std::exp(F(-2.0) * Consts<F>::PI * f);
-            F a0 = F(1.0) - b1;
-            slot(S.slot_base + 0, v) = fw(F(0));
-            slot(S.slot_base + 1, v) = fw(a0);
-            slot(S.slot_base + 2, v) = fw(b1);
-          } break;
-          case KNH_STAGE_MUL_ENV_ASR:
-          case KNH_STAGE_MUL_ENV_AR: {  // envelopes.rs:33-43,135-151 / :187-197,268-284
-            if (v == 0) { sh.a.resize(nv); sh.b.resize(nv); }
-            F atk = static_cast<F>(a[0]), rel = static_cast<F>(a[1]);
-            sh.a[v] = atk; sh.b[v] = rel;
-            F ar = atk == F(0) ? F(1) : F(1) / (atk * static_cast<F>(sr));
-            F rr = rel == F(0) ? F(1) : F(1) / (rel * static_cast<F>(sr));
-            slot(S.slot_base + 0, v) = 0;          // Stopped
-            slot(S.slot_base + 1, v) = fw(F(0));   // t
-            slot(S.slot_base + 2, v) = fw(ar);
-            slot(S.slot_base + 3, v) = fw(rr);
-            slot(S.slot_base + 4, v) = fw(F(1));   // release_scale
-          } break;
-          case KNH_STAGE_MUL_ENVELOPE: {  // envelopes.rs:373-400 (+ builder methods), init :404-406
-            if (S.n_ctor < 0) return fail(KNH_ERR_INVALID_ARGUMENT, "Envelope stage without constructor arguments");
-            const uint32_t n_max = static_cast<uint32_t>((S.n_ctor - 4) / 2);
-            if (v == 0) { env_start.assign(nv, 0.0); env_nseg.assign(nv, 0); seg_max = n_max; seg_rows.assign(static_cast<size_t>(nv) * n_max * 3, 0.0); }
-            uint32_t n_seg = a[3] >= 1 ? static_cast<uint32_t>(a[3]) : 1u;
-            if (n_seg > n_max) n_seg = n_max;
-            env_start[v] = a[0];
-            env_nseg[v] = n_seg;
-            const double dt = a[1] * (1.0 / static_cast<double>(sr));  // time_scale * base_scale
-            auto put2 = [&](int rel, double d) {
-              uint64_t b = to_bits(d);
-              slot(S.slot_base + rel, v) = static_cast<W>(static_cast<uint32_t>(b));
-              slot(S.slot_base + rel + 1, v) = static_cast<W>(static_cast<uint32_t>(b >> 32));
-            };
-            slot(S.slot_base + 0, v) = 0;  // Stopped
-            slot(S.slot_base + 1, v) = 0;
-            put2(2, 0.0);
-            put2(4, a[0]);  // from_value = start_value
-            put2(6, dt);
-            slot(S.slot_base + 8, v) = n_seg;
-            slot(S.slot_base + 9, v) = a[2] != 0.0 ? 1u : 0u;
-            slot(S.slot_base + 10, v) = v;
-            for (uint32_t k = 0; k < n_max; ++k) {
-              const double dur = a[4 + 2 * k], val = a[5 + 2 * k];
-              double* row = &seg_rows[(static_cast<size_t>(v) * n_max + k) * 3];
-              row[0] = dur; row[1] = 1.0 / dur; row[2] = val;  // EnvelopeSegment::new, envelopes.rs:327-333
-            }
-          } break;
-          case KNH_STAGE_BUFFER_READER: {  // buffer.rs:40-57 (new, start_at), :106-115 (init)
-            if (pool.empty()) return fail(KNH_ERR_INVALID_ARGUMENT, "BufferReader stage without knh_bank_set_buffer or knh_bank_add_buffer");
-            if (S.dcpb > 0) return fail(KNH_ERR_INVALID_ARGUMENT, "BufferReader cannot be wrapped in WrPreciseTiming here");
-            if (v == 0 && reader_at(S, 0) == 0) {  // the chain's first reader: the shadows of all of them, the pool's layout
-              size_t readers = 0;
-              for (const StageInfo& T : stages) readers += T.kind == KNH_STAGE_BUFFER_READER;
-              buf_start.assign(readers * nv, 0.0); buf_dur.assign(readers * nv, 0.0); buf_rate.assign(readers * nv, 0.0);
-              uint64_t off = 0;  // (put_buffer has kept the sum within 32 bits)
-              for (PoolEntry& e : pool) { e.off = static_cast<uint32_t>(off); off += (e.n_frames + 63ull) & ~63ull; }
-            }
-            reader_construct(S, v, a, [&](int rel, uint32_t word) { slot(S.slot_base + rel, v) = static_cast<W>(word); });
-          } break;
-          case KNH_STAGE_PHASOR: {  // osc.rs:181-188 (new), :197-200 (init: step = freq * (1 / sample_rate))
-            const double step = a[0] * (1.0 / static_cast<double>(sr));
-            const uint64_t sb = to_bits(step);
-            slot(S.slot_base + 0, v) = 0;
-            slot(S.slot_base + 1, v) = 0;
-            slot(S.slot_base + 2, v) = static_cast<W>(static_cast<uint32_t>(sb));
-            slot(S.slot_base + 3, v) = static_cast<W>(static_cast<uint32_t>(sb >> 32));
-          } break;
-          case KNH_STAGE_SAFETY_LIMITER: break;
-          case KNH_STAGE_INPUT: {
-            uses_input = true;
-            if (!(a[0] >= 0.0) || a[0] >= static_cast<double>(desc.in_channels)) return fail(KNH_ERR_INVALID_ARGUMENT, "KNH_STAGE_INPUT: channel is not below knh_bank_desc.in_channels");
-            slot(S.slot_base, v) = static_cast<W>(static_cast<uint32_t>(a[0]));
-          } break;
-          case KNH_STAGE_MATH_ADD: case KNH_STAGE_MATH_SUB: case KNH_STAGE_MATH_MUL: case KNH_STAGE_MATH_DIV: case KNH_STAGE_MATH_POW: break;  // no state
-          case KNH_STAGE_MATH1_CEIL: case KNH_STAGE_MATH1_SQRT: case KNH_STAGE_MATH1_FLOOR: case KNH_STAGE_MATH1_TRUNC: case KNH_STAGE_MATH1_FRACT:
-          case KNH_STAGE_MATH1_EXP: break;  // Math1UGen (math.rs:167-305): no constructor arguments, no state
-          case KNH_STAGE_WHITE_NOISE: case KNH_STAGE_PINK_NOISE: case KNH_STAGE_BROWN_NOISE: {
-            // fastrand::Rng::with_seed(next_randomness_seed()) (noise.rs:34,66,134): the state is the seed
-            const uint64_t seed = a[0] >= 0.0 ? static_cast<uint64_t>(a[0]) : 0u;
-            slot(S.slot_base + 0, v) = static_cast<W>(static_cast<uint32_t>(seed));
-            slot(S.slot_base + 1, v) = static_cast<W>(static_cast<uint32_t>(seed >> 32));
-            if (S.kind == KNH_STAGE_BROWN_NOISE) slot(S.slot_base + 2, v) = to_bits(F(0));
-            if (S.kind == KNH_STAGE_PINK_NOISE) {  // noise.rs:64-75: counter 1, everything else zero
-              slot(S.slot_base + 2, v) = 1u;
-              for (int k = 3; k < 14; ++k) slot(S.slot_base + k, v) = to_bits(F(0));
-            }
-          } break;
-          case KNH_STAGE_RANDOM_LIN: {  // noise.rs:172-200: new() draws the first value, init() turns freq into a step and draws the second
-            uint64_t rng = (a[0] >= 0.0 ? static_cast<uint64_t>(a[0]) : 0u) * 94u + 53u;
-            auto draw = [&rng]() {  // fastrand 2.3.0 Rng::f32 (wyrand), restated: voice_stages.hpp NoiseRng
-              rng += 0x2d358dccaa6c78a5ull;
-              const unsigned __int128 t = static_cast<unsigned __int128>(rng) * static_cast<unsigned __int128>(rng ^ 0x8bb84b93962eacc9ull);
-              const uint32_t r = static_cast<uint32_t>(static_cast<uint64_t>(t) ^ static_cast<uint64_t>(t >> 64));
-              const uint32_t bits = 0x3F800000u + (r >> 9);
-              float f;
-              std::memcpy(&f, &bits, 4);
-              return f - 1.0f;
-            };
-            const F first = static_cast<F>(draw());              // current_value: F::new(rng.f32())
-            const F inc = F(1) / static_cast<F>(sr);             // freq_to_phase_inc = F::ONE / F::from(sample_rate)
-            const F step = static_cast<F>(a[1]) * inc;           // phase_step *= freq_to_phase_inc
-            const F old_target = first + F(0);                   // new_value(): current_value + current_change_width
-            const F second = static_cast<F>(draw());
-            slot(S.slot_base + 0, v) = static_cast<W>(static_cast<uint32_t>(rng));
-            slot(S.slot_base + 1, v) = static_cast<W>(static_cast<uint32_t>(rng >> 32));
-            slot(S.slot_base + 2, v) = to_bits(old_target);
-            slot(S.slot_base + 3, v) = to_bits(static_cast<F>(second - old_target));
-            slot(S.slot_base + 4, v) = to_bits(F(0));
-            slot(S.slot_base + 5, v) = to_bits(step);
-          } break;
-          case KNH_STAGE_POLYBLEP: {  // polyblep.rs:136-153: new(waveform, freq), init -> set_freq: dt = freq / sample_rate
-            const F srf = static_cast<F>(sr);  // F::from(sample_rate)
-            const F freq = static_cast<F>(a[1]);
-            const F dt = freq != F(0) ? freq / srf : F(0);
-            const uint64_t wf = a[0] >= 0.0 && a[0] < 14.0 ? static_cast<uint64_t>(a[0]) : 0u;
-            slot(S.slot_base + 0, v) = fw(F(0));
-            slot(S.slot_base + 1, v) = fw(dt);
-            slot(S.slot_base + 2, v) = fw(F(0.5));
-            slot(S.slot_base + 3, v) = static_cast<W>(wf);
-            slot(S.slot_base + 4, v) = (dt * srf >= srf / F(4)) ? 1u : 0u;  // get_freq_in_hz() >= sample_rate / 4, :210
-          } break;
-          case KNH_STAGE_ALLPASS_FB_DELAY:  // delay.rs:221-229: an AllpassDelay and feedback = 0
-          case KNH_STAGE_ALLPASS_DELAY: {  // delay.rs:107-123: buffer = max_delay_seconds.to_samples(sample_rate) zeros
-            if (v == 0) delay_len.assign(nv, 0u);
-            const double secs_in = a[0];
-            if (!(secs_in >= 0.0) || secs_in >= 4294967296.0) return fail(KNH_ERR_INVALID_ARGUMENT, "AllpassDelay: max delay out of range");
-            const uint64_t whole = static_cast<uint64_t>(std::floor(secs_in));
-            const uint64_t tes = sat_u32((secs_in - std::floor(secs_in)) * 282240000.0);
-            const uint64_t nsamp = whole * sr + tes * static_cast<uint64_t>(sr) / 282240000ull;  // Seconds::to_samples, time.rs:86-90
-            if (nsamp == 0) return fail(KNH_ERR_INVALID_ARGUMENT, "AllpassDelay: the ring would be empty (the reference takes a remainder by zero)");
-            if (nsamp >= (1ull << 30)) return fail(KNH_ERR_INVALID_ARGUMENT, "AllpassDelay: max delay too long");
-            delay_len[v] = static_cast<uint32_t>(nsamp);
-            slot(S.slot_base + 0, v) = 0;  // write_frame
-            slot(S.slot_base + 1, v) = 0;  // read_frame
-            slot(S.slot_base + 2, v) = static_cast<W>(nsamp);
-            slot(S.slot_base + 3, v) = v;
-            slot(S.slot_base + 4, v) = fw(F(1));  // AllpassInterpolator::new: coeff, prev_input, prev_output all ONE (:61-67)
-            slot(S.slot_base + 5, v) = fw(F(1));
-            slot(S.slot_base + 6, v) = fw(F(1));
-            if (S.kind == KNH_STAGE_ALLPASS_FB_DELAY) slot(S.slot_base + 7, v) = fw(F(0));
-          } break;
-          case KNH_STAGE_SAMPLE_DELAY: {  // delay.rs:24-31 (new), :45-49 (init)
-            if (v == 0) delay_len.assign(nv, 0u);
-            // Seconds::from_secs_f64 / to_secs_f64 (knaster_primitives/src/time.rs:59-74), then `as usize`
-            const double secs_in = a[0];
-            if (!(secs_in >= 0.0) || secs_in >= 4294967296.0) return fail(KNH_ERR_INVALID_ARGUMENT, "SampleDelay: max delay out of range");
-            const uint32_t whole = static_cast<uint32_t>(std::floor(secs_in));
-            const uint32_t tes = sat_u32((secs_in - std::floor(secs_in)) * 282240000.0);
-            const double secs = static_cast<double>(whole) + static_cast<double>(tes) / 282240000.0;
-            const double nf = secs * static_cast<double>(sr);
-            if (!(nf >= 1.0)) return fail(KNH_ERR_INVALID_ARGUMENT, "SampleDelay: the ring would be empty (the reference divides by zero)");
-            if (nf >= 1073741824.0) return fail(KNH_ERR_INVALID_ARGUMENT, "SampleDelay: max delay too long");
-            const uint32_t len = static_cast<uint32_t>(nf);
-            delay_len[v] = len;
-            slot(S.slot_base + 0, v) = 0;    // write_position
-            slot(S.slot_base + 1, v) = len;  // len - delay_samples, delay_samples = 0
-            slot(S.slot_base + 2, v) = len;
-            slot(S.slot_base + 3, v) = v;
-          } break;
-          case KNH_STAGE_WR_POWI:  // WrPowi::new(ugen, value: i32), wrappers_core/math.rs:591-595
-            slot(S.slot_base, v) = static_cast<W>(static_cast<uint32_t>(static_cast<int32_t>(a[0])));
-            break;
-          case KNH_STAGE_PAN2: {  // Pan2::new(pan: f32), pan.rs:18-23; the gains of process(), :33-35, as F::new(..)
-            float gl, gr;
-            pan2_gains(static_cast<float>(a[0]), &gl, &gr);
-            slot(S.slot_base + 0, v) = fw(static_cast<F>(gl));
-            slot(S.slot_base + 1, v) = fw(static_cast<F>(gr));
-          } break;
-          default:  // Constant / wrapper value: util.rs:43-45, wrappers_core/math.rs:21-23
-            slot(S.slot_base, v) = fw(static_cast<F>(a[0]));
-            break;
-        }
+        int rc = construct_stage(si, v, ca + static_cast<size_t>(v) * S.n_ctor,
+                                 [&](int rel, W word) { st[static_cast<size_t>(S.slot_base + rel) * stride + v] = word; });
+        if (rc != KNH_OK) return rc;
       }
     }
     // device allocations
@@ -888,6 +930,157 @@ struct Bank final : knh_bank {
   hipError_t ensure_voices() {
     if (d_voices) return hipSuccess;
     return hipMalloc(&d_voices, static_cast<size_t>(fold_planes) * nv * block_size * sizeof(F));
+  }
+
+  // ---- restarting voices ---------------------------------------------------------------
+  // knh_bank_restart_voices: what the reference has after a voice's nodes are freed (graph.rs:2483-2513) and the same chain is
+  // pushed and initialised again.  The host runs the construction again at the call (construct_stage: the shadows the setters
+  // read are the new nodes' from then on) and keeps the voices' rows; the next launch -- or whatever reads the state first --
+  // puts them on the device, in front of its voice kernel on its stream (restart_voices_kernel, kernels_restart.hip).
+  bool mid_block = false;             // the last process call ended inside a block
+  std::vector<uint8_t> rs_mark;       // [voice]: named by the call being made
+  std::vector<int32_t> rs_row;        // [voice] -> its row among those waiting, -1: none
+  std::vector<uint32_t> rs_voices;    // the rows waiting for the device: voice, state words, segment rows
+  std::vector<W> rs_words;
+  std::vector<double> rs_seg;
+  uint32_t* h_rs_voices = nullptr;    // pinned: what the kernel reads
+  W* h_rs_words = nullptr;
+  double* h_rs_seg = nullptr;
+  size_t h_rs_cap = 0;                // rows
+  hipEvent_t rs_done = nullptr;       // behind the last restart kernel
+  bool rs_busy = false;
+  int set_voice_ctor(uint32_t stage, size_t count, const uint32_t* voices, const double* args, uint32_t n_args, bool keep) override {
+    if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
+    if (stage >= stages.size()) return fail(KNH_ERR_OUT_OF_RANGE, "stage out of range");
+    const StageInfo& S = stages[stage];
+    if (static_cast<int>(n_args) != S.n_ctor) return fail(KNH_ERR_INVALID_ARGUMENT, "wrong number of constructor arguments");
+    if (count && (!voices || (n_args && !args))) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
+    for (size_t k = 0; k < count; ++k)
+      if (voices[k] >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
+    if (mid_block) return fail(KNH_ERR_INVALID_ARGUMENT, "a block is partly processed: voices restart between blocks");
+    for (size_t k = 0; k < count; ++k) {  // what knh_bank_init would refuse, and a ring the allocation made at init cannot hold
+      const double* a = args + k * n_args;
+      if (S.kind == KNH_STAGE_SAMPLE_DELAY || S.kind == KNH_STAGE_ALLPASS_DELAY || S.kind == KNH_STAGE_ALLPASS_FB_DELAY) {
+        uint32_t len = 0;
+        int rc = delay_ring_len(S, a, &len);
+        if (rc != KNH_OK) return rc;
+        if (len > delay_stride) return fail(KNH_ERR_OUT_OF_RANGE, "the delay's ring would be longer than the rings allocated at knh_bank_init");
+      }
+      if (S.kind == KNH_STAGE_INPUT && (!(a[0] >= 0.0) || a[0] >= static_cast<double>(desc.in_channels)))
+        return fail(KNH_ERR_INVALID_ARGUMENT, "KNH_STAGE_INPUT: channel is not below knh_bank_desc.in_channels");
+    }
+    for (size_t k = 0; k < count && n_args && keep; ++k)
+      std::copy(args + k * n_args, args + (k + 1) * n_args, ctor[stage].begin() + static_cast<size_t>(voices[k]) * n_args);
+    return KNH_OK;
+  }
+  // Everything already said to the nodes of the marked voices is dropped -- patches of the coming launch and of later ones,
+  // calls kept for later blocks, records and changes waiting in a WrPreciseTiming queue, ramps of WrSmoothParams -- and the
+  // wrappers' host state is a new node's: they addressed nodes that no longer exist.
+  void forget_voices(const std::vector<uint8_t>& marked, const std::vector<uint32_t>& list) {
+    expand_ranges();
+    auto drop = [&](auto& vec, auto&& voice_of) {
+      vec.erase(std::remove_if(vec.begin(), vec.end(), [&](const auto& x) { return marked[voice_of(x)] != 0; }), vec.end());
+    };
+    drop(pending, [](const HostEvent& e) { return e.voice; });
+    for (auto& calls : future) drop(calls, [](const Call& c) { return c.voice; });
+    for (auto& recs : qfuture) drop(recs, [](const QRec& r) { return r.voice; });
+    const uint64_t ns = stages.size();
+    drop(queued, [ns](const std::pair<uint64_t, QueuedChange>& q) { return static_cast<uint32_t>(q.first / ns); });
+    drop(smooth_active, [ns](uint64_t key) { return static_cast<uint32_t>(key / ns); });
+    if (resolver.active()) resolver.drop_voices(marked);
+    for (uint32_t v : list) {
+      for (size_t si = 0; si < stages.size(); ++si) {
+        const StageInfo& S = stages[si];
+        if (!smooth[si].empty()) {
+          std::fill_n(smooth[si].begin() + static_cast<size_t>(v) * S.n_params, S.n_params, SmoothState{});
+          smooth_mark[si][v] = 0u;
+        }
+        if (S.dcpb > 0 && !next_delay.empty())
+          for (int p = 0; p < S.n_params; ++p) next_delay[static_cast<size_t>(S.param_base + p) * nv + v] = 0;
+      }
+      for (uint32_t w = 0; w < n_wrapped; ++w) node_q[static_cast<size_t>(v) * n_wrapped + w] = NodeQ{0u, 0, 0, 0};
+    }
+  }
+  int restart_voices(size_t count, const uint32_t* voices) override {
+    if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
+    if (count && !voices) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
+    for (size_t k = 0; k < count; ++k)
+      if (voices[k] >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
+    if (mid_block) return fail(KNH_ERR_INVALID_ARGUMENT, "a block is partly processed: voices restart between blocks");
+    if (count == 0) return KNH_OK;
+    { int rl = resident.leave(); if (rl != KNH_OK) return rl; }  // (a resident kernel holds the voices' state in its registers)
+    rs_mark.assign(nv, 0);
+    if (rs_row.empty()) rs_row.assign(nv, -1);
+    std::vector<uint32_t> list;  // each voice once
+    for (size_t k = 0; k < count; ++k)
+      if (!rs_mark[voices[k]]) { rs_mark[voices[k]] = 1; list.push_back(voices[k]); }
+    forget_voices(rs_mark, list);
+    const size_t n_seg = static_cast<size_t>(seg_max) * 3u;
+    for (uint32_t v : list) {
+      if (rs_row[v] < 0) {  // (restarted twice between two launches: the later construction stands)
+        rs_row[v] = static_cast<int32_t>(rs_voices.size());
+        rs_voices.push_back(v);
+        rs_words.resize(rs_voices.size() * static_cast<size_t>(n_slots));
+        rs_seg.resize(rs_voices.size() * n_seg);
+      }
+      W* row = rs_words.data() + static_cast<size_t>(rs_row[v]) * n_slots;
+      std::fill_n(row, n_slots, W(0));
+      for (size_t si = 0; si < stages.size(); ++si) {
+        const StageInfo& S = stages[si];
+        int rc = construct_stage(si, v, ctor[si].data() + static_cast<size_t>(v) * (S.n_ctor > 0 ? S.n_ctor : 0),
+                                 [&](int rel, W word) { row[S.slot_base + rel] = word; });
+        if (rc != KNH_OK) return rc;  // (not reached: the arguments were checked when they were given)
+      }
+      if (n_seg) std::copy_n(seg_rows.begin() + static_cast<size_t>(v) * n_seg, n_seg, rs_seg.begin() + static_cast<size_t>(rs_row[v]) * n_seg);
+    }
+    return KNH_OK;
+  }
+  // The rows that wait go to the device on `s`, the stream of what reads the state next.
+  int flush_restart(hipStream_t s) {
+    if (rs_voices.empty()) return KNH_OK;
+    const size_t n = rs_voices.size(), n_seg = static_cast<size_t>(seg_max) * 3u;
+    if (flags_stream_set && flags_stream != s) KNH_HIP(hipStreamSynchronize(flags_stream));  // the launch before wrote the state in that stream's order
+    if (!rs_done) KNH_HIP(hipEventCreateWithFlags(&rs_done, hipEventDisableTiming));
+    if (rs_busy) { KNH_HIP(hipEventSynchronize(rs_done)); rs_busy = false; }  // the kernel of the restart before reads the pinned rows
+    if (n > h_rs_cap) {
+      void* old[] = {h_rs_voices, h_rs_words, h_rs_seg};
+      for (void* p : old)
+        if (p) KNH_HIP(hipHostFree(p));
+      h_rs_voices = nullptr; h_rs_words = nullptr; h_rs_seg = nullptr;
+      h_rs_cap = 0;
+      const size_t cap = std::max<size_t>(n, 64);
+      KNH_HIP(hipHostMalloc(&h_rs_voices, cap * sizeof(uint32_t)));
+      KNH_HIP(hipHostMalloc(&h_rs_words, std::max<size_t>(cap * static_cast<size_t>(n_slots), 1) * sizeof(W)));
+      if (n_seg) KNH_HIP(hipHostMalloc(&h_rs_seg, cap * n_seg * sizeof(double)));
+      h_rs_cap = cap;
+    }
+    std::copy(rs_voices.begin(), rs_voices.end(), h_rs_voices);
+    std::copy(rs_words.begin(), rs_words.end(), h_rs_words);
+    if (n_seg) std::copy(rs_seg.begin(), rs_seg.end(), h_rs_seg);
+    knh_dev::RestartArgs ra{};
+    ra.voices = h_rs_voices;
+    ra.words = h_rs_words;
+    ra.seg_rows = h_rs_seg;
+    ra.state = d_state;
+    ra.stride = stride;
+    ra.n_slots = static_cast<uint32_t>(n_slots);
+    ra.n_voices = nv;
+    ra.f64 = sizeof(F) == 8 ? 1u : 0u;
+    ra.done_frames = d_done;
+    ra.armed = resolver.active() ? resolver.armed() : nullptr;
+    ra.n_params_total = static_cast<uint32_t>(n_params_total);
+    ra.seg_table = n_seg ? d_seg_table : nullptr;
+    ra.seg_max = seg_max;
+    ra.delay_ring = d_delay;
+    ra.delay_stride = delay_stride;
+    if (resolver.active()) { int rc = resolver.restart_may_write(s); if (rc != KNH_OK) return rc; }
+    KNH_HIP(knh::launch_restart_voices(ra, static_cast<unsigned>(n), s));
+    KNH_HIP(hipEventRecord(rs_done, s));
+    rs_busy = true;
+    if (resolver.active()) { int rc = resolver.restart_written(rs_done); if (rc != KNH_OK) return rc; }
+    for (uint32_t v : rs_voices) rs_row[v] = -1;
+    rs_voices.clear(); rs_words.clear(); rs_seg.clear();
+    return KNH_OK;
   }
 
   // ---- parameter changes ----------------------------------------------------------------
@@ -1669,6 +1862,8 @@ struct Bank final : knh_bank {
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : own_stream;
     if (resolver.take_overflow()) warn("Not enough space for scheduled changes in WrPreciseTiming, change ignored");
     const uint32_t fb = static_cast<uint32_t>(offset), fe = static_cast<uint32_t>(offset + ftp);
+    { int rr = flush_restart(s); if (rr != KNH_OK) return rr; }  // voices restarted since the last launch: their new state first
+    mid_block = fe < block_size;
     // Assemble the launch's state patches block by block, in the order the reference would apply them.
     for (uint32_t b = 0; b < n_blocks; ++b) {
       frame_base = b * static_cast<uint32_t>(block_size);
@@ -1924,6 +2119,7 @@ struct Bank final : knh_bank {
     if (!out) return fail(KNH_ERR_INVALID_ARGUMENT, "null output");
     { int rl = resident.leave(); if (rl != KNH_OK) return rl; }  // (a resident kernel's stores reach the copy engine when it ends)
     KNH_HIP(hipSetDevice(device));
+    { int rr = flush_restart(own_stream); if (rr != KNH_OK) return rr; }  // (restarted voices have no done frame)
     KNH_HIP(hipStreamSynchronize(own_stream));
     KNH_HIP(hipMemcpy(out, d_done, static_cast<size_t>(nv) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return KNH_OK;
