@@ -165,6 +165,8 @@ unsafe extern "C" {
     pub fn knh_bank_set_voice_ctor_args(bank: *mut knh_bank, stage: u32, count: usize, voices: *const u32, args: *const f64, n_args: u32) -> i32;
     pub fn knh_bank_restart_voices(bank: *mut knh_bank, count: usize, voices: *const u32) -> i32;
     pub fn knh_bank_buffer_count(bank: *const knh_bank, stage: u32) -> u32;
+    pub fn knh_bank_connect_outputs(bank: *mut knh_bank, n_channels: u32, stages: *const u32) -> i32;
+    pub fn knh_bank_output_stage(bank: *const knh_bank, channel: u32) -> u32;
     pub fn knh_bank_init(bank: *mut knh_bank, sample_rate: u32, block_size: usize) -> i32;
     pub fn knh_bank_destroy(bank: *mut knh_bank);
     pub fn knh_bank_inputs(bank: *const knh_bank) -> u16;

@@ -276,6 +276,19 @@ impl<F: Float, I: Size> GpuVoiceBank<F, I> {
     pub fn buffer_count(&self, stage: usize) -> u32 {
         unsafe { knh_bank_buffer_count(self.h, stage as u32) }
     }
+    /// Graph output 0 carries the signal of stage `left`'s node, output 1 that of stage `right`'s: what
+    /// `l.to_graph_out_channels([0]); r.to_graph_out_channels([1])` connects.  Before the bank is pushed; naming the last
+    /// stage twice restores the voice with one signal.
+    pub fn connect_outputs(&mut self, left: usize, right: usize) -> Result<(), BankError> {
+        let stages = [left as u32, right as u32];
+        let rc = unsafe { knh_bank_connect_outputs(self.h, 2, stages.as_ptr()) };
+        if rc != KNH_OK { Err(last_error(self.h)) } else { Ok(()) }
+    }
+    /// The stage (its node's output) graph output `channel` carries; `None`: the bank has no such channel.
+    pub fn output_stage(&self, channel: u32) -> Option<usize> {
+        let s = unsafe { knh_bank_output_stage(self.h, channel) };
+        if s == u32::MAX { None } else { Some(s as usize) }
+    }
 
     /// Flat parameter index of (`voice`, `stage`, parameter name), e.g. `"cutoff_freq"`, `"t_restart"`, `"wr_mul"`.
     pub fn index(&self, voice: u32, stage: usize, name: &str) -> Result<usize, BankError> {

@@ -424,6 +424,31 @@ int32_t knh_bank_assign_buffers(knh_bank* bank, uint32_t stage, size_t count, co
                                 const uint32_t* buffer_ids, const double* ctor);
 /* Entries in the pool of BufferReader stage `stage` (0 for any other stage). */
 uint32_t knh_bank_buffer_count(const knh_bank* bank, uint32_t stage);
+/* ---- Stereo voices: two of a voice's signals connected to graph outputs 0 and 1 ------------------------------------------
+ * Which signal of a voice each graph output carries (to_graph_out_channels / `(l | r).to_graph_out()`,
+ * graph_edit.rs:363-394, 1219-1368; one Add chain per output channel, graph.rs:827-872).  An output connection is an edge,
+ * not a node: no stage kind stands for it, knh_chain_ugen_count and knh_bank_algorithmic_bytes_per_voice_block do not change.
+ * stages[c]: the 0-based index of a stage, as in knh_bank_param_apply; graph output c carries the output of the node that
+ * stage stands for -- wrapper stages that follow the node belong to it, the rule knh_stage_desc.input follows.
+ * After knh_bank_create* (every kind of bank: plain, sharded, multi-device, rank), before knh_bank_init; it may be called
+ * again, the last accepted call holds.  Naming the last stage for both channels restores the default completely (the same
+ * signature, the same kernel, the mono per-voice shape); without any call nothing changes for any bank.
+ * A connected bank: knh_bank_process_block_voices writes [2][n_voices][block_size] as for Pan2, both mix modes work per
+ * channel, a voice's done frame is the last mark_done in the reference's task order for two connected outputs
+ * (Graph::calculate_node_order, graph.rs:1984-2067: the search starts from the deepest output node each output edge leads
+ * to -- as a rule the right output's subtree comes first, then what only the left reads; an output that feeds the other one
+ * is reached from it -- then unconnected nodes in push order).  The connected voice is a graph even when its stage list is a plain chain, and is fused
+ * like any graph: at most 512 stages -- also when it is made of SinWt oscillators and arithmetic only (the lane-per-frame
+ * kernels, which take up to 4 096 stages, hand out one signal per voice and do not run a connected voice).
+ * Refused, each with a knh_last_error text and leaving the bank as it was: a null argument, n_channels != 2, a bank whose
+ * out_channels is not 2, a chain that ends in KNH_STAGE_PAN2 or KNH_STAGE_GALACTIC, a named stage of kind KNH_STAGE_INPUT
+ * (an output connection starts at a node: put the input through `* 1.0`), a call after knh_bank_init
+ * (KNH_ERR_INVALID_ARGUMENT); a named stage >= n_stages (KNH_ERR_OUT_OF_RANGE); a connected voice of more than 512 stages
+ * (KNH_ERR_UNSUPPORTED_CHAIN). */
+int32_t knh_bank_connect_outputs(knh_bank* bank, uint32_t n_channels, const uint32_t* stages);
+/* The node-output stage index graph output `channel` carries: n_stages - 1 by default; 0xFFFFFFFF for a null handle or a
+ * channel the bank does not have. */
+uint32_t knh_bank_output_stage(const knh_bank* bank, uint32_t channel);
 int32_t knh_bank_init(knh_bank* bank, uint32_t sample_rate, size_t block_size);
 /* ---- Restarting voices of a running bank ----------------------------------------------------------------------------
  * A polyphonic host frees a voice's nodes when its envelope reports done (free_node_when_done, graph.rs:2483-2513) and
@@ -553,7 +578,8 @@ int32_t knh_bank_set_input(knh_bank* bank, uint32_t n_blocks, const void* in);
 int32_t knh_bank_set_input_device(knh_bank* bank, uint32_t n_blocks, const void* in_device);
 /* Parity/debug: also materialise every voice's own signal,
  * voices_out = host [n_voices][block_size] of F ([2][n_voices][block_size] for a chain that ends in
- * KNH_STAGE_PAN2: every voice's left signals, then every voice's right signals).  `out` may be NULL. */
+ * KNH_STAGE_PAN2 and for a bank with two connected outputs, knh_bank_connect_outputs: every voice's left signals, then
+ * every voice's right signals).  `out` may be NULL. */
 int32_t knh_bank_process_block_voices(knh_bank* bank, size_t frames_to_process,
                                       size_t block_start_offset, uint64_t frame_clock, void* out,
                                       void* voices_out, uint32_t* out_flags);

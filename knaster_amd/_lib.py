@@ -80,6 +80,8 @@ PROTOTYPES = {
     "knh_bank_set_voice_ctor_args": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32]),
     "knh_bank_restart_voices": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "knh_bank_buffer_count": (C.c_uint32, [C.c_void_p, C.c_uint32]),
+    "knh_bank_connect_outputs": (C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "knh_bank_output_stage": (C.c_uint32, [C.c_void_p, C.c_uint32]),
     "knh_bank_init": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_size_t]),
     "knh_bank_destroy": (None, [C.c_void_p]),
     "knh_bank_inputs": (C.c_uint16, [C.c_void_p]),

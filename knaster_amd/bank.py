@@ -179,6 +179,16 @@ class VoiceBank:
     def buffer_count(self, stage: int) -> int:
         return int(self._lib.knh_bank_buffer_count(self._h, stage))
 
+    def connect_outputs(self, left: int, right: int):
+        """Graph output 0 carries the signal of stage `left`'s node, output 1 that of stage `right`'s
+        (to_graph_out_channels; knh_bank_connect_outputs).  Before init; the last stage twice restores the default."""
+        arr = (C.c_uint32 * 2)(int(left), int(right))
+        self._check(self._lib.knh_bank_connect_outputs(self._h, 2, arr))
+
+    def output_stage(self, channel: int) -> int:
+        """The node-output stage graph output `channel` carries (knh_bank_output_stage); 0xFFFFFFFF: no such channel."""
+        return int(self._lib.knh_bank_output_stage(self._h, channel))
+
     def init(self, sample_rate: int, block_size: int):
         self._check(self._lib.knh_bank_init(self._h, sample_rate, block_size))
         self.sample_rate, self.block_size = sample_rate, block_size
@@ -277,8 +287,11 @@ class VoiceBank:
     def process_block_voices(self, frames_to_process: Optional[int] = None, block_start_offset: int = 0, frame_clock: int = 0):
         ftp = self.block_size if frames_to_process is None else frames_to_process
         out = np.zeros((self.out_channels, self.block_size), dtype=self.dtype)
-        # a chain that ends in Pan2 or Galactic has a left and a right signal per voice: [2][n_voices][block_size]
-        pan = bool(self.stages) and self.stages[-1].kind in (L.STAGE_PAN2, L.STAGE_GALACTIC)
+        # a chain that ends in Pan2 or Galactic, and a voice with two connected outputs, has a left and a right signal per
+        # voice: [2][n_voices][block_size]
+        last = len(self.stages) - 1
+        pan = bool(self.stages) and (self.stages[-1].kind in (L.STAGE_PAN2, L.STAGE_GALACTIC) or
+                                     (self.out_channels == 2 and (self.output_stage(0), self.output_stage(1)) != (last, last)))
         voices = np.zeros((2, self.n_voices, self.block_size) if pan else (self.n_voices, self.block_size), dtype=self.dtype)
         flags = C.c_uint32(0)
         self._check(self._lib.knh_bank_process_block_voices(self._h, ftp, block_start_offset, frame_clock,

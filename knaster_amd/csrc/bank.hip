@@ -44,12 +44,16 @@ using knh_dev::VoiceKernelArgs;
 
 namespace {
 
+// The pre-built kernel forms of a bank: at creation, and again when knh_bank_connect_outputs changes the voice's signature.
 template <typename F>
-knh_bank* make_bank(const knh_bank_desc& d, const knh::KernelEntry* entry, const std::string& sig) {
-  std::unique_ptr<Bank<F>> b(new Bank<F>());
-  b->desc = d;
+void choose_forms(Bank<F>* b, const knh::KernelEntry* entry, const std::string& sig) {
+  const knh_bank_desc& d = b->desc;
   b->entry = entry;
   b->signature = sig;
+  b->pipe = nullptr;
+  b->pipe_pair = false;
+  b->wide = nullptr;
+  b->wide_waves = 0;
   {  // KNH_PIPELINE=0 forces the single-wave kernel (A/B measurements); KNH_JIT=1 forces run-time fusion
     const char* jit_env = std::getenv("KNH_JIT");
     if (jit_env && jit_env[0] == '1') b->entry = nullptr;
@@ -106,6 +110,13 @@ knh_bank* make_bank(const knh_bank_desc& d, const knh::KernelEntry* entry, const
       if (ww == 4 || ww == 8 || ww == 16) b->wide_waves = ww;
     }
   }
+}
+
+template <typename F>
+knh_bank* make_bank(const knh_bank_desc& d, const knh::KernelEntry* entry, const std::string& sig) {
+  std::unique_ptr<Bank<F>> b(new Bank<F>());
+  b->desc = d;
+  choose_forms(b.get(), entry, sig);
   b->nv = d.n_voices;
   int slot = 0, pbase = 0;
   for (uint32_t i = 0; i < d.n_stages; ++i) {
@@ -468,6 +479,42 @@ int32_t knh_bank_restart_voices(knh_bank* bank, size_t count, const uint32_t* vo
     if (!bank) return KNH_ERR_INVALID_ARGUMENT;
     return bank->restart_voices(count, voices);
   });
+}
+int32_t knh_bank_connect_outputs(knh_bank* bank, uint32_t n_channels, const uint32_t* stages) {
+  return guarded(bank, [&]() -> int32_t {
+    if (!bank) return KNH_ERR_INVALID_ARGUMENT;
+    if (!stages) return bank->fail(KNH_ERR_INVALID_ARGUMENT, "null stages");
+    if (n_channels != 2) return bank->fail(KNH_ERR_INVALID_ARGUMENT, "two graph outputs can be connected (n_channels = 2)");
+    if (bank->desc.out_channels != 2) return bank->fail(KNH_ERR_INVALID_ARGUMENT, "connected outputs need a bank with two output channels (out_channels = 2)");
+    if (bank->initialised) return bank->fail(KNH_ERR_INVALID_ARGUMENT, "outputs are connected before knh_bank_init");
+    const uint32_t n = static_cast<uint32_t>(bank->stages.size());
+    if (stages[0] >= n || stages[1] >= n) return bank->fail(KNH_ERR_OUT_OF_RANGE, "stage out of range");
+    if (bank->stages.back().kind == KNH_STAGE_PAN2 || bank->stages.back().kind == KNH_STAGE_GALACTIC)
+      return bank->fail(KNH_ERR_INVALID_ARGUMENT, "a chain that ends in Pan2 or Galactic makes its two outputs itself");
+    uint32_t out[2];
+    for (int c = 0; c < 2; ++c) {
+      if (bank->stages[stages[c]].kind == KNH_STAGE_INPUT)
+        return bank->fail(KNH_ERR_INVALID_ARGUMENT, "an output connection starts at a node, not at a bank input (put the input through `* 1.0`)");
+      out[c] = stages[c];  // the node's output: behind the wrapper stages that follow it (build_signature, node_output)
+      while (out[c] + 1 < n && is_wrapper_kind(bank->stages[out[c] + 1].kind)) ++out[c];
+    }
+    std::vector<knh_stage_desc> st(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      const StageInfo& S = bank->stages[i];
+      st[i] = knh_stage_desc{};
+      st[i].kind = S.kind; st[i].flags = S.flags; st[i].delayed_changes_per_block = S.dcpb;
+      st[i].input = S.input; st[i].input2 = S.input2; st[i].ar_param = S.ar_param;
+    }
+    std::string sig, why;
+    const int rc = build_signature(st.data(), n, &sig, &why, out);
+    if (rc != KNH_OK) return bank->fail(rc, why);
+    bank->set_outputs(!(out[0] == n - 1 && out[1] == n - 1), out[0], out[1], sig);
+    return KNH_OK;
+  });
+}
+uint32_t knh_bank_output_stage(const knh_bank* bank, uint32_t channel) {
+  if (!bank || channel >= bank->desc.out_channels || bank->stages.empty()) return 0xFFFFFFFFu;
+  return bank->connected ? bank->out_stage[channel] : static_cast<uint32_t>(bank->stages.size()) - 1u;
 }
 uint32_t knh_bank_buffer_count(const knh_bank* bank, uint32_t stage) {
   try {

@@ -95,6 +95,16 @@ struct knh_bank {
   virtual int synchronize() = 0;
   virtual int debug_read(uint32_t* out16) = 0;
   virtual const char* debug_signature() const { return ""; }  // (a bank cut into ranges: its parts have one each)
+  // knh_bank_connect_outputs: which stage's signal (its node output) graph output 0 and 1 carry; `connected` false: both the
+  // last stage's, the voice with one signal.  The call is checked at the C boundary (bank.hip), which also makes the
+  // signature of the connected voice; a bank of several ranges passes both on to each of them.
+  bool connected = false;
+  uint32_t out_stage[2] = {0, 0};
+  virtual void set_outputs(bool conn, uint32_t left, uint32_t right, const std::string& /*sig*/) {
+    connected = conn;
+    out_stage[0] = left;
+    out_stage[1] = right;
+  }
   virtual int timing_reset(int enable) = 0;
   virtual int timing_read(double* ms, uint64_t* launches) = 0;
   virtual int collective_timing_read(double* ms, uint64_t* reduces) {

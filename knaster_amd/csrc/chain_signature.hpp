@@ -7,7 +7,9 @@
 namespace {
 
 // Chain descriptor -> device signature (kernel_registry.hpp) with structural validation.
-int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std::string* why) {
+// outs (or null): the node-output stages of the two connected graph outputs (knh_bank_connect_outputs); null, or the last
+// stage twice, is the voice whose one signal is the last stage's.
+int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std::string* why, const uint32_t* outs = nullptr) {
   if (n == 0) { *why = "empty chain"; return KNH_ERR_INVALID_ARGUMENT; }
   sig->clear();
   bool have_x = false;
@@ -67,7 +69,9 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
   // annotated "@a,b,o" with the SIGNAL SLOTS it reads and writes -- they are part of the kernel's type (knh_dev::At).  Slots
   // are handed out like registers, a signal's slot free again after its last reader, so that a voice of a thousand stages
   // (the reference's 256-oscillator FM cascade) keeps a handful of signals alive, not a thousand.
-  bool dag = false;
+  // (a voice with two connected outputs is a graph even when its stage list is a plain chain: two signals leave it)
+  const bool connected = outs && n > 0 && !(outs[0] == n - 1 && outs[1] == n - 1);
+  bool dag = connected;
   {
     uint32_t sources = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -77,11 +81,12 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     }
     dag = dag || sources > 1;
   }
-  if (dag && n > 512 && !(interp_can_run(st, n) && n <= 4096)) {
+  if (dag && n > 512 && !(interp_can_run(st, n) && n <= 4096 && !connected)) {
     // every stage unrolls into the one kernel the voice is fused into: 91 stages build in 2 s, 379 in a minute, and the
     // time grows faster than the count (the reference's 256-oscillator FM cascade, 1 531 stages, does not finish)
     // (graphs of SinWt oscillators and arithmetic alone are not fused at all: up to 4 096 stages run in kernels_interp.hip)
-    *why = "a voice that is a graph may hold at most 512 stages (4 096 if it is made of SinWt oscillators and arithmetic only)";
+    *why = connected ? "a voice with two connected outputs is fused like any graph: it may hold at most 512 stages"
+                     : "a voice that is a graph may hold at most 512 stages (4 096 if it is made of SinWt oscillators and arithmetic only)";
     return KNH_ERR_UNSUPPORTED_CHAIN;
   }
   if (dag) {
@@ -101,6 +106,10 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       if (b[i] >= 0) last_use[b[i]] = static_cast<int>(i);
     }
     last_use[n - 1] = static_cast<int>(n);  // the voice's output
+    if (connected) {  // ... or the two connected ones: neither slot is given to a later stage
+      last_use[n - 1] = -1;
+      last_use[outs[0]] = last_use[outs[1]] = static_cast<int>(n);
+    }
     std::vector<int> slot(n, -1);
     std::vector<char> busy;
     std::string out;
@@ -122,6 +131,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       out += "@" + num(sa) + "," + num(sb) + "," + num(o);
     }
     *sig = out + "#" + std::to_string(busy.size());  // "#R": the number of slots
+    if (connected) *sig += ":" + std::to_string(slot[outs[0]]) + "," + std::to_string(slot[outs[1]]);  // "#R:l,r": the slots of the two connected outputs
   }
   return KNH_OK;
 }
@@ -186,7 +196,15 @@ bool parse_frame_program(const std::string& signature, const std::vector<StageIn
 // which for a graph is the order Graph::calculate_node_order sorts the nodes into (graph.rs:1938-2067): depth first from
 // the output, a node's inputs in channel order, each node after everything it reads; nodes the output does not depend on
 // come last, in the order they were pushed.  0: list order (every chain; and graphs whose task order agrees with it).
-uint64_t envelope_task_ranks(const std::string& signature, const std::vector<StageInfo>& stages) {
+// outs (or null): the two connected outputs' stages (knh_bank_connect_outputs).  For each output edge, in channel order, the
+// reference pushes the DEEPEST output node its source leads to -- get_deepest_output_node, graph.rs:1984-2018: from the
+// source forward along the first node (in push order) that reads the current one through an input edge, until a node
+// already pushed or one nobody reads; the last output node met on the way, the source itself if none -- and only if that
+// node is not pushed yet (graph.rs:2022-2040).  The search then works from the top of that stack and never enters a node
+// that is on it: as a rule the right output's subtree is ordered first, then what only the left one reads; an output
+// that feeds the other one along that walk is not a root of its own, the search reaches it from the other.  Unconnected
+// nodes come last, in push order.
+uint64_t envelope_task_ranks(const std::string& signature, const std::vector<StageInfo>& stages, const uint32_t* outs = nullptr) {
   if (!signature_is_dag(signature)) return 0;
   const int n = static_cast<int>(stages.size());
   auto is_src = [&](int i) { return std::strchr("WNPUKOGBFI", kKinds[stages[i].kind].sig) != nullptr && !(stages[i].flags & KNH_STAGE_FLAG_AR_FREQ); };
@@ -199,10 +217,29 @@ uint64_t envelope_task_ranks(const std::string& signature, const std::vector<Sta
     if (stages[i].ar_param && !is_math2_kind(stages[i].kind)) b[i] = node_output(stages[i].input2 - 1);
   }
   std::vector<int> order, state(n, 0), stack{n - 1};
+  std::vector<char> root(n, 0);  // pushed as the start of the search ("visited" from then on: the search does not enter it from a reader)
+  if (outs) {
+    stack.clear();
+    auto first_reader = [&](int k) {  // input edges only: a parameter edge is not followed forward
+      for (int i = k + 1; i < n; ++i)
+        if (a[i] == k || (is_math2_kind(stages[i].kind) && b[i] == k)) return i;
+      return -1;
+    };
+    for (int c = 0; c < 2; ++c) {
+      int cur = static_cast<int>(outs[c]), deepest = cur;
+      while (!root[cur]) {
+        const int next = first_reader(cur);
+        if (next < 0) break;
+        cur = next;
+        if (cur == static_cast<int>(outs[0]) || cur == static_cast<int>(outs[1])) deepest = cur;
+      }
+      if (!root[deepest]) { stack.push_back(deepest); root[deepest] = 1; }
+    }
+  }
   while (!stack.empty()) {  // post-order, first operand first
     const int k = stack.back();
-    if (state[k] == 0) { state[k] = 1; if (a[k] >= 0 && state[a[k]] == 0) { stack.push_back(a[k]); continue; } }
-    if (state[k] == 1) { state[k] = 2; if (b[k] >= 0 && state[b[k]] == 0) { stack.push_back(b[k]); continue; } }
+    if (state[k] == 0) { state[k] = 1; if (a[k] >= 0 && state[a[k]] == 0 && !root[a[k]]) { stack.push_back(a[k]); continue; } }
+    if (state[k] == 1) { state[k] = 2; if (b[k] >= 0 && state[b[k]] == 0 && !root[b[k]]) { stack.push_back(b[k]); continue; } }
     if (state[k] == 2) { state[k] = 3; order.push_back(k); }
     stack.pop_back();
   }

@@ -112,6 +112,10 @@ struct ShardedBank final : knh_bank {
     return KNH_OK;
   }
   uint32_t buffer_count(uint32_t stage) const override { return shard[0]->buffer_count(stage); }
+  void set_outputs(bool conn, uint32_t left, uint32_t right, const std::string& sig) override {
+    knh_bank::set_outputs(conn, left, right, sig);
+    for (auto& s : shard) s->set_outputs(conn, left, right, sig);
+  }
   std::vector<uint32_t> asg_voices, asg_ids;
   std::vector<double> asg_ctor;
   int assign_buffers(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* ids, const double* ctor) override {
@@ -379,7 +383,7 @@ struct ShardedBank final : knh_bank {
     // A chain that ends in Pan2 hands out two planes, [2][voices][block_size]: a range's right plane belongs behind the whole
     // bank's left plane, not behind its own.  Each range renders its [2][count][block_size] into rows of its own (range k from
     // 2 * base[k] rows on: the ranges do not overlap), and the planes are put in place below.
-    const bool pan_planes = voices_host && n() > 1 && !stages.empty() && stages.back().kind == KNH_STAGE_PAN2;
+    const bool pan_planes = voices_host && n() > 1 && !stages.empty() && (stages.back().kind == KNH_STAGE_PAN2 || connected);  // (two connected outputs: two planes as well)
     if (pan_planes) pan_rows.resize(2 * static_cast<size_t>(nv) * block_size);
     workers->run([&](int k) {
       if (hipSetDevice(dev_of(k)) != hipSuccess) { rcs[k] = KNH_ERR_DEVICE; return; }

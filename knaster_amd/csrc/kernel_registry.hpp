@@ -7,6 +7,8 @@
 //     through one of the kernels below and the reverb in kernels_galactic.hip)
 //   J Pan2 (last stage only: two output channels)   I an input channel of the bank node (a source shared by all voices)
 //   + - * / ^  MathUGen of two signals; "@a" / "@a,b" after a stage: the stage(s) whose output it reads, when not the one before it
+//   "#R" ends a graph's signature: its number of signal slots; "#R:l,r": ... and the slots of the signals its two connected
+//     outputs carry (knh_bank_connect_outputs) -- part of the kernel's type and of the code-object cache's key
 //   m x*value   a x+value   s x-value   d x/value   v value-x   q value/x   p x.powf(value)   i x.powi(n)
 //   c x.ceil()   r x.sqrt()   f x.floor()   t x.trunc()   w x.fract()   e x.exp()   (Math1UGen: one operand, no state)
 #pragma once

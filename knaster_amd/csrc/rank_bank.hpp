@@ -97,6 +97,10 @@ struct RankBank final : knh_bank {
     pool_count += 1;
     return KNH_OK;
   }
+  void set_outputs(bool conn, uint32_t left, uint32_t right, const std::string& sig) override {
+    knh_bank::set_outputs(conn, left, right, sig);
+    if (local) local->set_outputs(conn, left, right, sig);
+  }
   uint32_t buffer_count(uint32_t stage) const override {
     if (local) return local->buffer_count(stage);
     return stage < stages.size() && stages[stage].kind == KNH_STAGE_BUFFER_READER ? pool_count : 0u;

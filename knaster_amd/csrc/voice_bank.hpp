@@ -9,6 +9,10 @@
 
 namespace {
 
+template <typename F> struct Bank;
+// which of the pre-built kernel forms a bank of this signature takes (bank.hip)
+template <typename F> void choose_forms(Bank<F>* b, const knh::KernelEntry* entry, const std::string& sig);
+
 template <typename F>
 struct Bank final : knh_bank {
   typedef typename knh_dev::WordOf<F>::type W;
@@ -32,6 +36,10 @@ struct Bank final : knh_bank {
   int pipeline_level = 1;                // KNH_PIPELINE
   std::string signature;
   const char* debug_signature() const override { return signature.c_str(); }
+  void set_outputs(bool conn, uint32_t left, uint32_t right, const std::string& sig) override {
+    knh_bank::set_outputs(conn, left, right, sig);
+    choose_forms(this, knh::find_kernel(sig.c_str()), sig);  // (no pre-built kernel has two connected outputs: such a voice is fused at init)
+  }
   uint32_t nv = 0;
   long stride = 0;
 
@@ -713,7 +721,8 @@ struct Bank final : knh_bank {
        // -- measured 10-27 times the lane-per-voice form from one voice to 65 536 (tools/bench_fm_cascade.py), and the only
        // form that takes the reference's 1 531-stage cascade.  KNH_INTERP=0: never (the lane-per-voice form, A/B runs).
       const char* ie = std::getenv("KNH_INTERP");
-      bool can = !entry && bs <= 1024 && stages.size() <= 4096;
+      // (a voice with two connected outputs is not one of them: the frame kernels hand out one signal; it is fused like any graph)
+      bool can = !entry && bs <= 1024 && stages.size() <= 4096 && !connected;
       for (const StageInfo& S : stages) can = can && frame_eligible(S.kind, S.flags, S.dcpb, S.ar_param);
       if (can && !(ie && ie[0] == '0')) {
         if (!parse_frame_program(signature, stages, &h_prog, &interp_sigs, &interp_out)) return fail(KNH_ERR_UNSUPPORTED_CHAIN, "interpreter: malformed graph signature");
@@ -739,7 +748,7 @@ struct Bank final : knh_bank {
         }
       }
     }
-    env_ranks = envelope_task_ranks(signature, stages);
+    env_ranks = envelope_task_ranks(signature, stages, connected ? out_stage : nullptr);
     const char* jp = std::getenv("KNH_JIT_PIPE");
     // (a single voice group with a pre-built kernel stays on it: nothing to gain, and no compile at init)
     // (a voice that is a graph, not a chain, runs in the single-wave form: the pipeline's edges carry one signal)
@@ -838,7 +847,7 @@ struct Bank final : knh_bank {
       KNH_HIP(hipMalloc(&d_sin_slots, std::max<size_t>(1, sins.size()) * sizeof(uint32_t)));
       if (!sins.empty()) KNH_HIP(hipMemcpy(d_sin_slots, sins.data(), sins.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
-    pan = !signature.empty() && stages.back().kind == KNH_STAGE_PAN2;  // a Pan2 ends the chain: every voice has a left and a right signal
+    pan = !signature.empty() && (stages.back().kind == KNH_STAGE_PAN2 || connected);  // a Pan2 ends the chain, or two outputs are connected: every voice has a left and a right signal
     fold_planes = pan ? 2u : 1u;
     KNH_HIP(hipMalloc(&d_partials, fold_planes * n_waves * bs * sizeof(F)));
     KNH_HIP(hipMalloc(&d_out, desc.out_channels * bs * sizeof(F)));
@@ -924,9 +933,9 @@ struct Bank final : knh_bank {
     return KNH_OK;
   }
   bool can_finish = false;   // the chain has a stage that can end a voice (ALL_DONE is reported only then)
-  bool pan = false;          // the chain ends in a Pan2
+  bool pan = false;          // the chain ends in a Pan2, or has two connected outputs
   F* stage_out = nullptr;    // set by a bank that wraps this one (galactic_bank.hpp): the voices' signals of the block go here, [n_voices][block_size]
-  unsigned fold_planes = 1;  // channel planes of the partial rows and of the per-voice output: 2 for a Pan2 chain
+  unsigned fold_planes = 1;  // channel planes of the partial rows and of the per-voice output: 2 for a Pan2 chain and for connected outputs
   hipError_t ensure_voices() {
     if (d_voices) return hipSuccess;
     return hipMalloc(&d_voices, static_cast<size_t>(fold_planes) * nv * block_size * sizeof(F));

@@ -26,6 +26,7 @@ struct Chain<F, FMA, BASE> {
   static constexpr int kSlots = BASE;
   static constexpr bool kUsesSine = false;
   static constexpr bool kPan = false;
+  static constexpr bool kStereo = false;
   static constexpr u64 kParamBits = 0ull, kNopOkBits = 0ull;
   static constexpr bool kBinds = false;
   static constexpr bool kUsesRing = false;
@@ -53,6 +54,7 @@ struct Chain<F, FMA, BASE, S0, Rest...> {
   static constexpr int kSlots = RestT::kSlots;
   static constexpr bool kUsesSine = S0::kUsesSine || RestT::kUsesSine;
   static constexpr bool kPan = IsPan<S0>::value || RestT::kPan;  // the chain ends in a Pan2: two output channels per voice
+  static constexpr bool kStereo = false;                         // (two connected outputs make a voice a graph: DagChain)
   // Absolute slots (bit = slot index, chains of up to 64 slots) that are parameters in the sense of
   // StageDefaults::kParamMask, and stage base slots to which a split mark without a change (EV_NOP) may be addressed
   // in the middle of a tile (the stage either carries its partial-block origin along in take_params or has none).
@@ -187,21 +189,24 @@ struct Math2 : StageDefaults {
 // A stage of a graph-shaped voice: the signal slots it reads (A, and B for Math2; -1: none -- a source) and writes (O).
 // The host hands slots out like registers (bank.hip, build_signature): a slot is free again after its signal's last
 // reader, and a stage whose operand dies with it writes in place.  Slots<R> at the end of the list: how many there are.
+// Outs<R, L, RR> in its place: a voice with two CONNECTED OUTPUTS (knh_bank_connect_outputs; the reference's
+// to_graph_out_channels, graph_edit.rs:381-394) -- graph output 0 carries the signal in slot L, output 1 the one in slot RR;
+// the host keeps both slots out of every later stage's hands.
 template <typename S, int A, int B, int O> struct At {};
 template <int R> struct Slots {};
+template <int R, int L, int RR> struct Outs {};
 template <typename X> struct NodeOf { static constexpr bool dag = false; };
 template <typename S, int A, int B, int O> struct NodeOf<At<S, A, B, O>> { typedef S stage; static constexpr int a = A, b = B, o = O; static constexpr bool dag = true; };
 template <int R> struct NodeOf<Slots<R>> { static constexpr bool dag = true; };
+template <int R, int L, int RR> struct NodeOf<Outs<R, L, RR>> { static constexpr bool dag = true; };
 
 template <typename F, bool FMA, int BASE, int R, int LAST, typename... Ns> struct DagChain;
-// end of the list: Slots<R> (LAST = the slot of the last stage's output: the voice's signal)
-template <typename F, bool FMA, int BASE, int R, int LAST, int R2>
-struct DagChain<F, FMA, BASE, R, LAST, Slots<R2>> {
-  static_assert(R == R2, "the slot count is the list's last entry");
+// end of the list: what every end has ...
+template <typename F, int BASE, int R>
+struct DagEnd {
   static constexpr int kSlots = BASE;
   static constexpr bool kUsesSine = false;
   static constexpr bool kPan = false;
-  static constexpr int kOut = LAST;
   static constexpr bool kUsesRing = false;
   __device__ __forceinline__ void pan_gains(F&, F&) const {}
   template <typename W> __device__ __forceinline__ void load(const W*, long) {}
@@ -215,6 +220,23 @@ struct DagChain<F, FMA, BASE, R, LAST, Slots<R2>> {
   template <int J> __device__ __forceinline__ void collect_done_ranked(u64, u32&, u32&) const {}
   __device__ __forceinline__ void begin_block(u32, const Ctx&) {}
 };
+// ... Slots<R> (LAST = the slot of the last stage's output: the voice's signal)
+template <typename F, bool FMA, int BASE, int R, int LAST, int R2>
+struct DagChain<F, FMA, BASE, R, LAST, Slots<R2>> : DagEnd<F, BASE, R> {
+  static_assert(R == R2, "the slot count is the list's last entry");
+  static constexpr int kOut = LAST;
+  static constexpr bool kStereo = false;
+  static constexpr int kOutL = LAST, kOutR = LAST;
+};
+// ... or Outs<R, L, RR>: the slots of the two connected outputs
+template <typename F, bool FMA, int BASE, int R, int LAST, int R2, int L, int RR>
+struct DagChain<F, FMA, BASE, R, LAST, Outs<R2, L, RR>> : DagEnd<F, BASE, R> {
+  static_assert(R == R2, "the slot count is the list's last entry");
+  static_assert(L >= 0 && L < R && RR >= 0 && RR < R, "signal slots are 0 .. R-1");
+  static constexpr int kOut = LAST;
+  static constexpr bool kStereo = true;
+  static constexpr int kOutL = L, kOutR = RR;
+};
 template <typename F, bool FMA, int BASE, int R, int LAST, typename N0, typename... Rest>
 struct DagChain<F, FMA, BASE, R, LAST, N0, Rest...> {
   typedef typename NodeOf<N0>::stage S0;
@@ -227,6 +249,8 @@ struct DagChain<F, FMA, BASE, R, LAST, N0, Rest...> {
   static constexpr bool kUsesSine = S0::kUsesSine || RestT::kUsesSine;
   static constexpr bool kPan = IsPan<S0>::value || RestT::kPan;
   static constexpr int kOut = RestT::kOut;
+  static constexpr bool kStereo = RestT::kStereo;  // two connected outputs: the voice's signals are those of slots kOutL and kOutR
+  static constexpr int kOutL = RestT::kOutL, kOutR = RestT::kOutR;
   static constexpr bool kUsesRing = S0::kUsesRing || RestT::kUsesRing;
   typename S0::template Regs<F> r;
   u32 mark = 0xFFFFFFFFu;
@@ -282,6 +306,19 @@ struct DagChain<F, FMA, BASE, R, LAST, N0, Rest...> {
     run_one(sig, c, frame);
     return sig[kOut];
   }
+  // ... of a voice with two connected outputs: the two signals
+  template <int T> __device__ __forceinline__ void tick_tile2(F (&xl)[T], F (&xr)[T], const Ctx& c, u32 frame0) {
+    F sig[R][T];
+    run_tile<T>(sig, c, frame0);
+#pragma unroll
+    for (int j = 0; j < T; ++j) { xl[j] = sig[kOutL][j]; xr[j] = sig[kOutR][j]; }
+  }
+  __device__ __forceinline__ void tick2(F& xl, F& xr, const Ctx& c, u32 frame) {
+    F sig[R];
+    run_one(sig, c, frame);
+    xl = sig[kOutL];
+    xr = sig[kOutR];
+  }
   __device__ __forceinline__ u32 collect_done(u32 acc) const {
     if constexpr (S0::kIsEnv) acc = mark != 0xFFFFFFFFu ? mark : acc;
     return rest.collect_done(acc);
@@ -320,6 +357,7 @@ struct DagChain<F, FMA, BASE, R, LAST, N0, Rest...> {
 template <typename... S> struct SlotCount { static constexpr int value = 0; };
 template <typename S0, typename... S> struct SlotCount<S0, S...> { static constexpr int value = SlotCount<S...>::value; };
 template <int R> struct SlotCount<Slots<R>> { static constexpr int value = R; };
+template <int R, int L, int RR> struct SlotCount<Outs<R, L, RR>> { static constexpr int value = R; };
 // the kernel's chain type: a plain chain unless the list is a graph's
 template <bool DAG, typename F, bool FMA, typename... S> struct ChainSelect { typedef Chain<F, FMA, 0, S...> type; };
 template <typename F, bool FMA, typename... S> struct ChainSelect<true, F, FMA, S...> { typedef DagChain<F, FMA, 0, SlotCount<S...>::value, 0, S...> type; };
@@ -927,7 +965,8 @@ template <int WAVES, typename S> struct ForWaves { typedef S type; };
 template <bool AR> struct ForWaves<8, MulEnvT<AR>> { typedef TightEnv<MulEnvT<AR>, 128> type; };
 template <bool AR> struct ForWaves<16, MulEnvT<AR>> { typedef TightEnv<MulEnvT<AR>, 32> type; };  // (128 registers: eight f32 samples at a time)
 
-// LDS: the sine table (64 KiB, only if a stage uses it) + eight rows of 64 samples per wavefront for the sample-by-sample path.
+// LDS: the sine table (64 KiB, only if a stage uses it) + eight rows of 64 samples per wavefront for the sample-by-sample path
+// (two sets of eight for a voice with two connected outputs).
 // WAVES = wavefronts (64-voice groups) per workgroup sharing the table: 1 for small banks, 4, 8 or 16 when
 // the bank has more 64-voice groups than the chip has SIMDs to give each its own (throughput regime).
 // The voices' samples never leave the registers on the fast path: each visit's frames are folded over the wavefront's
@@ -950,7 +989,8 @@ __global__ void __launch_bounds__(WAVES * 64) voice_kernel(VoiceKernelArgs<F> a)
   constexpr int KT = sizeof...(S) > 16 ? kTile : (WAVES >= 16 ? (sizeof(F) == 4 ? 16 : 8) : (WAVES <= 4 ? (sizeof(F) == 4 ? 64 : 32) : (sizeof(F) == 4 && !ChainT::kUsesRing ? KNH_WIDE_KT8 : 32)));  // (a delay's tile, its lines and the lines read ahead: 64 samples of each spill at 256 registers)
   // (one LDS object with the table first: the table at LDS address 0, a table read's address is the masked phase itself)
   constexpr bool kRingTile = ChainT::kUsesRing && WAVES <= 8 && KT * (int)sizeof(F) >= RingLines<F>::kLine;  // (sixteen tiles do not fit beside the table)
-  constexpr int kSlowBytes = kTile * 64 * (int)sizeof(F);
+  constexpr bool kTwoPlanes = ChainT::kPan || ChainT::kStereo;  // a left and a right signal per voice: two partial rows per wavefront
+  constexpr int kSlowBytes = (ChainT::kStereo ? 2 : 1) * kTile * 64 * (int)sizeof(F);
   constexpr int kScratch = kRingTile && RingLines<F>::kTileBytes > kSlowBytes ? RingLines<F>::kTileBytes : kSlowBytes;
   struct Lds {
     float sine[ChainT::kUsesSine ? 16384 : 4];
@@ -959,6 +999,8 @@ __global__ void __launch_bounds__(WAVES * 64) voice_kernel(VoiceKernelArgs<F> a)
     __attribute__((aligned(16))) char scratch[WAVES][kScratch];
     u32 res_slot[4];                                        // a resident launch's command word
   };
+  // 160 KiB per workgroup: the table, sixteen f32 or eight f64 wavefronts' rows (two sets each for connected outputs), a ring tile
+  static_assert(sizeof(Lds) <= 160 * 1024, "the table and every wavefront's scratch fit in a CU's LDS");
   __shared__ Lds lds;
   auto& sine = lds.sine;
 
@@ -1074,17 +1116,18 @@ __global__ void __launch_bounds__(WAVES * 64) voice_kernel(VoiceKernelArgs<F> a)
     ctx.input_block = reinterpret_cast<const F*>(a.input) + (long)b * a.in_channels * a.block_size;
     chain.begin_block(fbeg, ctx);
     // a chain that ends in Pan2 has a left and a right partial row per wavefront: [block][channel][wavefront][frame]
-    F* const row0 = a.partials + ((long)b * (ChainT::kPan ? 2 : 1) * n_waves_total + wave_global) * a.block_size;
+    F* const row0 = a.partials + ((long)b * (kTwoPlanes ? 2 : 1) * n_waves_total + wave_global) * a.block_size;
     F* const row1 = row0 + (long)n_waves_total * a.block_size;
     // m of the V frames x[0..V) from frame n on are real: fold them over the wavefront's voices, one sum per frame
-    auto emit = [&](auto& x, u32 n, u32 m) {
+    // (y: the right signal's frames of a voice with two connected outputs; any other voice has one signal, and y is x)
+    auto emit = [&](auto& x, auto& y, u32 n, u32 m) {
       constexpr int V = (int)(sizeof(x) / sizeof(x[0]));
 #ifdef KNH_DAG_STAMPS
       const u64 st_f0 = __builtin_amdgcn_s_memtime();
 #endif
       bool writer;
       const u32 f = fold_frame_of<V>(fl.v, writer);
-      if constexpr (!ChainT::kPan) {
+      if constexpr (!kTwoPlanes) {
         if (a.voices_out && live) {  // (parity / debug output, single blocks only: every lane its own voice's row)
 #pragma unroll
           for (int j = 0; j < V; ++j)
@@ -1100,11 +1143,18 @@ __global__ void __launch_bounds__(WAVES * 64) voice_kernel(VoiceKernelArgs<F> a)
           }
         }
       } else {
-        // Pan2 (pan.rs:31-36): each voice's sample times its two gains (the product is rounded), then one sum per channel
-        chain.pan_gains(pan_l, pan_r);
+        // a left and a right signal per voice, one sum per channel
         F xl[V], xr[V];
+        if constexpr (ChainT::kPan) {
+          // Pan2 (pan.rs:31-36): each voice's sample times its two gains (the product is rounded)
+          chain.pan_gains(pan_l, pan_r);
 #pragma unroll
-        for (int j = 0; j < V; ++j) { xl[j] = x[j] * pan_l; xr[j] = x[j] * pan_r; }
+          for (int j = 0; j < V; ++j) { xl[j] = x[j] * pan_l; xr[j] = x[j] * pan_r; }
+        } else {
+          // two connected outputs: the two signals as they are
+#pragma unroll
+          for (int j = 0; j < V; ++j) { xl[j] = x[j]; xr[j] = y[j]; }
+        }
         if (a.voices_out && live) {
 #pragma unroll
           for (int j = 0; j < V; ++j)
@@ -1147,15 +1197,27 @@ __global__ void __launch_bounds__(WAVES * 64) voice_kernel(VoiceKernelArgs<F> a)
           st_visits += 1;
         } else
 #endif
-        chain.template tick_tile<KT>(x, ctx, n);
-        emit(x, n, (u32)KT);
+        if constexpr (ChainT::kStereo) {  // two connected outputs: the voice's two tiles
+          F y[KT];
+          chain.template tick_tile2<KT>(x, y, ctx, n);
+          emit(x, y, n, (u32)KT);
+        } else {
+          chain.template tick_tile<KT>(x, ctx, n);
+          emit(x, x, n, (u32)KT);
+        }
         n += KT;
       } else if (KT > kTile && left >= (u32)kTile && !__builtin_amdgcn_ballot_w64(nxt.frame < base + n + kTile)) {
         F x[kTile];
 #pragma unroll
         for (int j = 0; j < kTile; ++j) x[j] = (F)0;
-        chain.template tick_tile<kTile>(x, ctx, n);
-        emit(x, n, (u32)kTile);
+        if constexpr (ChainT::kStereo) {
+          F y[kTile];
+          chain.template tick_tile2<kTile>(x, y, ctx, n);
+          emit(x, y, n, (u32)kTile);
+        } else {
+          chain.template tick_tile<kTile>(x, ctx, n);
+          emit(x, x, n, (u32)kTile);
+        }
         n += kTile;
       } else {
         // (through eight rows of LDS, written with a run-time index: the register tile is never indexed dynamically, which
@@ -1164,14 +1226,23 @@ __global__ void __launch_bounds__(WAVES * 64) voice_kernel(VoiceKernelArgs<F> a)
         F(*rows)[64] = reinterpret_cast<F(*)[64]>(lds.scratch[wave]);
         for (u32 j = 0; j < m; ++j) {
           apply_events_upto(base + n + j);
-          rows[j][lane] = chain.tick((F)0, ctx, n + j);
+          if constexpr (ChainT::kStereo) chain.tick2(rows[j][lane], rows[kTile + j][lane], ctx, n + j);  // (the second set of eight rows: the right signal)
+          else rows[j][lane] = chain.tick((F)0, ctx, n + j);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         F x[kTile];
 #pragma unroll
         for (int j = 0; j < kTile; ++j) x[j] = (u32)j < m ? rows[j][lane] : (F)0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        emit(x, n, m);
+        if constexpr (ChainT::kStereo) {
+          F y[kTile];
+#pragma unroll
+          for (int j = 0; j < kTile; ++j) y[j] = (u32)j < m ? rows[kTile + j][lane] : (F)0;
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          emit(x, y, n, m);
+        } else {
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          emit(x, x, n, m);
+        }
         n += m;
       }
     }

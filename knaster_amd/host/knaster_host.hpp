@@ -226,8 +226,12 @@ struct ChainPlan {
   std::vector<knh_stage_desc> stages;
   std::vector<int> stage_node;                  // node id whose parameters stage s exposes (-1: none)
   std::vector<std::vector<double>> stage_args;  // constructor arguments per stage
+  // two different signals on the two graph outputs (`(l | r).to_graph_out()`): the stages whose nodes they are, -1: the
+  // voice's one signal, the last stage's, on every output (knh_bank_connect_outputs)
+  int out_stage[2] = {-1, -1};
   std::string signature() const {
     std::string s;
+    if (out_stage[0] >= 0) s += "out" + std::to_string(out_stage[0]) + "," + std::to_string(out_stage[1]) + ";";
     for (auto& st : stages) {
       s += std::to_string(st.kind) + "." + std::to_string(st.flags) + "." + std::to_string(st.delayed_changes_per_block) + "." +
            std::to_string(st.input) + "." + std::to_string(st.input2) + "." + std::to_string(st.ar_param) + ";";
@@ -265,6 +269,17 @@ class Sig {  // SH / DH of graph_edit.rs:266-277: one or more output channels of
     return Sig(g_, n, ch);
   }
   void to_graph_out() const { g_->to_graph_out(*this); }  // additive (graph_edit.rs:363-369)
+  // (l | r): the channels of `l`, then those of `r`, as one handle (Stack, graph_edit.rs:1219-1368)
+  Sig operator|(const Sig& o) const {
+    std::vector<int> n(nodes_), ch(chans_);
+    n.insert(n.end(), o.nodes_.begin(), o.nodes_.end());
+    ch.insert(ch.end(), o.chans_.begin(), o.chans_.end());
+    return Sig(g_, n, ch);
+  }
+  // channel i of this handle to graph output channels[i] (graph_edit.rs:381-394).  The graph outputs of one voice may be
+  // connected by several calls -- l.to_graph_out_channels({0}); r.to_graph_out_channels({1}); -- a voice is complete when
+  // every graph output has a signal.
+  void to_graph_out_channels(std::initializer_list<int> channels) const { g_->to_graph_out_channels(*this, std::vector<int>(channels)); }
   int node() const { return nodes_.at(0); }
   const std::vector<int>& nodes() const { return nodes_; }
   const std::vector<int>& channels() const { return chans_; }  // output channel of nodes()[i] that channel i of this handle carries
@@ -466,22 +481,38 @@ class Graph {
 
   // graph.rs:1707-1726: plan the newly connected voices, create their banks, upload their state.
   void commit_changes() {
+    // a voice connected half (to_graph_out_channels({0}) and nothing on output 1) is dropped and the edit refused, before
+    // anything is planned: the graph stays usable, the edit's complete voices are committed by the next edit
+    for (auto& half : partial_output_)
+      if (half.first >= 0) {
+        partial_output_.clear();
+        throw GraphError("to_graph_out_channels(): a graph output of the voice has no signal");
+      }
     struct Voice { ChainPlan plan; std::vector<int> nodes; };
     std::vector<Voice> voices;
     for (auto& conn : new_outputs_) {
-      // conn = the per-channel (node, output channel) of one to_graph_out(): either the same mono signal on every
-      // graph output (`.out([0,0])`), or the two outputs of a Pan2 on the two graph outputs, in order
+      // conn = the per-channel (node, output channel) of one to_graph_out(): the same mono signal on every graph output
+      // (`.out([0,0])`), the two outputs of a Pan2 on the two graph outputs, in order, or two different signals
+      // (`(l | r).to_graph_out()`): one voice holding both subgraphs, a shared node traced once, its two outputs connected
       if (conn.size() != outputs_) throw GraphError("to_graph_out(): channel count does not match the graph outputs");
-      const NodeRec& last = nodes_[static_cast<size_t>(conn[0].first)];
-      const bool pan = last.type == NodeRec::UGEN && last.spec.kind == KNH_STAGE_PAN2;
+      bool pan = false, same = true;
       for (size_t c = 0; c < conn.size(); ++c) {
-        if (conn[c].first != conn[0].first) throw GraphError("different signals per output channel are not a voice chain");
-        if (conn[c].second != (pan ? static_cast<int>(c) : 0)) throw GraphError("a Pan2's outputs go to graph outputs 0 and 1, in order");
+        if (conn[c].first < 0) throw GraphError("to_graph_out_channels(): a graph output of the voice has no signal");
+        const NodeRec& x = nodes_[static_cast<size_t>(conn[c].first)];
+        pan = pan || (x.type == NodeRec::UGEN && x.spec.kind == KNH_STAGE_PAN2);
+        same = same && conn[c].first == conn[0].first;
       }
+      for (size_t c = 0; c < conn.size(); ++c)
+        if (conn[c].second != (pan ? static_cast<int>(c) : 0) || (pan && !same)) throw GraphError("a Pan2's outputs go to graph outputs 0 and 1, in order");
       if (pan && outputs_ != 2) throw GraphError("a Pan2 voice needs a stereo graph");
       Voice v;
       std::map<int, uint16_t> done;
-      trace(conn[0].first, v.plan, v.nodes, done);
+      const uint16_t left = trace(conn[0].first, v.plan, v.nodes, done);
+      if (!same) {
+        const uint16_t right = trace(conn[1].first, v.plan, v.nodes, done);
+        v.plan.out_stage[0] = left - 1;  // (a signal's name is 1 + the stage whose output it is)
+        v.plan.out_stage[1] = right - 1;
+      }
       voices.push_back(std::move(v));
     }
     new_outputs_.clear();
@@ -524,6 +555,10 @@ class Graph {
         d.device = -1;
         d.allow_fma = 0;
         if (knh_bank_create(&d, &b.h) != KNH_OK) throw GraphError(std::string("knh_bank_create: ") + knh_last_error(nullptr));
+        if (b.plan.out_stage[0] >= 0) {
+          const uint32_t outs[2] = {static_cast<uint32_t>(b.plan.out_stage[0]), static_cast<uint32_t>(b.plan.out_stage[1])};
+          check(b, knh_bank_connect_outputs(b.h, 2, outs));
+        }
         for (size_t s = 0; s < b.plan.stages.size(); ++s) {
           // voices of one bank may hold Envelopes of different lengths: pad to the longest (unused rows, duration 1)
           size_t n_args = 0;
@@ -569,6 +604,7 @@ class Graph {
   size_t block_size_;
   std::vector<NodeRec> nodes_;
   std::vector<std::vector<std::pair<int, int>>> new_outputs_;  // per to_graph_out(): (node, output channel) per graph output
+  std::vector<std::pair<int, int>> partial_output_;            // to_graph_out_channels(): the voice being connected, (-1, 0): no signal yet
   std::vector<Bank> banks_;
   std::vector<SchedulingEvent> events_;  // the rtrb channel of graph.rs:225-230, drained by the processor
 };
@@ -626,6 +662,24 @@ class GraphEdit {
     std::vector<std::pair<int, int>> conn;
     for (size_t c = 0; c < s.nodes().size(); ++c) conn.emplace_back(s.nodes()[c], s.channels()[c]);
     graph_->new_outputs_.push_back(std::move(conn));
+  }
+  void to_graph_out_channels(const Sig<F>& s, const std::vector<int>& channels) {
+    if (channels.size() != s.nodes().size()) throw GraphError("to_graph_out_channels(): one graph output per channel of the handle");
+    auto& part = graph_->partial_output_;
+    part.resize(graph_->outputs_, {-1, 0});
+    for (size_t c = 0; c < channels.size(); ++c) {
+      if (channels[c] < 0 || channels[c] >= static_cast<int>(graph_->outputs_)) throw GraphError("to_graph_out_channels(): channel out of range");
+      auto& slot = part[static_cast<size_t>(channels[c])];
+      if (slot.first >= 0) {
+        part.clear();  // (the voice being connected is dropped with the refusal)
+        throw GraphError("to_graph_out_channels(): two signals of one voice on one graph output are not fused");
+      }
+      slot = {s.nodes()[c], s.channels()[c]};
+    }
+    for (auto& slot : part)
+      if (slot.first < 0) return;  // the voice's other output is still to come
+    graph_->new_outputs_.push_back(part);
+    part.assign(graph_->outputs_, {-1, 0});
   }
   typename Sig<F>::Parameter param(int node, const std::string& name) {
     const NodeRec& n = graph_->nodes_[static_cast<size_t>(node)];

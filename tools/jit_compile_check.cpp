@@ -1,6 +1,7 @@
 // Compiles ONE chain signature with the library's run-time fusion (hiprtc) and says how it went -- no GPU needed: the compile
 // itself is host work, only loading the result asks for a device.  A compiler crash kills this process, not a host's:
-// tools/jit_compile_fuzz.py runs it over random voices.
+// tools/jit_compile_fuzz.py runs it over random voices.  A signature is what knh_bank_debug_signature prints: a chain
+// ("WSA"), a graph with its signal slots ("...#R"), a graph with two connected outputs ("...#R:l,r").
 //   make -C tests/cpp bin/jit_compile_check
 #include <algorithm>
 #include <cmath>
