@@ -133,6 +133,7 @@ pub const KNH_SVF_HIGH_SHELF: u32 = 8;
 
 pub const KNH_STAGE_FLAG_AR_FREQ: u16 = 1 << 0;
 pub const KNH_STAGE_FLAG_SMOOTH_PARAMS: u16 = 1 << 1;
+pub const KNH_STAGE_FLAG_READER_CH1: u16 = 1 << 2;
 
 // knh_mix_mode
 pub const KNH_MIX_TREE: u32 = 0;
@@ -161,6 +162,7 @@ unsafe extern "C" {
     pub fn knh_bank_set_ctor_args(bank: *mut knh_bank, stage: u32, first_voice: u32, count: u32, args: *const f64, n_args: u32) -> i32;
     pub fn knh_bank_set_buffer(bank: *mut knh_bank, stage: u32, samples: *const c_void, n_frames: usize, buffer_sample_rate: f64) -> i32;
     pub fn knh_bank_add_buffer(bank: *mut knh_bank, stage: u32, samples: *const c_void, n_frames: usize, buffer_sample_rate: f64, out_index: *mut u32) -> i32;
+    pub fn knh_bank_add_buffer_interleaved(bank: *mut knh_bank, stage: u32, samples: *const c_void, n_frames: usize, n_channels: u32, buffer_sample_rate: f64, out_index: *mut u32) -> i32;
     pub fn knh_bank_assign_buffers(bank: *mut knh_bank, stage: u32, count: usize, voices: *const u32, buffer_ids: *const u32, ctor: *const f64) -> i32;
     pub fn knh_bank_set_voice_ctor_args(bank: *mut knh_bank, stage: u32, count: usize, voices: *const u32, args: *const f64, n_args: u32) -> i32;
     pub fn knh_bank_restart_voices(bank: *mut knh_bank, count: usize, voices: *const u32) -> i32;

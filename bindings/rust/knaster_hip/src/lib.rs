@@ -246,6 +246,19 @@ impl<F: Float, I: Size> GpuVoiceBank<F, I> {
         let rc = unsafe { knh_bank_add_buffer(self.h, stage as u32, samples.as_ptr() as *const c_void, samples.len(), buffer_sample_rate, &mut index) };
         if rc != KNH_OK { Err(last_error(self.h)) } else { Ok(index) }
     }
+    /// `Buffer::from_vec_interleaved(samples, num_channels, sample_rate)`: one more pool entry of `n_channels` (1 or 2)
+    /// channels, `samples` frame by frame.  The first entry fixes the pool's channel count.  Channel 1 of a reader on a
+    /// two-channel pool is the stage flagged `KNH_STAGE_FLAG_READER_CH1` whose `input` names the reader stage.
+    pub fn add_buffer_interleaved(&mut self, stage: usize, samples: &[F], n_channels: u32, buffer_sample_rate: f64) -> Result<u32, BankError> {
+        if n_channels == 0 || samples.len() % (n_channels as usize) != 0 {
+            return Err(BankError("add_buffer_interleaved: samples holds whole frames of n_channels values".into()));
+        }
+        let mut index = 0u32;
+        let rc = unsafe {
+            knh_bank_add_buffer_interleaved(self.h, stage as u32, samples.as_ptr() as *const c_void, samples.len() / n_channels as usize, n_channels, buffer_sample_rate, &mut index)
+        };
+        if rc != KNH_OK { Err(last_error(self.h)) } else { Ok(index) }
+    }
     /// Voice `voices[i]` reads pool entry `buffer_ids[i]`.  `ctor`: `[rate, looping, start_s]` per voice.  Before the bank
     /// is pushed it may be `None` (the constructor arguments stay); afterwards it is required, and the voice's reader is
     /// from the next block on what `BufferReader::new(pool[id], rate, looping).start_at(start_s)` is after init.

@@ -124,6 +124,10 @@ typedef enum knh_value_kind {
  *     the bank runs.  Seconds-valued parameters convert with the rate of the voice's own Buffer.
  *     params: 0 rate, 1 looping(bool), 2 start_s, 3 duration_s, 4 end_s, 5 t_restart(trigger).  Not combinable with
  *     delayed_changes_per_block (the reference's block loop ignores partial blocks).  At most one per chain.
+ *     BufferReader::<F, U2> on a two-channel (interleaved) Buffer, knh_bank_add_buffer_interleaved: ONE node with TWO output
+ *     signals.  The reader stage is output channel 0; a second stage of this kind with KNH_STAGE_FLAG_READER_CH1 and
+ *     input = 1 + the reader stage's index is output channel 1 (below, at the flag).  Without such a stage a reader on a
+ *     two-channel pool plays channel 0 of the interleaved frames, as BufferReader::<F, U1> does on a stereo Buffer.
  * KNH_STAGE_PHASOR          g.push(Phasor::new(freq))           osc.rs:172-214       1    freq
  *     a source like SinWt: a 0..1 ramp, f64 phase and step whatever F is.  params: 0 freq
  * KNH_STAGE_POLYBLEP        g.push(PolyBlep::new(waveform, freq))   polyblep.rs:123-508   1    waveform (0..13), freq
@@ -272,7 +276,23 @@ enum {
    * KNH_VALUE_SMOOTHING value selects linear smoothing for one Float parameter, after which new
    * Float values are reached by a block-rate linear ramp (smooth_params.rs:12-311).  The ramp lives
    * on the host, as it does on the reference's audio thread: one param_apply per node per block. */
-  KNH_STAGE_FLAG_SMOOTH_PARAMS = 1u << 1
+  KNH_STAGE_FLAG_SMOOTH_PARAMS = 1u << 1,
+  /* kind = KNH_STAGE_BUFFER_READER, this flag, input = 1 + the index of a BufferReader stage: OUTPUT CHANNEL 1 of the node that
+   * stage stands for -- BufferReader::<F, U2> on a two-channel Buffer (buffer.rs:122-190: one read pointer, a sample per
+   * channel; knaster/examples/buffer_player.rs).  It is not a node: no constructor arguments, no parameters, no state;
+   * knh_chain_ugen_count counts 0 for it; every parameter call that names it is KNH_ERR_INVALID_ARGUMENT, before
+   * knh_bank_init too (the rule of the MATH1_* stages); ar_param, input2, delayed_changes_per_block and
+   * KNH_STAGE_FLAG_SMOOTH_PARAMS must be 0 on it; at most one per reader.  The reader stage itself is channel 0 and carries
+   * everything of the node: parameters 0-5, constructor arguments, knh_bank_assign_buffers, restart,
+   * KNH_STAGE_FLAG_SMOOTH_PARAMS, ar_param = 1 (a linked rate), the done mark (one per node) and KNH_FLAG_ALL_DONE.
+   * The signal is one like any other: knh_bank_connect_outputs may name it, `input` / `input2` of later stages may name it
+   * (MATH_ADD of both channels is a mono fold-down), it may be the last stage of an unconnected voice.  A voice with such
+   * a stage is a graph: the single-wave kernel form, fused at knh_bank_init.
+   * Refused: a KNH_STAGE_WR_* wrapper stage on a reader that has such a companion (KNH_ERR_UNSUPPORTED_CHAIN: the wrapper
+   * would have to act on both channels -- use a MUL_CONST per channel, which is what `play * amp.out([0, 0])` is);
+   * a pool of single-channel Buffers under it (knh_bank_init: KNH_ERR_INVALID_ARGUMENT -- the reference reads the
+   * neighbouring sample there and runs off the end); more than two channels. */
+  KNH_STAGE_FLAG_READER_CH1 = 1u << 2
 };
 
 typedef struct knh_stage_desc {
@@ -407,6 +427,17 @@ int32_t knh_bank_set_buffer(knh_bank* bank, uint32_t stage, const void* samples,
  * A refused call (not a BufferReader stage, a null or empty Buffer, a bad rate, after init, a pool too large) changes nothing. */
 int32_t knh_bank_add_buffer(knh_bank* bank, uint32_t stage, const void* samples, size_t n_frames, double buffer_sample_rate,
                             uint32_t* out_index);
+/* Buffer::from_vec_interleaved(samples, num_channels, sample_rate) (dsp/buffer.rs:70-78): one more pool entry of
+ * `n_channels` channels, `samples` = n_frames * n_channels values of the bank's sample type, frame by frame.  n_channels is
+ * 1 or 2 (anything else: KNH_ERR_INVALID_ARGUMENT); with 1 it is knh_bank_add_buffer.  The channel count is a property of
+ * the POOL: the first entry fixes it, a later entry with another count is refused and changes nothing -- so
+ * knh_bank_set_buffer and knh_bank_add_buffer, which add single-channel entries, are refused on a two-channel pool.
+ * The pool's layout and limits stay: one device allocation, every entry's start rounded up to 64 samples, at most
+ * 2^32 - 1 SAMPLES (channels counted); a voice's offset counts samples, its length counts frames.
+ * knh_bank_assign_buffers, knh_bank_buffer_count, restart and the "whole pool in every range / on every rank" rule apply
+ * unchanged. */
+int32_t knh_bank_add_buffer_interleaved(knh_bank* bank, uint32_t stage, const void* samples, size_t n_frames,
+                                        uint32_t n_channels, double buffer_sample_rate, uint32_t* out_index);
 /* Voice voices[i] reads pool entry buffer_ids[i] (every voice: entry 0 until told otherwise).
  * ctor: NULL, or [count][3] = rate, looping, start_s (the stage's constructor arguments).
  * Before knh_bank_init: the Buffer the voice is constructed on (a non-NULL ctor also replaces its constructor arguments).

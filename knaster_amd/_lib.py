@@ -31,6 +31,7 @@ VALUE_FLOAT, VALUE_TRIGGER, VALUE_INTEGER, VALUE_BOOL, VALUE_SMOOTHING = 0, 1, 2
  STAGE_MATH1_CEIL, STAGE_MATH1_SQRT, STAGE_MATH1_FLOOR, STAGE_MATH1_TRUNC, STAGE_MATH1_FRACT, STAGE_MATH1_EXP) = range(46)
 STAGE_FLAG_AR_FREQ = 1
 STAGE_FLAG_SMOOTH_PARAMS = 2
+STAGE_FLAG_READER_CH1 = 4  # a STAGE_BUFFER_READER stage with it: output channel 1 of the reader stage `input` names
 # knh_svf_type
 SVF_LOW, SVF_HIGH, SVF_BAND, SVF_NOTCH, SVF_PEAK, SVF_ALL, SVF_BELL, SVF_LOW_SHELF, SVF_HIGH_SHELF = range(9)
 # knh_mix_mode
@@ -76,6 +77,7 @@ PROTOTYPES = {
     "knh_bank_set_ctor_args": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     "knh_bank_set_buffer": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_double]),
     "knh_bank_add_buffer": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_double, C.POINTER(C.c_uint32)]),
+    "knh_bank_add_buffer_interleaved": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_double, C.POINTER(C.c_uint32)]),
     "knh_bank_assign_buffers": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "knh_bank_set_voice_ctor_args": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32]),
     "knh_bank_restart_voices": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_void_p]),

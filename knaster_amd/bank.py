@@ -137,12 +137,22 @@ class VoiceBank:
         a = np.ascontiguousarray(np.asarray(samples, dtype=self.dtype))
         self._check(self._lib.knh_bank_set_buffer(self._h, stage, a.ctypes.data_as(C.c_void_p), a.shape[0], float(buffer_sample_rate)))
 
-    def add_buffer(self, stage: int, samples, buffer_sample_rate: float) -> int:
-        """One more Buffer in the pool of the BufferReader stage -> its pool index (knh_bank_add_buffer); before init."""
+    def add_buffer(self, stage: int, samples, buffer_sample_rate: float, channels: Optional[int] = None) -> int:
+        """One more Buffer in the pool of the BufferReader stage -> its pool index; before init.  channels None: a
+        single-channel Buffer (knh_bank_add_buffer).  channels 1 or 2: Buffer::from_vec_interleaved
+        (knh_bank_add_buffer_interleaved) -- samples is [n_frames, channels] (or flat, frame by frame)."""
         a = np.ascontiguousarray(np.asarray(samples, dtype=self.dtype))
         index = C.c_uint32(0)
-        self._check(self._lib.knh_bank_add_buffer(self._h, stage, a.ctypes.data_as(C.c_void_p), a.shape[0],
-                                                  float(buffer_sample_rate), C.byref(index)))
+        if channels is None:
+            self._check(self._lib.knh_bank_add_buffer(self._h, stage, a.ctypes.data_as(C.c_void_p), a.shape[0],
+                                                      float(buffer_sample_rate), C.byref(index)))
+        else:
+            flat = a.reshape(-1)
+            if channels in (1, 2) and flat.shape[0] % channels != 0:
+                raise ValueError("add_buffer: samples holds whole frames of `channels` values")
+            n_frames = flat.shape[0] // channels if channels in (1, 2) else flat.shape[0]
+            self._check(self._lib.knh_bank_add_buffer_interleaved(self._h, stage, flat.ctypes.data_as(C.c_void_p), n_frames,
+                                                                  int(channels), float(buffer_sample_rate), C.byref(index)))
         return int(index.value)
 
     def assign_buffers(self, stage: int, voices, buffer_ids, ctor=None):

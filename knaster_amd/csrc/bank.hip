@@ -127,10 +127,12 @@ knh_bank* make_bank(const knh_bank_desc& d, const knh::KernelEntry* entry, const
     if (s.kind == KNH_STAGE_SVF && s.ar_param != 0) s.n_slots = 12;
     // a BufferReader whose rate is driven at audio rate keeps its Buffer's base rate there as well (knh_dev::BufferReaderP)
     if (s.kind == KNH_STAGE_BUFFER_READER && s.ar_param != 0) s.n_slots = 14;
+    // the second output of a BufferReader (KNH_STAGE_FLAG_READER_CH1) is no node: no slots, no parameters, no constructor arguments
+    if (s.ch1()) s.n_slots = s.n_params = s.n_ctor = 0;
     b->stages.push_back(s);
-    b->ctor.emplace_back(static_cast<size_t>(d.n_voices) * (k.n_ctor > 0 ? k.n_ctor : 0), 0.0);
+    b->ctor.emplace_back(static_cast<size_t>(d.n_voices) * (s.n_ctor > 0 ? s.n_ctor : 0), 0.0);
     slot += s.n_slots;
-    pbase += k.n_params;
+    pbase += s.n_params;
   }
   b->n_slots = slot;
   b->n_params_total = pbase;
@@ -309,7 +311,7 @@ int32_t knh_chain_ugen_count(const knh_stage_desc* stages, uint32_t n_stages) {
     if (!stages) return 0;
     int n = 0;
     for (uint32_t i = 0; i < n_stages; ++i)
-      if (stages[i].kind < KNH_STAGE_KIND_COUNT) n += kKinds[stages[i].kind].n_nodes;
+      if (stages[i].kind < KNH_STAGE_KIND_COUNT && !is_reader_ch1(stages[i])) n += kKinds[stages[i].kind].n_nodes;  // (a reader's second output is the reader)
     return n;
   });
 }
@@ -459,7 +461,14 @@ int32_t knh_bank_set_buffer(knh_bank* bank, uint32_t stage, const void* samples,
 int32_t knh_bank_add_buffer(knh_bank* bank, uint32_t stage, const void* samples, size_t n_frames, double buffer_sample_rate, uint32_t* out_index) {
   return guarded(bank, [&]() -> int32_t {
     if (!bank) return KNH_ERR_INVALID_ARGUMENT;
-    return bank->add_buffer(stage, samples, n_frames, buffer_sample_rate, out_index);
+    return bank->add_buffer(stage, samples, n_frames, 1, buffer_sample_rate, out_index);
+  });
+}
+int32_t knh_bank_add_buffer_interleaved(knh_bank* bank, uint32_t stage, const void* samples, size_t n_frames, uint32_t n_channels,
+                                        double buffer_sample_rate, uint32_t* out_index) {
+  return guarded(bank, [&]() -> int32_t {
+    if (!bank) return KNH_ERR_INVALID_ARGUMENT;
+    return bank->add_buffer(stage, samples, n_frames, n_channels, buffer_sample_rate, out_index);
   });
 }
 int32_t knh_bank_assign_buffers(knh_bank* bank, uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* buffer_ids, const double* ctor) {
@@ -794,7 +803,7 @@ int32_t knh_bank_algorithmic_bytes_per_voice_block(const knh_bank* bank, uint32_
         case KNH_STAGE_BROWN_NOISE: w += word * 3; break;
         case KNH_STAGE_RANDOM_LIN: w += word * 5; break;
         case KNH_STAGE_POLYBLEP: w += word; break;
-        case KNH_STAGE_BUFFER_READER: w += word * 3; break;  // + two Buffer samples read per frame
+        case KNH_STAGE_BUFFER_READER: w += s.ch1() ? 0 : word * 3; break;  // + two Buffer samples read per frame (two frames of two with a second output)
         case KNH_STAGE_ALLPASS_DELAY: case KNH_STAGE_ALLPASS_FB_DELAY: w += word * 4; break;  // + one sample read and one written per frame (ring in HBM)  // + one sample read and one written per frame (ring in HBM)
         default: break;
       }

@@ -38,7 +38,8 @@ struct knh_bank {
   virtual int set_ctor(uint32_t stage, uint32_t first, uint32_t count, const double* args, uint32_t n_args) = 0;
   virtual int set_buffer(uint32_t stage, const void* samples, size_t n_frames, double buffer_sample_rate) = 0;
   // the pool of Buffers of a BufferReader stage: one more entry; which entry each voice plays; how many there are
-  virtual int add_buffer(uint32_t stage, const void* samples, size_t n_frames, double buffer_sample_rate, uint32_t* out_index) = 0;
+  // (n_channels 1 or 2: samples holds n_frames * n_channels values, frame by frame; the first entry fixes the pool's channel count)
+  virtual int add_buffer(uint32_t stage, const void* samples, size_t n_frames, uint32_t n_channels, double buffer_sample_rate, uint32_t* out_index) = 0;
   virtual void drop_last_buffer(uint32_t /*stage*/) {}  // undoes the add_buffer just made (a bank of several ranges keeping them alike)
   virtual int assign_buffers(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* buffer_ids, const double* ctor) = 0;
   virtual uint32_t buffer_count(uint32_t stage) const = 0;

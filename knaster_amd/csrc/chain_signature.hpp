@@ -13,15 +13,40 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
   if (n == 0) { *why = "empty chain"; return KNH_ERR_INVALID_ARGUMENT; }
   sig->clear();
   bool have_x = false;
+  // KNH_STAGE_FLAG_READER_CH1 stages: companion[r] = the stage that stands for output channel 1 of the reader stage r
+  std::vector<int> companion(n, -1);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (st[i].kind >= KNH_STAGE_KIND_COUNT || !(st[i].flags & KNH_STAGE_FLAG_READER_CH1)) continue;
+    if (st[i].kind != KNH_STAGE_BUFFER_READER) { *why = "READER_CH1 is only defined for BUFFER_READER"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (st[i].flags != KNH_STAGE_FLAG_READER_CH1 || st[i].ar_param != 0 || st[i].input2 != 0 || st[i].delayed_changes_per_block != 0) {
+      *why = "a READER_CH1 stage is the second output of a BufferReader, not a node: ar_param, input2, delayed_changes_per_block and every other flag must be 0";
+      return KNH_ERR_INVALID_ARGUMENT;
+    }
+    if (st[i].input == 0 || st[i].input > i || st[st[i].input - 1].kind != KNH_STAGE_BUFFER_READER || (st[st[i].input - 1].flags & KNH_STAGE_FLAG_READER_CH1)) {
+      *why = "a READER_CH1 stage names the BufferReader stage it is channel 1 of (input = 1 + its index, an earlier stage)";
+      return KNH_ERR_INVALID_ARGUMENT;
+    }
+    if (companion[st[i].input - 1] >= 0) { *why = "at most one READER_CH1 stage per BufferReader"; return KNH_ERR_INVALID_ARGUMENT; }
+    companion[st[i].input - 1] = static_cast<int>(i);
+  }
   for (uint32_t i = 0; i < n; ++i) {
     if (st[i].kind >= KNH_STAGE_KIND_COUNT) { *why = "unknown stage kind"; return KNH_ERR_INVALID_ARGUMENT; }
-    const bool source = st[i].kind == KNH_STAGE_SIN_WT || st[i].kind == KNH_STAGE_SIN_NUMERIC || st[i].kind == KNH_STAGE_PHASOR ||
+    const bool ch1 = is_reader_ch1(st[i]);
+    if (is_wrapper_kind(st[i].kind) && i > 0) {  // the node the wrapper would wrap: a reader with two outputs?
+      uint32_t k = i - 1;
+      while (k > 0 && is_wrapper_kind(st[k].kind)) --k;
+      if (is_reader_ch1(st[k]) || (st[k].kind == KNH_STAGE_BUFFER_READER && companion[k] >= 0)) {
+        *why = "a wrapper stage on a BufferReader with a READER_CH1 companion would have to act on both channels: use a MUL_CONST (ADD_CONST, ...) per channel";
+        return KNH_ERR_UNSUPPORTED_CHAIN;
+      }
+    }
+    const bool source = !ch1 && (st[i].kind == KNH_STAGE_SIN_WT || st[i].kind == KNH_STAGE_SIN_NUMERIC || st[i].kind == KNH_STAGE_PHASOR ||
                         st[i].kind == KNH_STAGE_WHITE_NOISE || st[i].kind == KNH_STAGE_PINK_NOISE || st[i].kind == KNH_STAGE_BROWN_NOISE ||
                         st[i].kind == KNH_STAGE_RANDOM_LIN ||
-                        st[i].kind == KNH_STAGE_POLYBLEP || st[i].kind == KNH_STAGE_BUFFER_READER || st[i].kind == KNH_STAGE_INPUT;
+                        st[i].kind == KNH_STAGE_POLYBLEP || st[i].kind == KNH_STAGE_BUFFER_READER || st[i].kind == KNH_STAGE_INPUT);
     const bool ar = st[i].kind == KNH_STAGE_SIN_WT && (st[i].flags & KNH_STAGE_FLAG_AR_FREQ);
     const bool math2 = is_math2_kind(st[i].kind);
-    if (st[i].flags & ~(KNH_STAGE_FLAG_AR_FREQ | KNH_STAGE_FLAG_SMOOTH_PARAMS)) { *why = "unknown stage flag"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (st[i].flags & ~(KNH_STAGE_FLAG_AR_FREQ | KNH_STAGE_FLAG_SMOOTH_PARAMS | KNH_STAGE_FLAG_READER_CH1)) { *why = "unknown stage flag"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((st[i].flags & KNH_STAGE_FLAG_SMOOTH_PARAMS) && (st[i].flags & KNH_STAGE_FLAG_AR_FREQ)) { *why = "SMOOTH_PARAMS and AR_FREQ cannot be combined"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((st[i].flags & KNH_STAGE_FLAG_SMOOTH_PARAMS) && is_wrapper_kind(st[i].kind)) { *why = "SMOOTH_PARAMS applies to a node, not to a wrapper stage"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((st[i].flags & KNH_STAGE_FLAG_AR_FREQ) && st[i].kind != KNH_STAGE_SIN_WT) { *why = "AR_FREQ is only defined for SIN_WT"; return KNH_ERR_INVALID_ARGUMENT; }
@@ -62,7 +87,8 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       if (st[i].flags & (KNH_STAGE_FLAG_AR_FREQ | KNH_STAGE_FLAG_SMOOTH_PARAMS)) { *why = "ar_param cannot be combined with AR_FREQ or SMOOTH_PARAMS on one stage"; return KNH_ERR_INVALID_ARGUMENT; }
       if (kKinds[st[i].kind].sig == 'I' || st[st[i].input2 - 1].kind == KNH_STAGE_INPUT) { *why = "an audio-rate parameter edge starts at a node, not at a bank input (put the input through `* 1.0`)"; return KNH_ERR_INVALID_ARGUMENT; }
     }
-    sig->push_back(ar ? 'R' : kKinds[st[i].kind].sig);
+    // ('T': a reader with two outputs; '2': its second output, which is no device stage and leaves the signature below)
+    sig->push_back(ar ? 'R' : ch1 ? '2' : (st[i].kind == KNH_STAGE_BUFFER_READER && companion[i] >= 0) ? 'T' : kKinds[st[i].kind].sig);
     have_x = true;
   }
   // A voice that is a graph (a stage that names its operands, a MathUGen of two signals, a second source): every stage is
@@ -76,8 +102,8 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     uint32_t sources = 0;
     for (uint32_t i = 0; i < n; ++i) {
       const bool ar = st[i].kind == KNH_STAGE_SIN_WT && (st[i].flags & KNH_STAGE_FLAG_AR_FREQ);
-      sources += std::strchr("WNPUKOGBFI", kKinds[st[i].kind].sig) != nullptr && !ar;
-      dag = dag || is_math2_kind(st[i].kind) || (st[i].input != 0 && st[i].input != i) || st[i].ar_param != 0;
+      sources += std::strchr("WNPUKOGBFI", kKinds[st[i].kind].sig) != nullptr && !ar && !is_reader_ch1(st[i]);
+      dag = dag || is_math2_kind(st[i].kind) || (st[i].input != 0 && st[i].input != i) || st[i].ar_param != 0 || is_reader_ch1(st[i]);
     }
     dag = dag || sources > 1;
   }
@@ -98,7 +124,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       return k;
     };
     for (uint32_t i = 0; i < n; ++i) {
-      const bool reads = i > 0 && !(std::strchr("WNPUKOGBFI", (*sig)[i]) != nullptr);  // 'R' reads, the plain sources do not
+      const bool reads = i > 0 && !(std::strchr("WNPUKOGBFIT2", (*sig)[i]) != nullptr);  // 'R' reads, the plain sources do not (nor does a reader's second output: it IS the reader)
       if (is_math2_kind(st[i].kind)) { a[i] = node_output(st[i].input - 1); b[i] = node_output(st[i].input2 - 1); }
       else if (reads) a[i] = st[i].input ? node_output(st[i].input - 1) : static_cast<int>(i) - 1;
       if (st[i].ar_param != 0) b[i] = node_output(st[i].input2 - 1);  // the signal that drives the parameter
@@ -114,6 +140,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     std::vector<char> busy;
     std::string out;
     for (uint32_t i = 0; i < n; ++i) {
+      if ((*sig)[i] == '2') continue;  // a reader's second output: its slot was handed out with the reader's, it is no device stage
       const int sa = a[i] >= 0 ? slot[a[i]] : -1, sb = b[i] >= 0 ? slot[b[i]] : -1;
       // operands whose last reader this is give their slot back first: the stage may then write where it read
       if (a[i] >= 0 && last_use[a[i]] == static_cast<int>(i)) busy[sa] = 0;
@@ -125,12 +152,22 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       if (o < 0) { o = static_cast<int>(busy.size()); busy.push_back(0); }
       if (last_use[i] >= 0) busy[o] = 1;  // (a signal nobody reads holds its slot only while it is written)
       slot[i] = o;
+      int o2 = -1;
+      if (companion[i] >= 0) {  // a reader with two outputs writes both slots every frame: the second one is another slot, held like the first until its last reader
+        for (size_t k = 0; o2 < 0 && k < busy.size(); ++k)
+          if (!busy[k] && static_cast<int>(k) != o) o2 = static_cast<int>(k);
+        if (o2 < 0) { o2 = static_cast<int>(busy.size()); busy.push_back(0); }
+        if (last_use[companion[i]] >= 0) busy[o2] = 1;
+        slot[companion[i]] = o2;
+      }
       out.push_back((*sig)[i]);
       if (st[i].ar_param != 0) out += "%" + std::to_string(st[i].ar_param - 1);  // "%P": parameter P at audio rate (knh_dev::ArP)
       auto num = [](int v) { return v < 0 ? std::string("_") : std::to_string(v); };  // "_": none
       out += "@" + num(sa) + "," + num(sb) + "," + num(o);
+      if (o2 >= 0) out += "," + num(o2);  // "@a,b,o,o2": the slot of the node's second output (knh_dev::At2)
     }
     *sig = out + "#" + std::to_string(busy.size());  // "#R": the number of slots
+    if (!connected && (st[n - 1].flags & KNH_STAGE_FLAG_READER_CH1)) *sig += "=" + std::to_string(slot[n - 1]);  // "#R=k": the voice's signal is a reader's second output, in slot k (knh_dev::Out1)
     if (connected) *sig += ":" + std::to_string(slot[outs[0]]) + "," + std::to_string(slot[outs[1]]);  // "#R:l,r": the slots of the two connected outputs
   }
   return KNH_OK;
@@ -216,7 +253,19 @@ uint64_t envelope_task_ranks(const std::string& signature, const std::vector<Sta
     // an audio-rate parameter edge: followed after the node's input edges (graph.rs:1938-1980)
     if (stages[i].ar_param && !is_math2_kind(stages[i].kind)) b[i] = node_output(stages[i].input2 - 1);
   }
-  std::vector<int> order, state(n, 0), stack{n - 1};
+  // a reader's second output (KNH_STAGE_FLAG_READER_CH1) is the reader NODE: whoever reads it reads that node
+  auto node_of = [&](int k) { return k >= 0 && stages[k].ch1() ? static_cast<int>(stages[k].input) - 1 : k; };
+  for (int i = 0; i < n; ++i) {
+    if (stages[i].ch1()) { a[i] = b[i] = -1; continue; }
+    a[i] = node_of(a[i]);
+    b[i] = node_of(b[i]);
+  }
+  uint32_t out_nodes[2] = {0, 0};
+  if (outs) {
+    for (int c = 0; c < 2; ++c) out_nodes[c] = static_cast<uint32_t>(node_of(static_cast<int>(outs[c])));
+    outs = out_nodes;
+  }
+  std::vector<int> order, state(n, 0), stack{node_of(n - 1)};
   std::vector<char> root(n, 0);  // pushed as the start of the search ("visited" from then on: the search does not enter it from a reader)
   if (outs) {
     stack.clear();

@@ -97,9 +97,9 @@ struct GalacticBank final : knh_bank {
     if (mine(stage)) return fail(KNH_ERR_INVALID_ARGUMENT, "stage is not a BufferReader");
     return adopt(inner->set_buffer(stage, samples, n_frames, sr));
   }
-  int add_buffer(uint32_t stage, const void* samples, size_t n_frames, double sr, uint32_t* out_index) override {
+  int add_buffer(uint32_t stage, const void* samples, size_t n_frames, uint32_t n_channels, double sr, uint32_t* out_index) override {
     if (mine(stage)) return fail(KNH_ERR_INVALID_ARGUMENT, "stage is not a BufferReader");
-    return adopt(inner->add_buffer(stage, samples, n_frames, sr, out_index));
+    return adopt(inner->add_buffer(stage, samples, n_frames, n_channels, sr, out_index));
   }
   int assign_buffers(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* ids, const double* ctor) override {
     if (mine(stage)) return fail(KNH_ERR_INVALID_ARGUMENT, "stage is not a BufferReader");

@@ -93,7 +93,7 @@ struct ShardedBank final : knh_bank {
     }
     return KNH_OK;
   }
-  int add_buffer(uint32_t stage, const void* samples, size_t n_frames, double sr, uint32_t* out_index) override {  // every range holds the whole pool
+  int add_buffer(uint32_t stage, const void* samples, size_t n_frames, uint32_t n_channels, double sr, uint32_t* out_index) override {  // every range holds the whole pool
     // The ranges are alike, so what the first one refuses they all would; should a later one fail all the same (its copy of
     // the samples does not fit in memory), the ranges before it drop the entry again: a refused call changes nothing.
     uint32_t index = 0;
@@ -101,7 +101,7 @@ struct ShardedBank final : knh_bank {
     auto undo = [&] { for (int j = 0; j < done; ++j) shard[j]->drop_last_buffer(stage); };
     try {
       for (; done < n(); ++done) {
-        int rc = shard[done]->add_buffer(stage, samples, n_frames, sr, &index);
+        int rc = shard[done]->add_buffer(stage, samples, n_frames, n_channels, sr, &index);
         if (rc != KNH_OK) { adopt(done, rc); undo(); return rc; }
       }
     } catch (...) {
@@ -278,6 +278,7 @@ struct ShardedBank final : knh_bank {
   }
 
   int param_apply(uint32_t voice, uint32_t stage, uint32_t param, uint32_t kind, double f, int64_t i) override {
+    if (stage < stages.size() && stages[stage].ch1()) return fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams);  // (about the chain: named ahead of the state, as a range does)
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (voice >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
     flush_deferred();
@@ -285,6 +286,7 @@ struct ShardedBank final : knh_bank {
     return adopt(k, shard[k]->param_apply(voice - base[k], stage, param, kind, f, i));
   }
   int set_delay(uint32_t voice, uint32_t stage, uint32_t param, uint16_t delay) override {
+    if (stage < stages.size() && stages[stage].ch1()) return fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams);  // (about the chain: named ahead of the state, as a range does)
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (voice >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
     flush_deferred();
@@ -293,6 +295,7 @@ struct ShardedBank final : knh_bank {
   }
   int call_at(uint32_t block_offset, bool is_delay, uint32_t voice, uint32_t stage, uint32_t param, uint32_t kind, double f, int64_t i,
               uint16_t delay) override {
+    if (stage < stages.size() && stages[stage].ch1()) return fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams);  // (about the chain: named ahead of the state, as a range does)
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (voice >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
     flush_deferred();

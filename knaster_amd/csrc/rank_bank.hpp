@@ -74,26 +74,29 @@ struct RankBank final : knh_bank {
   }
   int set_buffer(uint32_t stage, const void* samples, size_t n_frames, double sr) override {
     if (local) return adopt(local->set_buffer(stage, samples, n_frames, sr));
-    int rc = check_buffer("knh_bank_set_buffer", stage, samples, n_frames, sr);
+    int rc = check_buffer("knh_bank_set_buffer", stage, samples, n_frames, 1, sr);
     if (rc != KNH_OK) return rc;
-    if (pool_count == 0) pool_count = 1;  // (entry 0 exists from here on)
+    if (pool_count == 0) { pool_count = 1; pool_channels = 1; }  // (entry 0 exists from here on)
     return KNH_OK;
   }
   // A rank without voices holds no pool, but refuses what the ranks with voices refuse and counts the entries, so that every
   // rank hands out the same indices.
-  int check_buffer(const char* who, uint32_t stage, const void* samples, size_t n_frames, double sr) {
+  int check_buffer(const char* who, uint32_t stage, const void* samples, size_t n_frames, uint32_t n_channels, double sr) {
     if (initialised) return fail(KNH_ERR_INVALID_ARGUMENT, std::string(who) + " comes before knh_bank_init");
-    if (stage >= stages.size() || stages[stage].kind != KNH_STAGE_BUFFER_READER) return fail(KNH_ERR_INVALID_ARGUMENT, "not a BufferReader stage");
+    if (stage >= stages.size() || !stages[stage].reader()) return fail(KNH_ERR_INVALID_ARGUMENT, "not a BufferReader stage");
+    if (n_channels < 1 || n_channels > 2) return fail(KNH_ERR_INVALID_ARGUMENT, "a Buffer has one or two channels");
+    if (pool_count != 0 && n_channels != pool_channels) return fail(KNH_ERR_INVALID_ARGUMENT, "every Buffer of a pool has the channel count of its first entry");
     if (!samples || n_frames == 0 || n_frames >= (1ull << 31) || !(sr > 0.0) || !std::isfinite(sr)) return fail(KNH_ERR_INVALID_ARGUMENT, "empty buffer or bad sample rate");
     return KNH_OK;
   }
   // (every rank is handed the whole pool)
-  uint32_t pool_count = 0;
-  int add_buffer(uint32_t stage, const void* samples, size_t n_frames, double sr, uint32_t* out_index) override {
-    if (local) return adopt(local->add_buffer(stage, samples, n_frames, sr, out_index));
-    int rc = check_buffer("knh_bank_add_buffer", stage, samples, n_frames, sr);
+  uint32_t pool_count = 0, pool_channels = 0;
+  int add_buffer(uint32_t stage, const void* samples, size_t n_frames, uint32_t n_channels, double sr, uint32_t* out_index) override {
+    if (local) return adopt(local->add_buffer(stage, samples, n_frames, n_channels, sr, out_index));
+    int rc = check_buffer("knh_bank_add_buffer", stage, samples, n_frames, n_channels, sr);
     if (rc != KNH_OK) return rc;
     if (out_index) *out_index = pool_count;
+    if (pool_count == 0) pool_channels = n_channels;
     pool_count += 1;
     return KNH_OK;
   }
@@ -103,12 +106,12 @@ struct RankBank final : knh_bank {
   }
   uint32_t buffer_count(uint32_t stage) const override {
     if (local) return local->buffer_count(stage);
-    return stage < stages.size() && stages[stage].kind == KNH_STAGE_BUFFER_READER ? pool_count : 0u;
+    return stage < stages.size() && stages[stage].reader() ? pool_count : 0u;
   }
   std::vector<uint32_t> asg_voices, asg_ids;
   std::vector<double> asg_ctor;
   int assign_buffers(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* ids, const double* ctor) override {
-    if (stage >= stages.size() || stages[stage].kind != KNH_STAGE_BUFFER_READER) return fail(KNH_ERR_INVALID_ARGUMENT, "not a BufferReader stage");
+    if (stage >= stages.size() || !stages[stage].reader()) return fail(KNH_ERR_INVALID_ARGUMENT, "not a BufferReader stage");
     if (count && (!voices || !ids)) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
     const uint32_t n_buffers = buffer_count(stage);
     for (size_t i = 0; i < count; ++i) {  // voice numbers are the whole bank's: checked here, on every rank alike
@@ -190,6 +193,9 @@ struct RankBank final : knh_bank {
     }
     int local_rc = KNH_OK;
     if (local) local_rc = local->init(sr, bs);
+    else  // a rank without voices refuses what the ranks with voices refuse: a reader's second output on a one-channel pool
+      for (const StageInfo& S : stages)
+        if (S.ch1() && pool_channels == 1) { local_rc = fail(KNH_ERR_INVALID_ARGUMENT, "a KNH_STAGE_FLAG_READER_CH1 stage needs a pool of two-channel Buffers (knh_bank_add_buffer_interleaved with n_channels = 2)"); break; }
     if (local_rc != KNH_OK) adopt(local_rc);
     if (comm) {
       // every rank says whether its own voices came up, and every rank learns whether all did: a rank that failed and left
@@ -221,6 +227,7 @@ struct RankBank final : knh_bank {
   }
   int check_global(uint32_t voice, uint32_t stage, uint32_t param) {
     if (stage < stages.size() && is_math1_kind(stages[stage].kind)) return fail(KNH_ERR_INVALID_ARGUMENT, "a KNH_STAGE_MATH1_* stage has no parameters");
+    if (stage < stages.size() && stages[stage].ch1()) return fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams);
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (voice >= total) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
     if (stage >= stages.size()) return fail(KNH_ERR_OUT_OF_RANGE, "stage out of range");
@@ -254,7 +261,11 @@ struct RankBank final : knh_bank {
   // same batch -- and dropped
   int apply_many(uint32_t block_offset, size_t count, const uint32_t* voices, const uint32_t* stgs, const uint32_t* params,
                  const uint32_t* kinds, const double* fvalues, const int64_t* ivalues, const uint16_t* delays) override {
-    if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
+    if (!initialised) {  // (a call that names a reader's second output is a mistake about the chain: named ahead of the state, as check_global does)
+      for (size_t k = 0; k < count; ++k)
+        if (stgs[k] < stages.size() && stages[stgs[k]].ch1()) return fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams);
+      return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
+    }
     r_voices.clear(); r_stages.clear(); r_params.clear(); r_kinds.clear(); r_f.clear(); r_i.clear(); r_d.clear();
     int rc = KNH_OK;  // the code of the last refused call, in array order: the same on every rank
     for (size_t k = 0; k < count; ++k) {
@@ -262,6 +273,7 @@ struct RankBank final : knh_bank {
       if (v >= total) { rc = fail(KNH_ERR_OUT_OF_RANGE, "voice out of range"); continue; }
       if (stgs[k] >= stages.size()) { rc = fail(KNH_ERR_OUT_OF_RANGE, "stage out of range"); continue; }
       if (is_math1_kind(stages[stgs[k]].kind)) { rc = fail(KNH_ERR_INVALID_ARGUMENT, "a KNH_STAGE_MATH1_* stage has no parameters"); continue; }
+      if (stages[stgs[k]].ch1()) { rc = fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams); continue; }
       if (params[k] >= static_cast<uint32_t>(stages[stgs[k]].n_params)) { rc = fail(KNH_ERR_OUT_OF_RANGE, "parameter index out of range"); continue; }
       if (block_offset >= 65536) { rc = fail(KNH_ERR_OUT_OF_RANGE, "block_offset too large"); continue; }
       if (!kind_ok(stgs[k], params[k], kinds[k])) { rc = fail(KNH_ERR_WRONG_VALUE_KIND, "parameter value kind does not match the parameter type"); continue; }

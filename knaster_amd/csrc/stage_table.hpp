@@ -87,7 +87,7 @@ inline int stage_cost(char c) {
   switch (c) {
     case 'W': return 7;  case 'R': return 10; case 'N': return 25; case 'S': return 10; case 'L': return 3;
     case 'H': return 4;  case 'A': return 5;  case 'E': return 5;  case 'V': return 14; case 'D': return 12;
-    case 'd': case 'q': return 8;  case 'p': return 40; case 'i': return 10; case 'P': return 6; case 'U': return 14; case 'O': return 19; case 'K': return 50; case 'G': return 10; case 'X': return 4; case 'B': return 45; case 'Y': return 14; case 'Z': return 18; case 'F': return 16;
+    case 'd': case 'q': return 8;  case 'p': return 40; case 'i': return 10; case 'P': return 6; case 'U': return 14; case 'O': return 19; case 'K': return 50; case 'G': return 10; case 'X': return 4; case 'B': return 45; case 'Y': return 14; case 'Z': return 18; case 'F': case 'C': return 16;  // ('C': the mono reader on a two-channel pool, the same work)
     case 'r': return 12; case 'e': return 20;  // Math1: the correctly rounded sqrt sequence, the device library's exp (ceil floor trunc fract: 1-2)
     default: return 1;
   }
@@ -219,7 +219,13 @@ struct StageInfo {
   int param_base;  // index of this stage's first parameter in the flat per-voice parameter table
   uint16_t input = 0, input2 = 0;  // knh_stage_desc: the stage(s) whose output this one reads (0: the one before it)
   uint16_t ar_param = 0;           // knh_stage_desc: 1 + the float parameter a second signal (input2) drives at audio rate, 0: none
+  // a BufferReader NODE (its stage is output channel 0) / the stage that stands for output channel 1 of one
+  // (KNH_STAGE_FLAG_READER_CH1: no node -- no slots, no parameters, no constructor arguments, no shadows)
+  bool reader() const { return kind == KNH_STAGE_BUFFER_READER && !(flags & KNH_STAGE_FLAG_READER_CH1); }
+  bool ch1() const { return kind == KNH_STAGE_BUFFER_READER && (flags & KNH_STAGE_FLAG_READER_CH1); }
 };
+const char kCh1NoParams[] = "a KNH_STAGE_FLAG_READER_CH1 stage is the second output of a BufferReader, not a node: it has no parameters (address the reader stage)";
+inline bool is_reader_ch1(const knh_stage_desc& d) { return d.kind == KNH_STAGE_BUFFER_READER && (d.flags & KNH_STAGE_FLAG_READER_CH1); }
 
 // Which (stage kind, float parameter) pairs can be driven at audio rate (knh_stage_desc.ar_param): the setters restated on
 // the device (voice_stages.hpp, ar_set).

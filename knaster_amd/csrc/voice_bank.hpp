@@ -149,9 +149,11 @@ struct Bank final : knh_bank {
   uint32_t seg_max = 0;
   // BufferReader's pool of Buffers: one device allocation, entry k's samples from pool[k].off on (every start rounded up to
   // 64 samples); the host copies are staged in the entries until init.  A voice plays the entry buf_id[voice] says.
+  // Every entry has the channel count of the first one (1, or 2: interleaved frames); `off` counts samples, n_frames frames.
   F* d_buffer = nullptr;
-  struct PoolEntry { std::vector<F> samples; double sr = 0.0; uint32_t n_frames = 0, off = 0; };
+  struct PoolEntry { std::vector<F> samples; double sr = 0.0; uint32_t n_frames = 0, off = 0, channels = 1; };
   std::vector<PoolEntry> pool;
+  uint32_t pool_channels() const { return pool.empty() ? 0u : pool[0].channels; }
   std::vector<uint32_t> buf_id;                      // [voice], empty: every voice on entry 0
   // BufferReader shadows, [reader][voice]: start_frame, dur_frame, rate.  A chain may hold several readers (a graph voice
   // that sums two): each has a start, a length and a rate of its own, so a seconds-valued setter or a restart of one reads
@@ -161,7 +163,7 @@ struct Bank final : knh_bank {
     size_t k = 0;
     for (const StageInfo& T : stages) {
       if (&T == &S) break;
-      k += T.kind == KNH_STAGE_BUFFER_READER;
+      k += T.reader();  // (a reader's second output, KNH_STAGE_FLAG_READER_CH1, is no reader: it has no shadows)
     }
     return k * nv + v;
   }
@@ -200,11 +202,11 @@ struct Bank final : knh_bank {
     put(11, e.n_frames);
     if (linked) put2(12, base_rate);
   }
-  // the pool's size in samples with `n_frames` in place of entry `at` (at == pool.size(): one more entry), every entry padded to 64
-  uint64_t pool_samples_with(size_t at, size_t n_frames) const {
+  // the pool's size in samples with `n_samples` (frames x channels) in place of entry `at` (at == pool.size(): one more entry), every entry padded to 64
+  uint64_t pool_samples_with(size_t at, uint64_t n_samples) const {
     uint64_t total = 0;
-    for (size_t k = 0; k < pool.size(); ++k) total += ((k == at ? n_frames : pool[k].n_frames) + 63ull) & ~63ull;
-    if (at == pool.size()) total += (n_frames + 63ull) & ~63ull;
+    for (size_t k = 0; k < pool.size(); ++k) total += ((k == at ? n_samples : static_cast<uint64_t>(pool[k].n_frames) * pool[k].channels) + 63ull) & ~63ull;
+    if (at == pool.size()) total += (n_samples + 63ull) & ~63ull;
     return total;
   }
   void* d_delay = nullptr;        // SampleDelay rings: [voice][delay_stride] of F
@@ -343,26 +345,35 @@ struct Bank final : knh_bank {
   }
 
   // knh_bank_set_buffer (entry 0 of the pool, made or replaced) and knh_bank_add_buffer (one more entry)
-  int put_buffer(size_t at, const char* who, uint32_t stage, const void* samples, size_t n_frames, double sr) {
+  // (n_channels 2: Buffer::from_vec_interleaved, dsp/buffer.rs:70-78 -- n_frames * 2 samples, frame by frame)
+  int put_buffer(size_t at, const char* who, uint32_t stage, const void* samples, size_t n_frames, uint32_t n_channels, double sr) {
     if (initialised) return fail(KNH_ERR_INVALID_ARGUMENT, std::string(who) + " comes before knh_bank_init");
-    if (stage >= stages.size() || stages[stage].kind != KNH_STAGE_BUFFER_READER) return fail(KNH_ERR_INVALID_ARGUMENT, "not a BufferReader stage");
+    if (stage >= stages.size() || !stages[stage].reader()) return fail(KNH_ERR_INVALID_ARGUMENT, "not a BufferReader stage");
+    if (n_channels < 1 || n_channels > 2) return fail(KNH_ERR_INVALID_ARGUMENT, "a Buffer has one or two channels");
+    // the channel count is the pool's: the first entry fixes it (replacing the only entry may change it)
+    if (!pool.empty() && !(at == 0 && pool.size() == 1) && n_channels != pool_channels())
+      return fail(KNH_ERR_INVALID_ARGUMENT, pool_channels() == 2 ? "every Buffer of this pool has two channels (knh_bank_add_buffer_interleaved): the first entry fixes the pool's channel count"
+                                                               : "every Buffer of this pool has one channel: the first entry fixes the pool's channel count");
     if (!samples || n_frames == 0 || n_frames >= (1ull << 31) || !(sr > 0.0) || !std::isfinite(sr)) return fail(KNH_ERR_INVALID_ARGUMENT, "empty buffer or bad sample rate");
     // a voice's offset into the pool is one 32-bit slot word
-    if (pool_samples_with(at, n_frames) > 0xFFFFFFFFull) return fail(KNH_ERR_INVALID_ARGUMENT, "the pool of buffers would hold more than 2^32 - 1 samples");
-    std::vector<F> copy(static_cast<const F*>(samples), static_cast<const F*>(samples) + n_frames);  // (first: nothing changes if it does not fit)
+    const uint64_t n_samples = static_cast<uint64_t>(n_frames) * n_channels;
+    if (pool_samples_with(at, n_samples) > 0xFFFFFFFFull) return fail(KNH_ERR_INVALID_ARGUMENT, "the pool of buffers would hold more than 2^32 - 1 samples");
+    std::vector<F> copy(static_cast<const F*>(samples), static_cast<const F*>(samples) + n_samples);  // (first: nothing changes if it does not fit)
     if (at == pool.size()) pool.emplace_back();
     PoolEntry& e = pool[at];
     e.samples.swap(copy);
     e.sr = sr;
     e.n_frames = static_cast<uint32_t>(n_frames);
+    e.channels = n_channels;
     return KNH_OK;
   }
   int set_buffer(uint32_t stage, const void* samples, size_t n_frames, double sr) override {
-    return put_buffer(0, "knh_bank_set_buffer", stage, samples, n_frames, sr);
+    if (pool_channels() == 2) return fail(KNH_ERR_INVALID_ARGUMENT, "knh_bank_set_buffer makes a single-channel entry: every Buffer of this pool has two channels");
+    return put_buffer(0, "knh_bank_set_buffer", stage, samples, n_frames, 1, sr);
   }
-  int add_buffer(uint32_t stage, const void* samples, size_t n_frames, double sr, uint32_t* out_index) override {
+  int add_buffer(uint32_t stage, const void* samples, size_t n_frames, uint32_t n_channels, double sr, uint32_t* out_index) override {
     const size_t at = pool.size();
-    int rc = put_buffer(at, "knh_bank_add_buffer", stage, samples, n_frames, sr);
+    int rc = put_buffer(at, n_channels == 1 ? "knh_bank_add_buffer" : "knh_bank_add_buffer_interleaved", stage, samples, n_frames, n_channels, sr);
     if (rc == KNH_OK && out_index) *out_index = static_cast<uint32_t>(at);
     return rc;
   }
@@ -370,13 +381,13 @@ struct Bank final : knh_bank {
     if (!initialised && !pool.empty()) pool.pop_back();
   }
   uint32_t buffer_count(uint32_t stage) const override {
-    return stage < stages.size() && stages[stage].kind == KNH_STAGE_BUFFER_READER ? static_cast<uint32_t>(pool.size()) : 0u;
+    return stage < stages.size() && stages[stage].reader() ? static_cast<uint32_t>(pool.size()) : 0u;
   }
   // knh_bank_assign_buffers.  Before init: the entry each voice is constructed on (and, with `args`, its constructor
   // arguments).  After init: the voice's reader becomes a new one on that entry -- every slot of the stage is patched at the
   // first frame of the next launch, the way a parameter change is, and the shadows the seconds-valued setters read follow.
   int assign_buffers(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* ids, const double* args) override {
-    if (stage >= stages.size() || stages[stage].kind != KNH_STAGE_BUFFER_READER) return fail(KNH_ERR_INVALID_ARGUMENT, "not a BufferReader stage");
+    if (stage >= stages.size() || !stages[stage].reader()) return fail(KNH_ERR_INVALID_ARGUMENT, "not a BufferReader stage");
     if (count && (!voices || !ids)) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
     const StageInfo& S = stages[stage];
     if (initialised) {
@@ -495,14 +506,15 @@ struct Bank final : knh_bank {
         env_start.assign(nv, 0.0); env_nseg.assign(nv, 0); seg_max = n_max; seg_rows.assign(static_cast<size_t>(nv) * n_max * 3, 0.0);
       } break;
       case KNH_STAGE_BUFFER_READER: {
+        if (S.ch1()) break;  // the second output of a reader: nothing of its own
         if (pool.empty()) return fail(KNH_ERR_INVALID_ARGUMENT, "BufferReader stage without knh_bank_set_buffer or knh_bank_add_buffer");
         if (S.dcpb > 0) return fail(KNH_ERR_INVALID_ARGUMENT, "BufferReader cannot be wrapped in WrPreciseTiming here");
         if (reader_at(S, 0) == 0) {  // the chain's first reader: the shadows of all of them, the pool's layout
           size_t readers = 0;
-          for (const StageInfo& T : stages) readers += T.kind == KNH_STAGE_BUFFER_READER;
+          for (const StageInfo& T : stages) readers += T.reader();
           buf_start.assign(readers * nv, 0.0); buf_dur.assign(readers * nv, 0.0); buf_rate.assign(readers * nv, 0.0);
-          uint64_t off = 0;  // (put_buffer has kept the sum within 32 bits)
-          for (PoolEntry& e : pool) { e.off = static_cast<uint32_t>(off); off += (e.n_frames + 63ull) & ~63ull; }
+          uint64_t off = 0;  // in samples (put_buffer has kept the sum within 32 bits)
+          for (PoolEntry& e : pool) { e.off = static_cast<uint32_t>(off); off += (static_cast<uint64_t>(e.n_frames) * e.channels + 63ull) & ~63ull; }
         }
       } break;
       case KNH_STAGE_INPUT: uses_input = true; break;
@@ -597,6 +609,7 @@ struct Bank final : knh_bank {
         }
       } break;
       case KNH_STAGE_BUFFER_READER: {  // buffer.rs:40-57 (new, start_at), :106-115 (init)
+        if (S.ch1()) break;  // (no slots: the reader stage holds the node)
         reader_construct(S, v, a, [&](int rel, uint32_t word) { put(rel, static_cast<W>(word)); });
       } break;
       case KNH_STAGE_PHASOR: {  // osc.rs:181-188 (new), :197-200 (init: step = freq * (1 / sample_rate))
@@ -708,6 +721,33 @@ struct Bank final : knh_bank {
     if (desc.device >= 0) device = desc.device;
     else KNH_HIP(hipGetDevice(&device));
     KNH_HIP(hipSetDevice(device));
+    // The pool's channel count is known now.  A reader's second output needs a second channel (in the reference it reads the
+    // neighbouring sample and runs off the end); a mono reader on a pool of two-channel Buffers plays channel 0 of the
+    // interleaved frames (BufferReader<F, U1> on a stereo Buffer: index * num_channels + 0) -- a stage of its own
+    // (knh_dev::BufferReaderCh0, 'C' for 'F'), so the voice is fused now whatever was pre-built for its mono form.
+    for (const StageInfo& S : stages)
+      if (S.ch1() && pool_channels() == 1) return fail(KNH_ERR_INVALID_ARGUMENT, "a KNH_STAGE_FLAG_READER_CH1 stage needs a pool of two-channel Buffers (knh_bank_add_buffer_interleaved with n_channels = 2)");
+    // (a refused init changes nothing: the signature and the pre-built forms it drops come back unless init gets to its end)
+    struct KeepForms {
+      Bank* b;
+      std::string signature;
+      const knh::KernelEntry* entry;
+      const knh::PipeEntry* pipe;
+      bool pipe_pair;
+      const knh::WideEntry* wide;
+      int wide_waves;
+      bool armed;
+      ~KeepForms() {
+        if (!armed) return;
+        b->signature.swap(signature);
+        b->entry = entry; b->pipe = pipe; b->pipe_pair = pipe_pair; b->wide = wide; b->wide_waves = wide_waves;
+      }
+    } keep{this, signature, entry, pipe, pipe_pair, wide, wide_waves, false};
+    if (pool_channels() == 2 && signature.find('F') != std::string::npos) {
+      keep.armed = true;
+      std::replace(signature.begin(), signature.end(), 'F', 'C');
+      entry = nullptr; pipe = nullptr; pipe_pair = false; wide = nullptr; wide_waves = 0;
+    }
     // Chains without a pre-built pipelined kernel are fused now (hiprtc).  Up to two voice groups per CU the
     // pipelined form wins by a wide margin, so the chain is cut into at most three stage groups of similar cost
     // (estimated instructions per sample) and instantiated as voice_pipe_kernel; KNH_JIT_PIPE=0 keeps the
@@ -929,6 +969,7 @@ struct Bank final : knh_bank {
       };
       resident.setup(rs);
     }
+    keep.armed = false;
     initialised = true;
     return KNH_OK;
   }
@@ -1098,6 +1139,7 @@ struct Bank final : knh_bank {
     // little too large -- every parameter entry point comes through here (or through RankBank's copy of these checks).  Ahead of
     // the initialised check on purpose: the chain is known from knh_bank_create on (knaster_hip.h says so)
     if (stage < stages.size() && is_math1_kind(stages[stage].kind)) return fail(KNH_ERR_INVALID_ARGUMENT, "a KNH_STAGE_MATH1_* stage has no parameters");
+    if (stage < stages.size() && stages[stage].ch1()) return fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams);  // (the same rule: it is no node)
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (voice >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
     if (stage >= stages.size()) return fail(KNH_ERR_OUT_OF_RANGE, "stage out of range");

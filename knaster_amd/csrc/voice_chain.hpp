@@ -192,12 +192,21 @@ struct Math2 : StageDefaults {
 // Outs<R, L, RR> in its place: a voice with two CONNECTED OUTPUTS (knh_bank_connect_outputs; the reference's
 // to_graph_out_channels, graph_edit.rs:381-394) -- graph output 0 carries the signal in slot L, output 1 the one in slot RR;
 // the host keeps both slots out of every later stage's hands.
+// At2<S, A, B, O, O2>: a node with TWO OUTPUT SIGNALS (BufferReader<F, U2>: one read pointer, a signal per channel) -- the
+// stage writes slot O and slot O2 every frame (S::tick2).  The second slot has a place of its own because B is taken when
+// the node's rate is linked to a signal.  The descriptor stage that stands for the second output
+// (KNH_STAGE_FLAG_READER_CH1) is no device stage: it only names O2.  Out1<R, K> at the end of the list: the voice's one
+// signal is the one in slot K (a voice whose last descriptor stage is such a second output).
 template <typename S, int A, int B, int O> struct At {};
+template <typename S, int A, int B, int O, int O2> struct At2 {};
 template <int R> struct Slots {};
+template <int R, int K> struct Out1 {};
 template <int R, int L, int RR> struct Outs {};
 template <typename X> struct NodeOf { static constexpr bool dag = false; };
-template <typename S, int A, int B, int O> struct NodeOf<At<S, A, B, O>> { typedef S stage; static constexpr int a = A, b = B, o = O; static constexpr bool dag = true; };
+template <typename S, int A, int B, int O> struct NodeOf<At<S, A, B, O>> { typedef S stage; static constexpr int a = A, b = B, o = O, o2 = -1; static constexpr bool dag = true; };
+template <typename S, int A, int B, int O, int O2> struct NodeOf<At2<S, A, B, O, O2>> { typedef S stage; static constexpr int a = A, b = B, o = O, o2 = O2; static constexpr bool dag = true; };
 template <int R> struct NodeOf<Slots<R>> { static constexpr bool dag = true; };
+template <int R, int K> struct NodeOf<Out1<R, K>> { static constexpr bool dag = true; };
 template <int R, int L, int RR> struct NodeOf<Outs<R, L, RR>> { static constexpr bool dag = true; };
 
 template <typename F, bool FMA, int BASE, int R, int LAST, typename... Ns> struct DagChain;
@@ -228,6 +237,15 @@ struct DagChain<F, FMA, BASE, R, LAST, Slots<R2>> : DagEnd<F, BASE, R> {
   static constexpr bool kStereo = false;
   static constexpr int kOutL = LAST, kOutR = LAST;
 };
+// ... Out1<R, K>: the voice's signal is the one in slot K
+template <typename F, bool FMA, int BASE, int R, int LAST, int R2, int K>
+struct DagChain<F, FMA, BASE, R, LAST, Out1<R2, K>> : DagEnd<F, BASE, R> {
+  static_assert(R == R2, "the slot count is the list's last entry");
+  static_assert(K >= 0 && K < R, "signal slots are 0 .. R-1");
+  static constexpr int kOut = K;
+  static constexpr bool kStereo = false;
+  static constexpr int kOutL = K, kOutR = K;
+};
 // ... or Outs<R, L, RR>: the slots of the two connected outputs
 template <typename F, bool FMA, int BASE, int R, int LAST, int R2, int L, int RR>
 struct DagChain<F, FMA, BASE, R, LAST, Outs<R2, L, RR>> : DagEnd<F, BASE, R> {
@@ -240,8 +258,9 @@ struct DagChain<F, FMA, BASE, R, LAST, Outs<R2, L, RR>> : DagEnd<F, BASE, R> {
 template <typename F, bool FMA, int BASE, int R, int LAST, typename N0, typename... Rest>
 struct DagChain<F, FMA, BASE, R, LAST, N0, Rest...> {
   typedef typename NodeOf<N0>::stage S0;
-  static constexpr int A = NodeOf<N0>::a, B = NodeOf<N0>::b, O = NodeOf<N0>::o;
-  static_assert(A < R && B < R && O >= 0 && O < R, "signal slots are 0 .. R-1");
+  static constexpr int A = NodeOf<N0>::a, B = NodeOf<N0>::b, O = NodeOf<N0>::o, O2 = NodeOf<N0>::o2;
+  static_assert(A < R && B < R && O >= 0 && O < R && O2 < R, "signal slots are 0 .. R-1");
+  static_assert(O2 < 0 || O2 != O, "the two outputs of a node are two slots");
   static_assert(!S0::kBinary || (A >= 0 && B >= 0), "a MathUGen of two signals reads both");
   static_assert(S0::kArParam < 0 || B >= 0, "an audio-rate parameter names the signal that drives it");
   typedef DagChain<F, FMA, BASE + S0::kSlots, R, O, Rest...> RestT;
@@ -264,7 +283,10 @@ struct DagChain<F, FMA, BASE, R, LAST, N0, Rest...> {
     rest.store(s, stride);
   }
   template <int T> __device__ __forceinline__ void run_tile(F (&sig)[R][T], const Ctx& c, u32 frame0) {
-    if constexpr (S0::kBinary) {
+    if constexpr (O2 >= 0) {
+#pragma unroll
+      for (int j = 0; j < T; ++j) two_out(sig[O][j], sig[O2][j], B >= 0 ? sig[B >= 0 ? B : 0][j] : (F)0, c, frame0 + (u32)j);
+    } else if constexpr (S0::kBinary) {
 #pragma unroll
       for (int j = 0; j < T; ++j) sig[O][j] = S0::template apply<F>(sig[A][j], sig[B][j]);
     } else if constexpr (S0::kArParam >= 0) {
@@ -288,8 +310,18 @@ struct DagChain<F, FMA, BASE, R, LAST, N0, Rest...> {
     if constexpr (S0::kIsEnv && S0::kHasSeg) frame = r.seg;
     return S0::template tick<F, FMA>(r, A >= 0 ? a : (F)0, c, frame, mark);
   }
+  // one frame of a node with two outputs (a source: it reads no signal; b = the sample of the signal that drives its
+  // audio-rate parameter, if one does -- taken by value, so the node may write the slot it came from)
+  __device__ __forceinline__ void two_out(F& y0, F& y1, F b, const Ctx& c, u32 frame) {
+    if constexpr (S0::kArParam >= 0) {
+      S0::template ar_set<F, (S0::kArParam >= 0 ? S0::kArParam : 0)>(r, b, c);
+      if constexpr (S0::kIsEnv && S0::kHasSeg) frame = r.seg;  // (the wrapper's one-sample "block": ar_one)
+    }
+    S0::template tick2<F, FMA>(r, c, frame, mark, y0, y1);
+  }
   __device__ __forceinline__ void run_one(F (&sig)[R], const Ctx& c, u32 frame) {
-    if constexpr (S0::kBinary) sig[O] = S0::template apply<F>(sig[A], sig[B]);
+    if constexpr (O2 >= 0) two_out(sig[O], sig[O2], B >= 0 ? sig[B >= 0 ? B : 0] : (F)0, c, frame);
+    else if constexpr (S0::kBinary) sig[O] = S0::template apply<F>(sig[A], sig[B]);
     else if constexpr (S0::kArParam >= 0) sig[O] = ar_one(sig[A >= 0 ? A : 0], sig[B >= 0 ? B : 0], c, frame);
     else sig[O] = S0::template tick<F, FMA>(r, A >= 0 ? sig[A >= 0 ? A : 0] : (F)0, c, frame, mark);
     rest.run_one(sig, c, frame);
@@ -358,6 +390,7 @@ template <typename... S> struct SlotCount { static constexpr int value = 0; };
 template <typename S0, typename... S> struct SlotCount<S0, S...> { static constexpr int value = SlotCount<S...>::value; };
 template <int R> struct SlotCount<Slots<R>> { static constexpr int value = R; };
 template <int R, int L, int RR> struct SlotCount<Outs<R, L, RR>> { static constexpr int value = R; };
+template <int R, int K> struct SlotCount<Out1<R, K>> { static constexpr int value = R; };
 // the kernel's chain type: a plain chain unless the list is a graph's
 template <bool DAG, typename F, bool FMA, typename... S> struct ChainSelect { typedef Chain<F, FMA, 0, S...> type; };
 template <typename F, bool FMA, typename... S> struct ChainSelect<true, F, FMA, S...> { typedef DagChain<F, FMA, 0, SlotCount<S...>::value, 0, S...> type; };

@@ -801,24 +801,39 @@ struct BufferReader : StageDefaults {
     const u64 b = __builtin_bit_cast(u64, r.rp);
     s[0] = (W)(u32)b; s[st] = (W)(u32)(b >> 32); s[8 * st] = (W)r.finished;
   }
-  template <typename F, bool FMA>
-  static __device__ __forceinline__ F tick(Regs<F>& r, F, const Ctx& c, u32 frame, u32& done_frame) {
-    bind<F>(r, c);
-    if (r.finished || r.n == 0u) return (F)0;
-    // get_linear_interp_f64: mix = fract(index); buffer[i] * (1 - mix) + buffer[(i + 1) % len] * mix.  `index as usize`
-    // saturates at 0; an index past the end is undefined behaviour in the reference, clamped here.
+  // get_linear_interp_f64: mix = fract(index); buffer[i] * (1 - mix) + buffer[(i + 1) % len] * mix.  `index as usize`
+  // saturates at 0; an index past the end is undefined behaviour in the reference, clamped here.  i, i1: the two FRAMES.
+  template <typename F>
+  static __device__ __forceinline__ F position(const Regs<F>& r, u32& i, u32& i1) {
     const double ip = __builtin_trunc(r.rp);
-    const F mix = (F)(r.rp - ip);
-    u32 i = r.rp > 0.0 ? (r.rp < 4294967040.0 ? (u32)r.rp : 0xFFFFFFFFu) : 0u;
+    i = r.rp > 0.0 ? (r.rp < 4294967040.0 ? (u32)r.rp : 0xFFFFFFFFu) : 0u;
     if (i >= r.n) i = r.n - 1u;
-    const u32 i1 = i + 1u == r.n ? 0u : i + 1u;
-    const F y = r.buf[i] * ((F)1 - mix) + r.buf[i1] * mix;
+    i1 = i + 1u == r.n ? 0u : i + 1u;
+    return (F)(r.rp - ip);
+  }
+  // the read pointer's step and what happens at the end (process_block, :166-173)
+  template <typename F>
+  static __device__ __forceinline__ void advance(Regs<F>& r, u32 frame, u32& done_frame) {
     r.rp += r.step;
-    if (r.rp >= r.end) {  // process_block, :166-173
+    if (r.rp >= r.end) {
       if (r.looping) { r.rp = r.start; }
       else { r.finished = 1u; done_frame = frame + 1u - r.seg; }
     }
+  }
+  // one sample of channel 0 of a Buffer whose frames are NCH samples apart (`index * num_channels + 0`, dsp/buffer.rs:100-110)
+  template <typename F, int NCH>
+  static __device__ __forceinline__ F tick_ch0(Regs<F>& r, const Ctx& c, u32 frame, u32& done_frame) {
+    bind<F>(r, c);
+    if (r.finished || r.n == 0u) return (F)0;
+    u32 i, i1;
+    const F mix = position<F>(r, i, i1);
+    const F y = r.buf[(size_t)i * NCH] * ((F)1 - mix) + r.buf[(size_t)i1 * NCH] * mix;
+    advance<F>(r, frame, done_frame);
     return y;
+  }
+  template <typename F, bool FMA>
+  static __device__ __forceinline__ F tick(Regs<F>& r, F, const Ctx& c, u32 frame, u32& done_frame) {
+    return tick_ch0<F, 1>(r, c, frame, done_frame);
   }
   template <typename F, bool FMA, int T>
   static __device__ __forceinline__ void tick_tile(Regs<F>& r, F (&x)[T], const Ctx& c, u32 frame0, u32& done_frame) {
@@ -845,28 +860,81 @@ struct BufferReader : StageDefaults {
     }
   }
 };
+// A mono reader (BufferReader<F, U1>) on a pool of TWO-channel Buffers: channel 0 of the interleaved frames, the reference's
+// `index * num_channels + 0`.  Slot 10 is still the offset in samples, slot 11 the length in frames.
+struct BufferReaderCh0 : BufferReader {
+  template <typename F, bool FMA>
+  static __device__ __forceinline__ F tick(Regs<F>& r, F, const Ctx& c, u32 frame, u32& done_frame) {
+    return BufferReader::tick_ch0<F, 2>(r, c, frame, done_frame);
+  }
+  template <typename F, bool FMA, int T>
+  static __device__ __forceinline__ void tick_tile(Regs<F>& r, F (&x)[T], const Ctx& c, u32 frame0, u32& done_frame) {
+#pragma unroll
+    for (int j = 0; j < T; ++j) x[j] = tick<F, FMA>(r, x[j], c, frame0 + j, done_frame);
+  }
+};
+// BufferReader<F, U2> -- buffer.rs:122-190 with two channels: ONE read pointer, TWO output signals (At2 in voice_chain.hpp
+// names the second signal's slot).  Frame i of a two-channel Buffer is the two adjacent samples 2i, 2i + 1; every entry of
+// the pool starts at a multiple of 64 samples, so the pair is naturally aligned and is fetched with one load of two samples
+// (8 bytes in f32, 16 in f64), and so is frame i1: two loads per output frame where two mono readers make four.  Channel c
+// is buf[2i + c] * (1 - mix) + buf[2 * i1 + c] * mix; the wrap to frame 0, the clamp, the end of a one-shot voice and the
+// zeros of a finished one are the mono reader's (position, advance).  Same slots, same events.
+struct BufferReader2 : BufferReader {
+  template <typename F> struct Pair { typedef F type __attribute__((ext_vector_type(2))); };
+  template <typename F, bool FMA>
+  static __device__ __forceinline__ void tick2(Regs<F>& r, const Ctx& c, u32 frame, u32& done_frame, F& y0, F& y1) {
+    bind<F>(r, c);
+    if (r.finished || r.n == 0u) { y0 = (F)0; y1 = (F)0; return; }
+    u32 i, i1;
+    const F mix = position<F>(r, i, i1);
+    typedef typename Pair<F>::type P;
+    const P* frames = reinterpret_cast<const P*>(r.buf);
+    const P a = frames[i], b = frames[i1];
+    const F w = (F)1 - mix;
+    y0 = a.x * w + b.x * mix;
+    y1 = a.y * w + b.y * mix;
+    advance<F>(r, frame, done_frame);
+  }
+  // (as a one-signal stage -- never instantiated by a graph that names the second slot -- it is channel 0)
+  template <typename F, bool FMA>
+  static __device__ __forceinline__ F tick(Regs<F>& r, F, const Ctx& c, u32 frame, u32& done_frame) {
+    return BufferReader::tick_ch0<F, 2>(r, c, frame, done_frame);
+  }
+  template <typename F, bool FMA, int T>
+  static __device__ __forceinline__ void tick_tile(Regs<F>& r, F (&x)[T], const Ctx& c, u32 frame0, u32& done_frame) {
+#pragma unroll
+    for (int j = 0; j < T; ++j) x[j] = tick<F, FMA>(r, x[j], c, frame0 + j, done_frame);
+  }
+};
 // BufferReader with `rate` driven at audio rate (ArP<BufferReaderP, 0>): BufferReader::rate (buffer.rs:76-78) stores the
 // value, and every sample steps by base_rate * rate (:137) -- so base_rate (Buffer::buf_rate_scale of the voice's own Buffer)
 // is device state too, written by the host with the other slots of a reader (init, and a swap to another pool entry).
 // Under the wrapper the reader runs through UGen::process, one sample at a time: a one-shot voice marks done at frame 0
 // of that sample's "block" (:143), not at i + 1 as process_block does (:172).
-// slots: 0..11 as BufferReader, 12,13 base_rate
-struct BufferReaderP : BufferReader {
+// slots: 0..11 as BufferReader, 12,13 base_rate.  Base: the reader it wraps (mono, channel 0 of two, or both channels).
+template <typename Base>
+struct BufferReaderPT : Base {
   static constexpr int kSlots = 14;
-  template <typename F> struct Regs : BufferReader::Regs<F> { double base; };
+  template <typename F> struct Regs : Base::template Regs<F> { double base; };
   template <typename F, typename W>
   static __device__ __forceinline__ void load(Regs<F>& r, const W* s, long st) {
-    BufferReader::load<F, W>(r, s, st);
-    r.base = ld2(s, st, 12);
+    Base::template load<F, W>(r, s, st);
+    r.base = Base::ld2(s, st, 12);
   }
   template <typename F, int P>
   static __device__ __forceinline__ void ar_set(Regs<F>& r, F v, const Ctx&) { r.step = r.base * (double)v; }
   template <typename F, bool FMA>
   static __device__ __forceinline__ F tick(Regs<F>& r, F x, const Ctx& c, u32 frame, u32& done_frame) {
     u32 mark = 0xFFFFFFFFu;
-    const F y = BufferReader::tick<F, FMA>(r, x, c, frame, mark);
+    const F y = Base::template tick<F, FMA>(r, x, c, frame, mark);
     if (mark != 0xFFFFFFFFu) done_frame = mark - 1u;  // mark_done(0): the frame the wrapper's caller handed in, not the one after it
     return y;
+  }
+  template <typename F, bool FMA>
+  static __device__ __forceinline__ void tick2(Regs<F>& r, const Ctx& c, u32 frame, u32& done_frame, F& y0, F& y1) {
+    u32 mark = 0xFFFFFFFFu;
+    Base::template tick2<F, FMA>(r, c, frame, mark, y0, y1);
+    if (mark != 0xFFFFFFFFu) done_frame = mark - 1u;
   }
   template <typename F, bool FMA, int T>
   static __device__ __forceinline__ void tick_tile(Regs<F>& r, F (&x)[T], const Ctx& c, u32 frame0, u32& done_frame) {
@@ -875,12 +943,15 @@ struct BufferReaderP : BufferReader {
   }
   template <typename F>
   static __device__ __forceinline__ void on_event(Regs<F>& r, u32 op, u32 rel, u64 bits, u32 frame) {
-    if (rel < 12u) { BufferReader::on_event<F>(r, op, rel, bits, frame); return; }
+    if (rel < 12u) { Base::template on_event<F>(r, op, rel, bits, frame); return; }
     if ((op & 0x7Fu) != EV_SET) return;
     const u64 b = __builtin_bit_cast(u64, r.base), w = (u64)(u32)bits;
     r.base = __builtin_bit_cast(double, rel == 12u ? ((b & 0xFFFFFFFF00000000ull) | w) : ((b & 0x00000000FFFFFFFFull) | (w << 32)));
   }
 };
+typedef BufferReaderPT<BufferReader> BufferReaderP;
+typedef BufferReaderPT<BufferReaderCh0> BufferReaderCh0P;
+typedef BufferReaderPT<BufferReader2> BufferReader2P;
 
 // SinNumeric -- osc.rs:222-271.  slots: 0 phase, 1 phase_offset, 2 phase_increment
 struct SinNum : StageDefaults {

@@ -102,6 +102,7 @@ struct UGenSpec {
   std::shared_ptr<const void> buffer;
   const void* buffer_samples = nullptr;
   size_t buffer_frames = 0, buffer_word = 0;  // buffer_word: sizeof(F) of its samples
+  uint32_t buffer_channels = 1;               // 2: interleaved frames (Buffer::from_vec_interleaved)
   double buffer_sample_rate = 0.0;
   // wrappers_core.rs:26-111
   UGenSpec wr_mul(double v) && { wrappers.emplace_back(KNH_STAGE_WR_MUL, v); return std::move(*this); }
@@ -164,27 +165,41 @@ inline UGenSpec Envelope(double start_value, const std::vector<EnvelopeSegment>&
   s.is_env = true;
   return s;
 }
-// Buffer::from_vec(samples, sample_rate) -- dsp/buffer.rs:58-66 (single channel); shared between the readers made on it
+// Buffer::from_vec(samples, sample_rate) -- dsp/buffer.rs:58-66 (single channel) -- and
+// Buffer::from_vec_interleaved(samples, num_channels, sample_rate) -- :70-78 (frame by frame; one or two channels here);
+// shared between the readers made on it
 template <typename F>
 struct Buffer {
   std::vector<F> samples;
   double sample_rate = 48000.0;
+  uint32_t num_channels = 1;
+  size_t num_frames() const { return samples.size() / num_channels; }
   static std::shared_ptr<const Buffer<F>> from_vec(std::vector<F> samples, double sample_rate) {
+    return from_vec_interleaved(std::move(samples), 1, sample_rate);
+  }
+  static std::shared_ptr<const Buffer<F>> from_vec_interleaved(std::vector<F> samples, uint32_t num_channels, double sample_rate) {
+    if (num_channels < 1 || num_channels > 2) throw std::runtime_error("Buffer: one or two channels");
+    if (samples.size() % num_channels != 0) throw std::runtime_error("Buffer::from_vec_interleaved: samples holds whole frames");
     auto b = std::make_shared<Buffer<F>>();
     b->samples = std::move(samples);
     b->sample_rate = sample_rate;
+    b->num_channels = num_channels;
     return b;
   }
 };
 // BufferReader::<F, U1>::new(buffer, rate, looping).start_at(start_s) -- buffer.rs:43-57.  Voices of one chain shape share a
 // bank whatever Buffer each was made on: the bank's pool holds every distinct Buffer once (knh_bank_add_buffer) and each voice
 // reads its own (knh_bank_assign_buffers).
+// On a two-channel Buffer it is BufferReader::<F, U2>::new(..) (knaster/examples/buffer_player.rs): ONE node whose handle has
+// two channels.  It is traced into the reader stage (channel 0) and a KNH_STAGE_FLAG_READER_CH1 stage (channel 1).
 template <typename F>
 inline UGenSpec BufferReader(std::shared_ptr<const Buffer<F>> buffer, double rate, bool looping, double start_s = 0.0) {
   if (!buffer || buffer->samples.empty()) throw std::runtime_error("BufferReader needs a Buffer with samples");
   UGenSpec s(KNH_STAGE_BUFFER_READER, {rate, looping ? 1.0 : 0.0, start_s});
   s.buffer_samples = buffer->samples.data();
-  s.buffer_frames = buffer->samples.size();
+  s.buffer_frames = buffer->num_frames();
+  s.buffer_channels = buffer->num_channels;
+  s.outputs = static_cast<uint16_t>(buffer->num_channels);
   s.buffer_word = sizeof(F);
   s.buffer_sample_rate = buffer->sample_rate;
   s.buffer = std::move(buffer);
@@ -206,9 +221,13 @@ struct NodeRec {
   uint16_t math_kind = 0;   // MATH: KNH_STAGE_{MUL,ADD,SUB,DIV}_CONST for op with a Constant; 0xFFFF = signal (op) signal
   uint16_t math2_kind = KNH_STAGE_MATH_MUL;  // MATH of two signals: KNH_STAGE_MATH_{ADD,SUB,MUL,DIV,POW}
   int in0 = -1, in1 = -1;   // input edges (node ids)
+  int in0_ch = 0, in1_ch = 0;  // ... and the output channel of that node the edge starts at (a two-channel BufferReader's 1)
   int link_source = -1, link_param = -1;  // audio-rate parameter edge (graph_edit.rs:735-754)
   // where the node ended up after commit
   int bank = -1, voice = -1, stage = -1;
+  // a Constant that scales several channels (`play * amp.out([0, 0])`) stands behind a MUL_CONST stage per channel: the
+  // stages after the first, so that amp.param("value") reaches every channel as the reference's one Constant does
+  std::vector<int> more_stages;
 };
 
 struct SchedulingEvent {  // scheduling.rs:29-36
@@ -290,6 +309,7 @@ class Sig {  // SH / DH of graph_edit.rs:266-277: one or more output channels of
     Parameter(Graph<F>* graph, int node, uint32_t index) : graph_(graph), node_(node), index_(index) {}
     void set(double v) { graph_->schedule({node_, index_, KNH_VALUE_FLOAT, v, 0, false, {}}); }
     void set(int64_t v) { graph_->schedule({node_, index_, KNH_VALUE_INTEGER, 0, v, false, {}}); }
+    void set(bool v) { graph_->schedule({node_, index_, KNH_VALUE_BOOL, 0, v ? 1 : 0, false, {}}); }  // PBool: BufferReader's "looping"
     void set_at(double v, Time t) { graph_->schedule({node_, index_, KNH_VALUE_FLOAT, v, 0, true, t}); }
     void trig() { graph_->schedule({node_, index_, KNH_VALUE_TRIGGER, 0, 0, false, {}}); }
     // param.smooth(ParameterSmoothing::Linear(seconds)) / ::None (graph_edit.rs:1773-1786); needs .smooth_params()
@@ -322,7 +342,9 @@ inline const char* const* stage_param_names(uint16_t kind, int* n) {
   static const char* seg[] = {"time_scale", "jump_to_segment", "t_restart", "t_stop"};
   static const char* dly[] = {"delay_time"};
   static const char* frq[] = {"freq"};
+  static const char* rdr[] = {"rate", "looping", "start_s", "duration_s", "end_s", "t_restart"};  // buffer.rs:62-103
   switch (kind) {
+    case KNH_STAGE_BUFFER_READER: *n = 6; return rdr;
     case KNH_STAGE_PHASOR: case KNH_STAGE_RANDOM_LIN: *n = 1; return frq;
     case KNH_STAGE_PAN2: { static const char* pan[] = {"pan"}; *n = 1; return pan; }
     case KNH_STAGE_POLYBLEP: { static const char* pb[] = {"freq", "pulse_width", "waveform"}; *n = 3; return pb; }
@@ -406,11 +428,13 @@ class Graph {
       const uint16_t drv = trace(x.link_source, p, visited, done);
       return {static_cast<uint16_t>(x.link_param + 1), drv};
     };
+    // an operand of a MathUGen: the signal of output channel in*_ch of node in*
+    auto operand = [&](bool first) -> uint16_t { return trace_channel(first ? n.in0 : n.in1, first ? n.in0_ch : n.in1_ch, p, visited, done); };
     if (n.type == NodeRec::MATH) {
       if (n.math_kind != 0xFFFF) {  // signal (op) Constant: graph_edit.rs:1036-1066
         const NodeRec& c = nodes_[static_cast<size_t>(n.in1)];
         const auto ar = ar_edge(c);
-        const uint16_t src = trace(n.in0, p, visited, done);
+        const uint16_t src = operand(true);
         push_stage(p, n.math_kind, c.spec.smooth_params_ ? KNH_STAGE_FLAG_SMOOTH_PARAMS : 0, c.spec.precise_timing_, n.in1, c.spec.args, in_of(src), ar.second, ar.first);
         visited.push_back(n.in1);
         return finish();
@@ -425,7 +449,7 @@ class Graph {
         const NodeRec& e = nodes_[static_cast<size_t>(env)];
         if (!e.spec.wrappers.empty()) throw GraphError("wrappers on an envelope inside a product are not fused");
         const auto ar = ar_edge(e);
-        const uint16_t src = trace(env == n.in1 ? n.in0 : n.in1, p, visited, done);
+        const uint16_t src = operand(env == n.in1);
         push_stage(p, e.spec.kind, e.spec.smooth_params_ ? KNH_STAGE_FLAG_SMOOTH_PARAMS : 0, e.spec.precise_timing_, env, e.spec.args, in_of(src), ar.second, ar.first);
         visited.push_back(env);
         return finish();
@@ -439,7 +463,7 @@ class Graph {
         const NodeRec& c = nodes_[static_cast<size_t>(cn)];
         if (!c.spec.wrappers.empty()) throw GraphError("wrappers on a Constant operand are not fused");
         const auto ar = ar_edge(c);
-        const uint16_t src = trace(b_const ? n.in0 : n.in1, p, visited, done);
+        const uint16_t src = operand(b_const);
         const uint16_t kind = n.math2_kind == KNH_STAGE_MATH_MUL ? KNH_STAGE_MUL_CONST : n.math2_kind == KNH_STAGE_MATH_ADD ? KNH_STAGE_ADD_CONST
                             : n.math2_kind == KNH_STAGE_MATH_SUB ? KNH_STAGE_SUB_CONST : n.math2_kind == KNH_STAGE_MATH_DIV ? KNH_STAGE_DIV_CONST : KNH_STAGE_POW_CONST;
         push_stage(p, kind, c.spec.smooth_params_ ? KNH_STAGE_FLAG_SMOOTH_PARAMS : 0, c.spec.precise_timing_, cn, c.spec.args, in_of(src), ar.second, ar.first);
@@ -447,8 +471,8 @@ class Graph {
         return finish();
       }
       // two signals of the voice: MathUGen<_, U1, Op> with both operands named
-      const uint16_t sa = trace(n.in0, p, visited, done);
-      const uint16_t sb = trace(n.in1, p, visited, done);
+      const uint16_t sa = operand(true);
+      const uint16_t sb = operand(false);
       push_stage(p, n.math2_kind, 0, 0, -1, {}, sa, sb);
       return finish();
     }
@@ -469,8 +493,27 @@ class Graph {
     }
     if (s.smooth_params_) flags |= KNH_STAGE_FLAG_SMOOTH_PARAMS;
     push_stage(p, s.kind, flags, s.precise_timing_, node, s.args, input, ar.second, ar.first);
+    if (s.kind == KNH_STAGE_BUFFER_READER && s.outputs == 2) {
+      // BufferReader<F, U2>: the node's second output is a stage of its own that names the reader stage
+      // (KNH_STAGE_FLAG_READER_CH1; no node behind it: parameters address the reader stage)
+      if (!s.wrappers.empty()) throw GraphError("wrappers on a two-channel BufferReader are not fused (use `* value` per channel)");
+      const uint16_t name = finish();
+      push_stage(p, KNH_STAGE_BUFFER_READER, KNH_STAGE_FLAG_READER_CH1, 0, -1, {}, name);
+      done[second_output_key(node)] = static_cast<uint16_t>(p.stages.size());
+      return name;
+    }
     for (auto& w : s.wrappers) push_stage(p, w.first, 0, 0, node, {w.second});
     return finish();
+  }
+  // The signal of output channel `channel` of `node`: channel 1 of a two-channel BufferReader is its second-output stage
+  // (kept in `done` under a key no node id has); every other node has one signal here (a Pan2's two go to the graph outputs).
+  static int second_output_key(int node) { return -2 - node; }
+  uint16_t trace_channel(int node, int channel, ChainPlan& p, std::vector<int>& visited, std::map<int, uint16_t>& done) {
+    const uint16_t name = trace(node, p, visited, done);
+    if (channel == 0) return name;
+    auto second = done.find(second_output_key(node));
+    if (channel != 1 || second == done.end()) throw GraphError("a node's output channel that is not a signal of the voice");
+    return second->second;
   }
   static void push_stage(ChainPlan& p, uint16_t kind, uint16_t flags, uint16_t dcpb, int node, std::vector<double> args, uint16_t input = 0,
                          uint16_t input2 = 0, uint16_t ar_param = 0) {
@@ -495,21 +538,29 @@ class Graph {
       // (`.out([0,0])`), the two outputs of a Pan2 on the two graph outputs, in order, or two different signals
       // (`(l | r).to_graph_out()`): one voice holding both subgraphs, a shared node traced once, its two outputs connected
       if (conn.size() != outputs_) throw GraphError("to_graph_out(): channel count does not match the graph outputs");
-      bool pan = false, same = true;
+      // ... or the two channels of a two-channel BufferReader, directly or through a `* value` each
+      bool pan = false, same_node = true, same = true;
       for (size_t c = 0; c < conn.size(); ++c) {
         if (conn[c].first < 0) throw GraphError("to_graph_out_channels(): a graph output of the voice has no signal");
         const NodeRec& x = nodes_[static_cast<size_t>(conn[c].first)];
         pan = pan || (x.type == NodeRec::UGEN && x.spec.kind == KNH_STAGE_PAN2);
-        same = same && conn[c].first == conn[0].first;
+        same_node = same_node && conn[c].first == conn[0].first;
+        same = same && conn[c] == conn[0];
       }
-      for (size_t c = 0; c < conn.size(); ++c)
-        if (conn[c].second != (pan ? static_cast<int>(c) : 0) || (pan && !same)) throw GraphError("a Pan2's outputs go to graph outputs 0 and 1, in order");
+      for (size_t c = 0; c < conn.size(); ++c) {
+        const NodeRec& x = nodes_[static_cast<size_t>(conn[c].first)];
+        const bool reader2 = x.type == NodeRec::UGEN && x.spec.kind == KNH_STAGE_BUFFER_READER && x.spec.outputs == 2;
+        if (pan && (conn[c].second != static_cast<int>(c) || !same_node)) throw GraphError("a Pan2's outputs go to graph outputs 0 and 1, in order");
+        if (!pan && conn[c].second != 0 && !(reader2 && conn[c].second == 1))
+          throw GraphError("to_graph_out(): the node has no such output channel (a two-channel BufferReader has channels 0 and 1, every other node one signal)");
+      }
       if (pan && outputs_ != 2) throw GraphError("a Pan2 voice needs a stereo graph");
+      if (pan) same = true;  // (one stage makes both graph outputs)
       Voice v;
       std::map<int, uint16_t> done;
-      const uint16_t left = trace(conn[0].first, v.plan, v.nodes, done);
+      const uint16_t left = pan ? trace(conn[0].first, v.plan, v.nodes, done) : trace_channel(conn[0].first, conn[0].second, v.plan, v.nodes, done);
       if (!same) {
-        const uint16_t right = trace(conn[1].first, v.plan, v.nodes, done);
+        const uint16_t right = trace_channel(conn[1].first, conn[1].second, v.plan, v.nodes, done);
         v.plan.out_stage[0] = left - 1;  // (a signal's name is 1 + the stage whose output it is)
         v.plan.out_stage[1] = right - 1;
       }
@@ -537,6 +588,9 @@ class Graph {
           if (node < 0) continue;  // a MathUGen of two signals: no parameters, found through v.nodes below
           NodeRec& nr = nodes_[static_cast<size_t>(node)];
           if (nr.bank < 0) { nr.bank = bank_index; nr.voice = static_cast<int>(vi); nr.stage = static_cast<int>(s); }
+          else if (nr.type == NodeRec::UGEN && nr.spec.is_constant && nr.bank == bank_index && nr.voice == static_cast<int>(vi) && nr.stage >= 0 &&
+                   nr.stage != static_cast<int>(s))
+            nr.more_stages.push_back(static_cast<int>(s));
         }
         for (int node : v.nodes) {
           NodeRec& nr = nodes_[static_cast<size_t>(node)];
@@ -571,7 +625,7 @@ class Graph {
         }
         for (size_t s = 0; s < b.plan.stages.size(); ++s) {
           // reader voices: every distinct Buffer once in the bank's pool, in order of first appearance; each voice on its own
-          if (b.plan.stages[s].kind != KNH_STAGE_BUFFER_READER) continue;
+          if (b.plan.stages[s].kind != KNH_STAGE_BUFFER_READER || (b.plan.stages[s].flags & KNH_STAGE_FLAG_READER_CH1)) continue;
           std::vector<const void*> pooled;
           std::vector<uint32_t> vs, ids;
           for (size_t vi = 0; vi < members.size(); ++vi) {
@@ -580,7 +634,11 @@ class Graph {
             size_t id = static_cast<size_t>(std::find(pooled.begin(), pooled.end(), spec.buffer_samples) - pooled.begin());
             if (id == pooled.size()) {
               uint32_t index = 0;
-              check(b, knh_bank_add_buffer(b.h, static_cast<uint32_t>(s), spec.buffer_samples, spec.buffer_frames, spec.buffer_sample_rate, &index));
+              // (a one-channel Buffer through the older call, to the bit the same entry)
+              check(b, spec.buffer_channels == 1
+                           ? knh_bank_add_buffer(b.h, static_cast<uint32_t>(s), spec.buffer_samples, spec.buffer_frames, spec.buffer_sample_rate, &index)
+                           : knh_bank_add_buffer_interleaved(b.h, static_cast<uint32_t>(s), spec.buffer_samples, spec.buffer_frames, spec.buffer_channels,
+                                                             spec.buffer_sample_rate, &index));
               pooled.push_back(spec.buffer_samples);
               id = index;
             }
@@ -631,26 +689,40 @@ class GraphEdit {
   Sig<F> math_const(const Sig<F>& s, uint16_t kind, double c) {  // graph_edit.rs:1036-1066
     std::vector<int> outs;
     int cn = push(Constant(c)).node();
-    for (int src : s.nodes()) {
+    for (size_t ch = 0; ch < s.nodes().size(); ++ch) {
+      const int src = s.nodes()[ch];
       NodeRec m;
       m.type = NodeRec::MATH;
       m.math_kind = kind;
       m.in0 = src;
+      m.in0_ch = s.channels()[ch];
       m.in1 = cn;
       graph_->nodes_.push_back(m);
       outs.push_back(static_cast<int>(graph_->nodes_.size()) - 1);
     }
     return Sig<F>(this, outs);
   }
+  // Two handles of the same channel count: channel c of one (op) channel c of the other.  `play * amp.out([0, 0])` of a
+  // two-channel BufferReader and a Constant handed out twice is ONE Constant and ONE MathUGen<_, U2, Mul> in the reference
+  // (three nodes with the reader); here it is a MathUGen per channel, traced into a MUL_CONST stage per channel -- for which
+  // knh_chain_ugen_count reports 1 + 2 x 2 = 5 (a Constant + MathUGen pair per MUL_CONST stage), two more than the
+  // reference has nodes.  amp.param("value") is sent to the stage of every channel (NodeRec::more_stages).
   Sig<F> math_sig(const Sig<F>& a, const Sig<F>& b, uint16_t kind) {  // graph_edit.rs:936-971
-    NodeRec m;
-    m.type = NodeRec::MATH;
-    m.math_kind = 0xFFFF;
-    m.math2_kind = kind;
-    m.in0 = a.node();
-    m.in1 = b.node();
-    graph_->nodes_.push_back(m);
-    return Sig<F>(this, {static_cast<int>(graph_->nodes_.size()) - 1});
+    if (a.nodes().size() != b.nodes().size()) throw GraphError("a (op) b: the two handles have different channel counts");
+    std::vector<int> outs;
+    for (size_t c = 0; c < a.nodes().size(); ++c) {
+      NodeRec m;
+      m.type = NodeRec::MATH;
+      m.math_kind = 0xFFFF;
+      m.math2_kind = kind;
+      m.in0 = a.nodes()[c];
+      m.in0_ch = a.channels()[c];
+      m.in1 = b.nodes()[c];
+      m.in1_ch = b.channels()[c];
+      graph_->nodes_.push_back(m);
+      outs.push_back(static_cast<int>(graph_->nodes_.size()) - 1);
+    }
+    return Sig<F>(this, outs);
   }
   Sig<F> connect(const Sig<F>& src, const Sig<F>& sink) {
     NodeRec& n = graph_->nodes_[static_cast<size_t>(sink.node())];
@@ -837,6 +909,10 @@ class AudioProcessor {
     const uint16_t d16 = static_cast<uint16_t>(delay);
     const uint32_t kind = ev.kind;
     knh_bank_param_apply_many_at(bank.h, block_offset, 1, &voice, &stage, &param, &kind, &ev.f, &ev.i, delay > 0 ? &d16 : nullptr);
+    for (int extra : n.more_stages) {  // one Constant behind a MUL_CONST stage per channel: the same change to each
+      const uint32_t s2 = static_cast<uint32_t>(extra);
+      knh_bank_param_apply_many_at(bank.h, block_offset, 1, &voice, &s2, &param, &kind, &ev.f, &ev.i, delay > 0 ? &d16 : nullptr);
+    }
     return true;
   }
   Graph<F>* graph_;

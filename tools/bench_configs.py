@@ -121,10 +121,78 @@ def run_sampler(case, n_voices=16384, block_size=512, launches=16, blocks=32, re
         b.close()
 
 
+def run_sampler_stereo(n_voices=16384, block_size=512, launches=8, blocks=32, repeats=4):
+    """The stereo sampler, f32, every voice looping at a rate of its own on one of 64 Buffers of about 1 s.  Two banks in this
+    process, timed in turn (A, B, A, B, ...) after a warm-up of each, by the banks' own device events around launches that end
+    in a synchronise:
+      A  one stereo reader (BufferReader<F, U2> on interleaved two-channel Buffers), a MUL_CONST per channel, connected outputs;
+      B  two mono readers on the voice's entry of a one-channel pool, a MUL_CONST each, connected outputs -- the voice the
+         library ran before it had a stereo reader: the yardstick.
+    A voice-sample is one frame of one voice, both channels.  Both fetch 16 pool bytes per voice-sample (two frames of two
+    f32 samples; two readers x two samples); A with two 8-byte loads and one read pointer, B with four 4-byte loads and two.
+    One JSON line per repeat and bank, then a summary: medians, the spread between B's own repeats, and whether A is within it."""
+    from knaster_amd.bank import Stage
+    CH1 = Stage(L.STAGE_BUFFER_READER, flags=L.STAGE_FLAG_READER_CH1, input=1)
+    stages = {"A": [Stage(L.STAGE_BUFFER_READER), CH1, Stage(L.STAGE_MUL_CONST, input=1), Stage(L.STAGE_MUL_CONST, input=2)],
+              "B": [Stage(L.STAGE_BUFFER_READER), Stage(L.STAGE_MUL_CONST), Stage(L.STAGE_BUFFER_READER), Stage(L.STAGE_MUL_CONST)]}
+    outs = {"A": (2, 3), "B": (1, 3)}
+    rng = np.random.default_rng(7)
+    v = np.arange(n_voices, dtype=np.uint32)
+    u = v.astype(np.int64)
+    ctor = np.stack([0.5 + 1.5 * ((u * 2654435761) % 1000) / 1000.0, np.ones(n_voices), np.zeros(n_voices)], axis=1)
+    n_buffers = 64
+    buffers = [rng.uniform(-1, 1, (48000 + 37 * k, 2)).astype(np.float32) for k in range(n_buffers)]
+    banks = {}
+    for name in ("A", "B"):
+        b = knaster_amd.VoiceBank(stages[name], n_voices, L.F32, 2, L.MIX_TREE)
+        for s, st in enumerate(stages[name]):
+            if st.kind == L.STAGE_MUL_CONST:
+                b.set_ctor_args(s, np.full((n_voices, 1), 1.0 / n_voices))
+            elif not st.flags:
+                b.set_ctor_args(s, ctor)
+        for k in range(n_buffers):
+            if name == "A":
+                b.add_buffer(0, buffers[k], 48000.0, channels=2)
+            else:
+                b.add_buffer(0, np.ascontiguousarray(buffers[k][:, 0]), 48000.0)
+        b.assign_buffers(0, v, v % n_buffers)
+        b.connect_outputs(*outs[name])
+        b.init(configs.SAMPLE_RATE, block_size)
+        for _ in range(3):  # untimed: first-use allocations, the clock
+            b.process_blocks_device(blocks)
+        b.synchronize()
+        banks[name] = b
+    us = {"A": [], "B": []}
+    for rep in range(repeats):
+        for name in ("A", "B"):
+            b = banks[name]
+            b.timing_reset(True)
+            for _ in range(launches):
+                b.process_blocks_device(blocks)
+            b.synchronize()
+            kms, n = b.timing_read()
+            us[name].append(kms * 1e3 / (n * blocks))
+            print(json.dumps({"config": "sampler", "case": "stereo", "bank": name, "buffers": n_buffers, "voices": n_voices, "block_size": block_size,
+                              "sample_type": "f32", "signature": b.debug_signature(), "repeat": rep, "us_per_block_kernel": us[name][-1],
+                              "kernel_only_voice_samples_per_s": float(n_voices) * block_size / (us[name][-1] * 1e-6),
+                              "pool_bytes_per_voice_sample": 16, "pool_loads_per_voice_sample": 2 if name == "A" else 4}), flush=True)
+    for b in banks.values():
+        b.close()
+    med = {k: float(np.median(x)) for k, x in us.items()}
+    spread = max(us["B"]) - min(us["B"])
+    print(json.dumps({"config": "sampler", "case": "stereo", "summary": True, "us_per_block_A": med["A"], "us_per_block_B": med["B"],
+                      "voice_samples_per_s_A": float(n_voices) * block_size / (med["A"] * 1e-6),
+                      "voice_samples_per_s_B": float(n_voices) * block_size / (med["B"] * 1e-6),
+                      "B_spread_us": spread, "A_minus_B_us": med["A"] - med["B"], "A_within_B_spread": bool(med["A"] - med["B"] <= spread)}), flush=True)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "sampler":  # tools/bench_configs.py sampler shared|pool: BASELINE.md section 4, the sampler rows
+    if len(sys.argv) > 1 and sys.argv[1] == "sampler":  # tools/bench_configs.py sampler shared|pool|stereo: BASELINE.md section 4, the sampler rows
         for case in sys.argv[2:] or ["shared", "pool"]:
-            run_sampler(case)
+            if case == "stereo":
+                run_sampler_stereo()
+            else:
+                run_sampler(case)
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "ab":  # the configs that run on kernels other than the headline one
         run("C3", n_voices=65536)
