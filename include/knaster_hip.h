@@ -32,6 +32,8 @@ extern "C" {
 #endif
 
 #define KNH_ABI_VERSION 4
+/* Delay stages (KNH_STAGE_SAMPLE_DELAY, _ALLPASS_DELAY, _ALLPASS_FB_DELAY) a voice may hold; Freeverb's mono topology needs 12 */
+#define KNH_MAX_DELAY_STAGES 16
 
 typedef enum knh_status {
   KNH_OK = 0,
@@ -108,11 +110,15 @@ typedef enum knh_value_kind {
  *     params: 0 delay_time (seconds; delay_samples = (seconds * sample_rate) as usize).  The ring holds
  *     (Seconds::to_secs_f64() * sample_rate) as usize samples per voice, in HBM.  A delay_time longer than the ring
  *     is refused with KNH_ERR_OUT_OF_RANGE (the reference indexes out of bounds there); a zero-length ring fails init.
- *     At most one per chain.
+ *     A voice may hold several delay stages, of any of the three kinds: see KNH_MAX_DELAY_STAGES.
  * KNH_STAGE_ALLPASS_DELAY   x >> g.push(AllpassDelay::new(Seconds::from_secs_f64(max_delay)))  delay.rs:93-206  1  max_delay (s)
  *     params: 0 delay_time (seconds).  The ring holds Seconds::to_samples(sample_rate) samples per voice (HBM); the
  *     fractional part of the delay goes through the reference's first-order allpass interpolator.  A delay_time of
- *     the ring length or more is ignored, as in the reference.  At most one delay stage (of either kind) per chain.
+ *     the ring length or more is ignored, as in the reference.
+ *     Delay stages (SAMPLE_DELAY, ALLPASS_DELAY, ALLPASS_FB_DELAY) are nodes like any other: a chain or graph voice holds up
+ *     to KNH_MAX_DELAY_STAGES of them, in series or in parallel, each with its own max_delay per voice (a ring of its own in
+ *     HBM, sized by that stage's longest ring), its own parameters and its own delayed_changes_per_block.  One more is
+ *     KNH_ERR_UNSUPPORTED_CHAIN at knh_bank_create.  A chain that ends in KNH_STAGE_GALACTIC holds none.
  * KNH_STAGE_ALLPASS_FB_DELAY  x >> g.push(AllpassFeedbackDelay::new(Seconds::from_secs_f64(max_delay)))  delay.rs:210-306  1  max_delay (s)
  *     the Schroeder allpass around an AllpassDelay.  params: 0 delay_time (seconds; longer than the ring: ignored -- the
  *     reference does not check and would index out of bounds), 1 feedback

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KNH_LIB") or os.path.join(_HERE, "csrc", "libknaster_hip.so")
 
 KNH_ABI_VERSION = 4
+KNH_MAX_DELAY_STAGES = 16  # delay stages a voice may hold (knaster_hip.h)
 
 # knh_status
 OK, ERR_INVALID_ARGUMENT, ERR_OUT_OF_RANGE, ERR_UNSUPPORTED_CHAIN, ERR_DEVICE = 0, 1, 2, 3, 4

@@ -17,6 +17,8 @@ from .bank import Stage
 
 SEED = 0x9E3779B9
 SAMPLE_RATE = 48000
+D4_ALLPASS_SAMPLES = (2017, 647, 239, 83)  # D4's allpass rings, samples at 48 kHz
+D4_FEEDBACK = (0.7, 0.65, 0.6, 0.5)
 
 
 def xorshift32_stream(seed: int, n: int) -> np.ndarray:
@@ -70,6 +72,7 @@ class Workload:
     delay_times: np.ndarray = None  # D3: per-voice SampleDelay delay_time set before block 0 (stage 3, param 0)
     buffer: tuple = None  # (stage, samples, sample_rate): the Buffer of a BufferReader stage
     in_channels: int = 0  # UGen::Inputs of the bank node (KNH_STAGE_INPUT stages read them)
+    param_sets: tuple = ()  # D4: (stage, param, per-voice float values) set on every voice before block 0
 
 
 def config(name: str, n_voices: int | None = None, block_size: int | None = None, sample_type: int | None = None,
@@ -79,7 +82,7 @@ def config(name: str, n_voices: int | None = None, block_size: int | None = None
     defaults = {"C1": (1, 64, L.F32), "C2": (1024, 256, L.F32), "C3": (16384, 512, L.F32),
                 "C4": (65536, 512, L.F64), "C5": (4096, 128, L.F32),
                 "D3": (16384, 512, L.F32), "B3": (16384, 512, L.F32), "M1": (600, 64, L.F32), "P3": (16384, 512, L.F32),
-                "G1": (4096, 512, L.F32)}
+                "G1": (4096, 512, L.F32), "D4": (16384, 512, L.F32)}
     nv, bs, st = defaults[name]
     nv = n_voices or nv
     bs = block_size or bs
@@ -147,6 +150,22 @@ def config(name: str, n_voices: int | None = None, block_size: int | None = None
         w.restart = (4, 3)
         w.release = (4, 2, 32)
         w.delay_times = 0.01 + 0.2 * (p["q"] - 0.5) / 3.5  # 10 .. 210 ms, different per voice
+    elif name == "D4":  # not a BASELINE.json config: five delay stages per voice, a pre-delay into a Schroeder allpass series
+        # Ring lengths in samples at 48 kHz, all prime (so mutually prime): the allpass lengths of Schroeder's reverberators --
+        # 42 and 13.5 ms (the 1051 and 337 samples at 25 kHz that JCRev carries, scaled) and the 5 ms / 1.7 ms pair of the
+        # 1962 paper.  A stage's rings are as long as that stage needs: 2 017 samples beside 83.
+        w = Workload(name, [Stage(L.STAGE_SIN_WT), Stage(L.STAGE_WR_MUL), Stage(L.STAGE_SAMPLE_DELAY)] +
+                     [Stage(L.STAGE_ALLPASS_FB_DELAY) for _ in D4_ALLPASS_SAMPLES] + [Stage(L.STAGE_MUL_ENV_ASR, delayed_changes_per_block=precise)],
+                     nv, bs, st, description="SinWt.wr_mul(1/N) -> SampleDelay(25 ms) -> 4 x AllpassFeedbackDelay(42, 13.5, 5, 1.7 ms) -> * EnvAsr")
+        w.ctor = {0: col(p["freq"]), 1: col(gain), 2: col(np.full(nv, 0.025)), 7: np.stack([p["attack"], p["release"]], axis=1)}
+        u = (p["q"] - 0.5) / 3.5  # one of the uniform draws: every voice its own delays, 80 .. 99 % of each ring (the shortest: 66 samples and up)
+        sets = [(2, 0, 0.005 + 0.015 * u)]
+        for k, (ring, fb) in enumerate(zip(D4_ALLPASS_SAMPLES, D4_FEEDBACK)):
+            w.ctor[3 + k] = col(np.full(nv, (ring + 0.5) / SAMPLE_RATE))
+            sets += [(3 + k, 0, ring * (0.8 + 0.19 * u) / SAMPLE_RATE), (3 + k, 1, np.full(nv, fb))]
+        w.param_sets = tuple(sets)
+        w.restart = (7, 3)
+        w.release = (7, 2, 32)
     elif name == "C5":  # modulator SinWt * index + carrier_freq -> carrier SinWt.ar_params() "freq"; * gain
         pr = precise or 4
         w = Workload(name, [Stage(L.STAGE_SIN_WT, delayed_changes_per_block=pr), Stage(L.STAGE_MUL_CONST),

@@ -105,6 +105,9 @@ void choose_forms(Bank<F>* b, const knh::KernelEntry* entry, const std::string& 
       // workgroup, 131 072 233 / 126 / 118 for eight).  (Rounds 1-3 kept every delay chain on the pipeline: a lane per
       // voice's 16-byte pieces ran at 2.0 TB/s in any form.)
       if (b->pipe && sig.find_first_of("DYZ") != std::string::npos) ww = groups <= 256 ? 0 : (groups <= 1024 ? 4 : 8);
+      // Several delay stages per voice: four wavefronts per workgroup at any size -- a wavefront that shares its SIMD's
+      // registers has no room for four delays' tiles (kernels_wide.hip KNH_WIDE_RINGS)
+      if (ww == 8 && std::count_if(sig.begin(), sig.end(), [](char c) { return c == 'D' || c == 'Y' || c == 'Z'; }) > 1) ww = 4;
       const char* wenv = std::getenv("KNH_WIDE");
       if (wenv) ww = std::atoi(wenv);
       if (ww == 4 || ww == 8 || ww == 16) b->wide_waves = ww;

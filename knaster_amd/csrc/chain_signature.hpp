@@ -64,9 +64,10 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     if (source && !ar && st[i].input != 0) { *why = "a source stage reads no signal"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((!source || ar) && !have_x) { *why = "stage needs a preceding signal"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((st[i].kind == KNH_STAGE_SAMPLE_DELAY || st[i].kind == KNH_STAGE_ALLPASS_DELAY || st[i].kind == KNH_STAGE_ALLPASS_FB_DELAY) &&
-        sig->find_first_of("DYZ") != std::string::npos) {
-      *why = "at most one delay stage per chain";
-      return KNH_ERR_INVALID_ARGUMENT;
+        std::count_if(sig->begin(), sig->end(), [](char c) { return c == 'D' || c == 'Y' || c == 'Z'; }) >= KNH_MAX_DELAY_STAGES) {
+      // (every delay stage has a ring of its own per voice; the restart kernel's arguments name each stage's rings: RestartArgs)
+      *why = "a voice holds at most KNH_MAX_DELAY_STAGES delay stages";
+      return KNH_ERR_UNSUPPORTED_CHAIN;
     }
     if (st[i].kind == KNH_STAGE_MUL_ENVELOPE && sig->find('V') != std::string::npos) { *why = "at most one Envelope stage per chain"; return KNH_ERR_INVALID_ARGUMENT; }
     if (st[i].kind == KNH_STAGE_PAN2 && i + 1 != n) { *why = "Pan2 ends the chain: it must be the last stage"; return KNH_ERR_INVALID_ARGUMENT; }

@@ -73,8 +73,10 @@ struct RestartArgs {
   u32 n_params_total;
   double* seg_table;        // device, [n_voices][seg_max][3], or null
   u32 seg_max;
-  void* delay_ring;         // device, [n_voices + 1][delay_stride] samples, or null
-  u32 delay_stride;         // samples, a multiple of four
+  void* delay_ring;         // device: the delay stages' rings (Bank::d_delay), or null
+  u32 n_rings;              // delay stages of the voice, up to KNH_MAX_DELAY_STAGES; stage k's ring of voice v is the samples
+  u64 ring_base[16];        // [ring_base[k] + v * ring_stride[k], + ring_stride[k]) of the allocation: both in samples,
+  u32 ring_stride[16];      // both multiples of 32 (whole 16-byte pieces, each ring from a 128-byte line on)
 };
 }  // namespace knh_dev
 

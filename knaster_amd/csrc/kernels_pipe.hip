@@ -84,6 +84,12 @@ typedef Group<MulVal> G_m;
 typedef Group<SinWt, MulVal, AddVal> G_Wma;
 typedef Group<SinWtAr, MulVal> G_Rm;
 typedef Group<SampleDelay, MulAsr> G_DA;
+// (groups of chains with several delay stages: a group's delays share the group's one RingLines tile, in turn)
+typedef Group<SinWt, MulVal, SampleDelayNoAhead> G_WmD;
+typedef Group<AllpassFbDelay, AllpassFbDelay> G_ZZ;
+typedef Group<AllpassFbDelay, AllpassFbDelay, MulAsr> G_ZZA;
+typedef Group<SampleDelayNoAhead, AllpassFbDelay> G_DZ;
+typedef Group<AllpassDelay, MulVal> G_Ym;
 typedef Group<PolyBlepOsc, MulVal> G_Bm;
 typedef Group<MulAr, Pan2> G_E2;
 typedef Group<MulAsr, Pan2> G_A2;
@@ -108,6 +114,8 @@ static const PipeEntry kTable[] = {
     KNH_PIPE_FAN_("N", 2, G_Np, F_N)
     KNH_PIPE("NSAm", 3, G_N, G_S, G_Am)
     KNH_PIPE("WmSDA", 3, G_Wm, G_S, G_DA)  // the delay's HBM traffic rides in the envelope wave
+    KNH_PIPE("WmDZZZZA", 3, G_WmD, G_ZZ, G_ZZA)  // D4: three stage groups with rings, a tile each; two delays take turns on the second's and the third's
+    KNH_PIPE("WmDZYm", 3, G_Wm, G_DZ, G_Ym)
     KNH_PIPE("BmSA", 3, G_Bm, G_S, G_A)
     KNH_PIPE_BIG("WmEJ", 2, G_Wm, G_E2)     // many_sines: oscillator | envelope + pan (+ fold)
     KNH_PIPE("WmEJ", 2, G_Wm, G_E2)

@@ -37,13 +37,18 @@ __global__ void __launch_bounds__(kRestartThreads) restart_voices_kernel(Restart
     for (u32 i = t; i < n; i += kRestartThreads) a.seg_table[static_cast<size_t>(v) * n + i] = a.seg_rows[static_cast<size_t>(k) * n + i];
   }
   if (a.delay_ring) {
-    // The voice's ring and nothing else: [v * stride, (v + 1) * stride) samples.  The stride is a multiple of four samples and
-    // the allocation 256-byte aligned, so the ring is whole 16-byte pieces; consecutive lanes store consecutive pieces (a
-    // wavefront's store is 1 KiB in a row).  The neighbours' rings and the spare ring behind the last voice are never touched.
-    const size_t ring_bytes = static_cast<size_t>(a.delay_stride) * (a.f64 ? 8u : 4u);
-    uint4* ring = reinterpret_cast<uint4*>(static_cast<char*>(a.delay_ring) + static_cast<size_t>(v) * ring_bytes);
-    const size_t n16 = ring_bytes / 16u;
-    for (size_t i = t; i < n16; i += kRestartThreads) ring[i] = make_uint4(0u, 0u, 0u, 0u);
+    // The voice's rings, one per delay stage, and nothing else: stage r's is [base_r + v * stride_r, + stride_r) samples.
+    // Bases and strides are multiples of 32 samples and the allocation 256-byte aligned, so a ring is whole 16-byte pieces
+    // from a 128-byte line on; consecutive lanes store consecutive pieces (a wavefront's store is 1 KiB in a row).  The
+    // neighbours' rings, the other stages' and the spare ring behind the last one are never touched.
+    static_assert(sizeof(a.ring_stride) / sizeof(a.ring_stride[0]) == KNH_MAX_DELAY_STAGES, "a base and a stride per delay stage");
+    const size_t word = a.f64 ? 8u : 4u;
+    for (u32 r = 0; r < a.n_rings && r < (u32)KNH_MAX_DELAY_STAGES; ++r) {
+      const size_t ring_bytes = static_cast<size_t>(a.ring_stride[r]) * word;
+      uint4* ring = reinterpret_cast<uint4*>(static_cast<char*>(a.delay_ring) + static_cast<size_t>(a.ring_base[r]) * word + static_cast<size_t>(v) * ring_bytes);
+      const size_t n16 = ring_bytes / 16u;
+      for (size_t i = t; i < n16; i += kRestartThreads) ring[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
   }
 }
 

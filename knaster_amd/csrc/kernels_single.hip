@@ -44,6 +44,9 @@ static const KernelEntry kEntries[] = {
     KNH_CHAIN("WmV", SinWt, MulVal, MulSegEnv),                 // SinWt.wr_mul * segment Envelope
     KNH_CHAIN("WmSDA", SinWt, MulVal, Svf, SampleDelay, MulAsr), // C3 with a delay line behind the filter (HBM-bound regime)
     KNH_CHAIN("BmSA", PolyBlepOsc, MulVal, Svf, MulAsr),         // the C3 voice with a band-limited oscillator
+    // several delay stages per voice, one after the other on the wavefront's one RingLines tile; no SampleDelay reads ahead (SampleDelayT)
+    KNH_CHAIN("WmDZZZZA", SinWt, MulVal, SampleDelayNoAhead, AllpassFbDelay, AllpassFbDelay, AllpassFbDelay, AllpassFbDelay, MulAsr),  // D4: pre-delay into a Schroeder allpass series
+    KNH_CHAIN("WmDZYm", SinWt, MulVal, SampleDelayNoAhead, AllpassFbDelay, AllpassDelay, MulVal),  // one delay stage of each kind in series
 };
 
 const KernelEntry* find_kernel(const char* signature) {

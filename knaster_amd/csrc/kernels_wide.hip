@@ -22,11 +22,24 @@ static hipError_t launch_wide(const VoiceKernelArgs<F>& args, unsigned n_wavefro
    {launch_wide<double, false, 8, __VA_ARGS__>, launch_wide<double, true, 8, __VA_ARGS__>},          \
    {launch_wide<float, false, 16, __VA_ARGS__>, launch_wide<float, true, 16, __VA_ARGS__>},          \
    {launch_wide<double, false, 16, __VA_ARGS__>, launch_wide<double, true, 16, __VA_ARGS__>}}
+// A voice of several delay stages has room in the four-wavefront form only: with a SIMD's registers to itself a wavefront
+// holds twelve delays' tiles without scratch, with half of them (eight per workgroup: 256) four delays already spill.  Banks
+// that would take eight or sixteen wavefronts per workgroup run workgroups of four.
+#define KNH_WIDE_RINGS(sig, ...)                                                                      \
+  {sig,                                                                                               \
+   {launch_wide<float, false, 4, __VA_ARGS__>, launch_wide<float, true, 4, __VA_ARGS__>},            \
+   {launch_wide<float, false, 4, __VA_ARGS__>, launch_wide<float, true, 4, __VA_ARGS__>},            \
+   {launch_wide<double, false, 4, __VA_ARGS__>, launch_wide<double, true, 4, __VA_ARGS__>},          \
+   {launch_wide<double, false, 4, __VA_ARGS__>, launch_wide<double, true, 4, __VA_ARGS__>},          \
+   {launch_wide<float, false, 4, __VA_ARGS__>, launch_wide<float, true, 4, __VA_ARGS__>},            \
+   {launch_wide<double, false, 4, __VA_ARGS__>, launch_wide<double, true, 4, __VA_ARGS__>}}
 static const WideEntry kWides[] = {
     KNH_WIDE("Wm", SinWt, MulVal),
     KNH_WIDE("Nm", SinNum, MulVal),
     KNH_WIDE("WmSA", SinWt, MulVal, Svf, MulAsr),
     KNH_WIDE("WmSDA", SinWt, MulVal, Svf, SampleDelay, MulAsr),
+    KNH_WIDE_RINGS("WmDZZZZA", SinWt, MulVal, SampleDelayNoAhead, AllpassFbDelay, AllpassFbDelay, AllpassFbDelay, AllpassFbDelay, MulAsr),  // D4
+    KNH_WIDE_RINGS("WmDZYm", SinWt, MulVal, SampleDelayNoAhead, AllpassFbDelay, AllpassDelay, MulVal),
     KNH_WIDE("BmSA", PolyBlepOsc, MulVal, Svf, MulAsr),
     KNH_WIDE("WSAm", SinWt, Svf, MulAsr, MulVal),
     KNH_WIDE("WmE", SinWt, MulVal, MulAr),

@@ -209,9 +209,24 @@ struct Bank final : knh_bank {
     if (at == pool.size()) total += (n_samples + 63ull) & ~63ull;
     return total;
   }
-  void* d_delay = nullptr;        // SampleDelay rings: [voice][delay_stride] of F
-  uint32_t delay_stride = 0;
-  std::vector<uint32_t> delay_len;  // ring length per voice (samples)
+  // The delay stages' rings: one per (delay stage, voice), all in one allocation.  Stage after stage in chain order, each
+  // stage's rings [voice][that stage's stride] of F, the stride the stage's own longest ring rounded up to the granule -- a
+  // 40 ms delay beside a 1.7 ms allpass costs one 40 ms ring per voice, not two.  Behind the last stage's rings the spare
+  // ring (RingLines' sink, voice_stages.hpp).  A device stage finds its ring by its first granule (its slot 3, Ctx::delay_stride
+  // = kRingGranule): 32 samples, so every ring starts on a 128-byte line and is whole 16-byte pieces.
+  static constexpr uint32_t kRingGranule = 32;
+  struct DelayRings { uint32_t stage, stride; uint64_t base; };  // stride and base (of voice 0's ring) in samples, multiples of the granule
+  void* d_delay = nullptr;
+  uint32_t delay_stride = 0;        // kRingGranule once there are rings
+  uint32_t ring_sink_row = 0;       // the spare ring's first granule
+  std::vector<DelayRings> rings;    // per delay stage, in chain order
+  std::vector<int> ring_of_stage;   // [stage] -> its entry of `rings`, -1: no delay stage
+  std::vector<uint32_t> delay_len;  // [delay stage (entry of `rings`)][voice]: ring length (samples)
+  uint32_t& ring_len(size_t stage, uint32_t v) { return delay_len[static_cast<size_t>(ring_of_stage[stage]) * nv + v]; }
+  uint32_t ring_row(size_t stage, uint32_t v) const {
+    const DelayRings& r = rings[static_cast<size_t>(ring_of_stage[stage])];
+    return static_cast<uint32_t>((r.base + static_cast<uint64_t>(v) * r.stride) / kRingGranule);
+  }
   std::vector<double> env_start;  // Envelope::start_value per voice (t_restart restores it)
   std::vector<uint32_t> env_nseg;
   F* d_partials = nullptr;
@@ -284,6 +299,7 @@ struct Bank final : knh_bank {
     a.seg_max = seg_max;
     a.delay_ring = d_delay;
     a.delay_stride = delay_stride;
+    a.ring_sink_row = ring_sink_row;
     a.buffer = d_buffer;
     a.input = nullptr;
     a.in_channels = desc.in_channels;
@@ -518,7 +534,23 @@ struct Bank final : knh_bank {
         }
       } break;
       case KNH_STAGE_INPUT: uses_input = true; break;
-      case KNH_STAGE_ALLPASS_FB_DELAY: case KNH_STAGE_ALLPASS_DELAY: case KNH_STAGE_SAMPLE_DELAY: delay_len.assign(nv, 0u); break;
+      case KNH_STAGE_ALLPASS_FB_DELAY: case KNH_STAGE_ALLPASS_DELAY: case KNH_STAGE_SAMPLE_DELAY: {
+        // the stage's rings: behind the delay stages before it, as far apart as its own longest ring asks
+        uint32_t mx = 0;
+        for (uint32_t v = 0; v < nv; ++v) {
+          uint32_t len = 0;
+          int rc = delay_ring_len(S, ctor[si].data() + static_cast<size_t>(v) * S.n_ctor, &len);
+          if (rc != KNH_OK) return rc;
+          mx = std::max(mx, len);
+        }
+        const uint64_t base = rings.empty() ? 0u : rings.back().base + static_cast<uint64_t>(nv) * rings.back().stride;
+        const uint32_t own = (mx + kRingGranule - 1u) / kRingGranule * kRingGranule;
+        // (a ring is named by its first granule in a 32-bit state word; the spare ring's comes behind the last one)
+        if ((base + static_cast<uint64_t>(nv) * own) / kRingGranule >= 0xFFFFFFFFull) return fail(KNH_ERR_INVALID_ARGUMENT, "the delay rings of the bank are too long in sum");
+        ring_of_stage[si] = static_cast<int>(rings.size());
+        rings.push_back(DelayRings{static_cast<uint32_t>(si), own, base});
+        delay_len.resize(rings.size() * nv, 0u);
+      } break;
       default: break;
     }
     return KNH_OK;
@@ -677,11 +709,11 @@ struct Bank final : knh_bank {
       case KNH_STAGE_ALLPASS_DELAY: {  // delay.rs:107-123: buffer = max_delay_seconds.to_samples(sample_rate) zeros
         uint32_t nsamp = 0;
         { int rc = delay_ring_len(S, a, &nsamp); if (rc != KNH_OK) return rc; }
-        delay_len[v] = nsamp;
+        ring_len(si, v) = nsamp;
         put(0, 0);  // write_frame
         put(1, 0);  // read_frame
         put(2, static_cast<W>(nsamp));
-        put(3, v);
+        put(3, ring_row(si, v));
         put(4, fw(F(1)));  // AllpassInterpolator::new: coeff, prev_input, prev_output all ONE (:61-67)
         put(5, fw(F(1)));
         put(6, fw(F(1)));
@@ -690,11 +722,11 @@ struct Bank final : knh_bank {
       case KNH_STAGE_SAMPLE_DELAY: {  // delay.rs:24-31 (new), :45-49 (init)
         uint32_t len = 0;
         { int rc = delay_ring_len(S, a, &len); if (rc != KNH_OK) return rc; }
-        delay_len[v] = len;
+        ring_len(si, v) = len;
         put(0, 0);    // write_position
         put(1, len);  // len - delay_samples, delay_samples = 0
         put(2, len);
-        put(3, v);
+        put(3, ring_row(si, v));
       } break;
       case KNH_STAGE_WR_POWI:  // WrPowi::new(ugen, value: i32), wrappers_core/math.rs:591-595
         put(0, static_cast<W>(static_cast<uint32_t>(static_cast<int32_t>(a[0]))));
@@ -804,7 +836,15 @@ struct Bank final : knh_bank {
       const unsigned n_cuts = partition_chain(signature, cuts);
       jit = knh::jit_pipe_kernel(signature.c_str(), cuts, n_cuts, sizeof(F) == 8, desc.allow_fma != 0, &why);
       jit_pipe = jit != nullptr;
-      if (!jit) return fail(why.rfind("JIT_CRASH: ", 0) == 0 ? KNH_ERR_INTERNAL : KNH_ERR_UNSUPPORTED_CHAIN, "run-time fusion of chain '" + signature + "' (pipelined) failed: " + why);
+      // A chain of several delay stages for which the pipeline has no room (a RingLines tile per stage group beside the
+      // table and the edges: voice_pipe.hpp's LDS sum) is not refused: it takes the whole-chain form below.
+      const bool crashed = why.rfind("JIT_CRASH: ", 0) == 0;
+      const bool several_delays = std::count_if(signature.begin(), signature.end(), [](char c) { return c == 'D' || c == 'Y' || c == 'Z'; }) > 1;
+      if (!jit && (crashed || !several_delays)) return fail(crashed ? KNH_ERR_INTERNAL : KNH_ERR_UNSUPPORTED_CHAIN, "run-time fusion of chain '" + signature + "' (pipelined) failed: " + why);
+      if (!jit) warnings.push_back("pipelined kernel not built (" + why.substr(0, 300) + "): the whole-chain form runs the voice");
+    }
+    if (jit || (pipe_jit && entry)) {
+      // (fused as a pipeline, or a pre-built whole-chain kernel stands in for the pipeline that was not built)
     } else if (!entry && !interp) {  // no pre-built kernel at all
       std::string why;
       // Beyond the pipeline's reach (more than 512 voice groups) a fused chain runs as whole-chain wavefronts sharing a staged
@@ -813,6 +853,8 @@ struct Bank final : knh_bank {
       // A voice that is a graph keeps the one-wavefront form (its signals' registers leave no room to share a SIMD).
       // KNH_JIT_WAVES=1|4|8|16 overrides (tests: the filter's steps at one, two and four wavefronts per SIMD).
       unsigned jw = !signature_is_dag(signature) && n_groups > jit_pipe_max ? (n_groups <= 1024 ? 4u : 8u) : 1u;
+      // (several delay stages: four per workgroup at any size, as the pre-built chains -- at eight, four delays' tiles spill)
+      if (jw == 8u && std::count_if(signature.begin(), signature.end(), [](char c) { return c == 'D' || c == 'Y' || c == 'Z'; }) > 1) jw = 4u;
       if (const char* e = std::getenv("KNH_JIT_WAVES")) { const int v = std::atoi(e); if ((v == 1 || v == 4 || v == 8 || v == 16) && !signature_is_dag(signature)) jw = static_cast<unsigned>(v); }
       if (sizeof(F) == 8 && jw == 16) jw = 8;  // (sixteen f64 tiles do not fit beside the table)
       jit = knh::jit_voice_kernel(signature.c_str(), sizeof(F) == 8, desc.allow_fma != 0, &why, jw);
@@ -830,6 +872,9 @@ struct Bank final : knh_bank {
     // reference can produce and the one in which the low-pass tiles must take the general step (Svf::low_pass)
     const char* const neg0_env = std::getenv("KNH_DEBUG_SVF_IC2_NEG0");
     svf_ic2_neg0 = neg0_env && neg0_env[0] == '1';
+    rings.clear();
+    delay_len.clear();
+    ring_of_stage.assign(stages.size(), -1);
     for (size_t si = 0; si < stages.size(); ++si) {
       const StageInfo& S = stages[si];
       const double* ca = ctor[si].data();
@@ -860,12 +905,15 @@ struct Bank final : knh_bank {
         std::vector<F>().swap(e.samples);
       }
     }
-    if (!delay_len.empty()) {
+    if (!rings.empty()) {
+      // the sum over the delay stages of nv x the stage's stride
+      const uint64_t samples = rings.back().base + static_cast<uint64_t>(nv) * rings.back().stride;
       uint32_t mx = 0;
-      for (uint32_t l : delay_len) mx = std::max(mx, l);
-      delay_stride = (mx + 3u) & ~3u;
-      // (+ a spare ring behind the last voice's: where lanes without a voice move their lines, voice_stages.hpp RingLines)
-      const size_t bytes = (static_cast<size_t>(nv) + 1) * delay_stride * sizeof(F) + 4096;
+      for (const DelayRings& r : rings) mx = std::max(mx, r.stride);
+      delay_stride = kRingGranule;
+      ring_sink_row = static_cast<uint32_t>(samples / kRingGranule);
+      // (+ a spare ring behind the last one, as long as the longest: where lanes without a voice move their lines, voice_stages.hpp RingLines)
+      const size_t bytes = (static_cast<size_t>(samples) + mx) * sizeof(F) + 4096;
       size_t free_b = 0, total_b = 0;
       KNH_HIP(hipMemGetInfo(&free_b, &total_b));
       if (bytes > free_b) return fail(KNH_ERR_DEVICE, "SampleDelay: the delay rings do not fit in device memory");
@@ -1014,7 +1062,8 @@ struct Bank final : knh_bank {
         uint32_t len = 0;
         int rc = delay_ring_len(S, a, &len);
         if (rc != KNH_OK) return rc;
-        if (len > delay_stride) return fail(KNH_ERR_OUT_OF_RANGE, "the delay's ring would be longer than the rings allocated at knh_bank_init");
+        // (the stage's own rings: another delay stage's longer ones are no room for this one's)
+        if (len > rings[static_cast<size_t>(ring_of_stage[stage])].stride) return fail(KNH_ERR_OUT_OF_RANGE, "the delay's ring would be longer than the rings allocated at knh_bank_init");
       }
       if (S.kind == KNH_STAGE_INPUT && (!(a[0] >= 0.0) || a[0] >= static_cast<double>(desc.in_channels)))
         return fail(KNH_ERR_INVALID_ARGUMENT, "KNH_STAGE_INPUT: channel is not below knh_bank_desc.in_channels");
@@ -1122,7 +1171,8 @@ struct Bank final : knh_bank {
     ra.seg_table = n_seg ? d_seg_table : nullptr;
     ra.seg_max = seg_max;
     ra.delay_ring = d_delay;
-    ra.delay_stride = delay_stride;
+    ra.n_rings = static_cast<uint32_t>(rings.size());  // (at most KNH_MAX_DELAY_STAGES: build_signature)
+    for (size_t r = 0; r < rings.size() && r < static_cast<size_t>(KNH_MAX_DELAY_STAGES); ++r) { ra.ring_base[r] = rings[r].base; ra.ring_stride[r] = rings[r].stride; }
     if (resolver.active()) { int rc = resolver.restart_may_write(s); if (rc != KNH_OK) return rc; }
     KNH_HIP(knh::launch_restart_voices(ra, static_cast<unsigned>(n), s));
     KNH_HIP(hipEventRecord(rs_done, s));
@@ -1564,7 +1614,7 @@ struct Bank final : knh_bank {
         [[fallthrough]];  // delay_time, :231-236: set_delay_in_frames without the length check of AllpassDelay's
       case KNH_STAGE_ALLPASS_DELAY: {  // delay_time, :136-143 -> set_delay_in_frames, :160-174
         const double delay_frames = f * static_cast<double>(sample_rate);
-        const uint32_t len = delay_len[v];
+        const uint32_t len = ring_len(stage, v);
         if (!(delay_frames < static_cast<double>(len))) {  // `(delay_frames as usize) < buffer.len()` fails: ignored
           if (S.kind == KNH_STAGE_ALLPASS_FB_DELAY) warn("AllpassFeedbackDelay: delay_time longer than the ring, change ignored");
           break;
@@ -1582,7 +1632,7 @@ struct Bank final : knh_bank {
       } break;
       case KNH_STAGE_SAMPLE_DELAY: {  // delay.rs:33-36: delay_samples = (seconds * sample_rate) as usize
         const double ds = f * static_cast<double>(sample_rate);
-        const uint32_t len = delay_len[v];
+        const uint32_t len = ring_len(stage, v);
         if (!(ds < static_cast<double>(len) + 1.0)) {  // the reference would read outside its buffer
           warn("SampleDelay: delay_time longer than the ring, change ignored");
           break;

@@ -30,6 +30,7 @@ struct Chain<F, FMA, BASE> {
   static constexpr u64 kParamBits = 0ull, kNopOkBits = 0ull;
   static constexpr bool kBinds = false;
   static constexpr bool kUsesRing = false;
+  static constexpr int kRingStages = 0;
   template <int T> __device__ __forceinline__ void tick_tile_sw(const Chain&, u32, u64, F (&)[T], const Ctx&, u32) {}
   __device__ __forceinline__ void pan_gains(F&, F&) const {}
   template <typename W> __device__ __forceinline__ void load(const W*, long) {}
@@ -63,6 +64,7 @@ struct Chain<F, FMA, BASE, S0, Rest...> {
   static constexpr u64 kNopOkBits = ((S0::kParamMask != 0u || !S0::kHasSeg) && BASE < 64 ? (u64)1 << (BASE < 64 ? BASE : 0) : 0ull) | RestT::kNopOkBits;
   static constexpr bool kBinds = S0::kNeedsBind || RestT::kBinds;  // a stage with memory behind it (delay ring, segment table, buffer)
   static constexpr bool kUsesRing = S0::kUsesRing || RestT::kUsesRing;
+  static constexpr int kRingStages = (S0::kUsesRing ? 1 : 0) + RestT::kRingStages;  // delay stages of the voice
   typename S0::template Regs<F> r;
   // The frame this stage last passed to mark_done (UGenFlags::mark_done, ugen.rs:199-202), 0xFFFFFFFF: never.  The
   // reference hands one UGenFlags to every task of a block in node order (graph_gen.rs:196-200), so the mark a voice
@@ -217,6 +219,7 @@ struct DagEnd {
   static constexpr bool kUsesSine = false;
   static constexpr bool kPan = false;
   static constexpr bool kUsesRing = false;
+  static constexpr int kRingStages = 0;
   __device__ __forceinline__ void pan_gains(F&, F&) const {}
   template <typename W> __device__ __forceinline__ void load(const W*, long) {}
   template <typename W> __device__ __forceinline__ void store(W*, long) const {}
@@ -271,6 +274,7 @@ struct DagChain<F, FMA, BASE, R, LAST, N0, Rest...> {
   static constexpr bool kStereo = RestT::kStereo;  // two connected outputs: the voice's signals are those of slots kOutL and kOutR
   static constexpr int kOutL = RestT::kOutL, kOutR = RestT::kOutR;
   static constexpr bool kUsesRing = S0::kUsesRing || RestT::kUsesRing;
+  static constexpr int kRingStages = (S0::kUsesRing ? 1 : 0) + RestT::kRingStages;  // delay stages of the voice
   typename S0::template Regs<F> r;
   u32 mark = 0xFFFFFFFFu;
   RestT rest;
@@ -578,8 +582,9 @@ struct VoiceKernelArgs {
   u32 sample_rate;                  // for the setters that run on the device (audio-rate parameters, ArP)
   const double* seg_table;          // segment Envelope table [n_voices][seg_max][3], or null
   u32 seg_max;
-  void* delay_ring;                 // SampleDelay rings [n_voices][delay_stride] of F, or null
-  u32 delay_stride;
+  void* delay_ring;                 // the delay stages' rings, per stage [n_voices][that stage's stride] of F, then the spare ring; or null
+  u32 delay_stride;                 // the granule rings start on, in samples (Ctx::delay_stride)
+  u32 ring_sink_row;                // the spare ring's first granule (Ctx::ring_sink_row)
   const void* buffer;               // BufferReader's pool of Buffers (single channel, F; a voice's offset and length are its slots), or null
   const void* input;                // the bank node's input channels, [n_blocks][in_channels][block_size] of F, or null
   u32 in_channels;
@@ -1019,7 +1024,13 @@ __global__ void __launch_bounds__(WAVES * 64) voice_kernel(VoiceKernelArgs<F> a)
 #ifndef KNH_WIDE_KT8
 #define KNH_WIDE_KT8 64  // (eight wavefronts per workgroup, two per SIMD: 262 144 voices 76.2 -> 73.9 us per block; 32 for an A/B build)
 #endif
-  constexpr int KT = sizeof...(S) > 16 ? kTile : (WAVES >= 16 ? (sizeof(F) == 4 ? 16 : 8) : (WAVES <= 4 ? (sizeof(F) == 4 ? 64 : 32) : (sizeof(F) == 4 && !ChainT::kUsesRing ? KNH_WIDE_KT8 : 32)));  // (a delay's tile, its lines and the lines read ahead: 64 samples of each spill at 256 registers)
+  // A voice of several delay stages (they run one after the other on the wavefront's one RingLines tile, none reading ahead:
+  // SampleDelayT) visits one line's samples at a time in f64 -- 16: an allpass delay holds its input tile, the delayed tile,
+  // the tile it writes back and the lines in flight at once, beside every other delay's state; at 32 f64 samples twelve
+  // delays spill (20 bytes of scratch per lane with a SIMD's 512 registers; none at 16).  In f32 the 64-sample visits fit
+  // with twelve delays.  The register table is in DESIGN.md section 4.
+  constexpr bool kManyRings = ChainT::kRingStages > 1;
+  constexpr int KT = sizeof...(S) > 16 ? kTile : (WAVES >= 16 ? (sizeof(F) == 4 ? 16 : 8) : (WAVES <= 4 ? (sizeof(F) == 4 ? 64 : (kManyRings ? 16 : 32)) : (sizeof(F) == 4 && !ChainT::kUsesRing ? KNH_WIDE_KT8 : (sizeof(F) == 8 && kManyRings ? 16 : 32))));  // (a delay's tile, its lines and the lines read ahead: 64 samples of each spill at 256 registers)
   // (one LDS object with the table first: the table at LDS address 0, a table read's address is the masked phase itself)
   constexpr bool kRingTile = ChainT::kUsesRing && WAVES <= 8 && KT * (int)sizeof(F) >= RingLines<F>::kLine;  // (sixteen tiles do not fit beside the table)
   constexpr bool kTwoPlanes = ChainT::kPan || ChainT::kStereo;  // a left and a right signal per voice: two partial rows per wavefront
@@ -1059,7 +1070,7 @@ __global__ void __launch_bounds__(WAVES * 64) voice_kernel(VoiceKernelArgs<F> a)
   ctx.seg_max = a.seg_max;
   ctx.delay_ring = a.delay_ring;
   ctx.delay_stride = a.delay_stride;
-  ctx.ring_sink_row = a.n_voices;
+  ctx.ring_sink_row = a.ring_sink_row;
   ctx.buffer = a.buffer;
   ctx.input_block = a.input;
   ctx.in_stride = a.block_size;

@@ -163,7 +163,7 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
   ctx.seg_max = a.seg_max;
   ctx.delay_ring = a.delay_ring;
   ctx.delay_stride = a.delay_stride;
-  ctx.ring_sink_row = a.n_voices;
+  ctx.ring_sink_row = a.ring_sink_row;
   ctx.buffer = a.buffer;
   ctx.input_block = a.input;
   ctx.in_stride = a.block_size;
@@ -723,6 +723,9 @@ __global__ void __launch_bounds__((GPW * PipeWaves<T, MODE, Gs...>::value * 64))
     u32 res_marks[16 * 64];  // a resident launch: the groups' done marks and running flags of the call (PipeShared)
     u32 res_slot[16];        // ... and its command word
   };
+  // (a ring tile per stage group with a delay, however many delays the group holds: three groups' tiles beside the table and
+  // six short edge tiles are 147 KiB)
+  static_assert(sizeof(Lds) <= 160 * 1024, "the table, the edges and the stage groups' ring tiles fit in a CU's LDS");
   __shared__ Lds lds;
   float* const sine = lds.sine;
   F* const edge = lds.edge;

@@ -105,14 +105,14 @@ struct Ctx {
   double f2pi;              // SinWt::freq_to_phase_inc (osc.rs:144-145)
   const double* seg_table;  // segment Envelope: [voice][seg_max][3] = (duration, 1/duration, value)
   u32 seg_max;
-  void* delay_ring;         // SampleDelay: [voice][delay_stride] samples of F, each voice's ring contiguous
-  u32 delay_stride;
+  void* delay_ring;         // the delay stages' rings, one per (delay stage, voice), each contiguous: a ring starts at granule
+  u32 delay_stride;         // `row` (the stage's slot 3) of the allocation, a granule being delay_stride samples of F (32: a 128-byte line or two)
   const void* buffer;       // BufferReader: the bank's pool of single-channel Buffers, samples of F (each voice's offset and length: its slots)
   const void* input_block;  // the bank node's input channels for the block being processed: [in_channels][in_stride] of F
   u32 in_stride;            // = block_size
   u32 sample_rate;          // ctx.sample_rate(), for setters that run on the device (audio-rate parameters)
   __attribute__((address_space(3))) char* ring_tile;  // this wavefront's RingLines tile in LDS (whole-chain kernels of up to eight wavefronts), or null
-  u32 ring_sink_row;        // the spare ring behind the last voice's (= the number of voices): where lanes without a voice move their lines
+  u32 ring_sink_row;        // the spare ring behind the last stage's last voice's (its first granule): where lanes without a voice move their lines
 };
 
 // ---------------------------------------------------------------------------
@@ -1946,7 +1946,12 @@ struct RingLines {
   // so that no access below needs to ask whether its voice exists.
   static __device__ __forceinline__ void exchange(tile_t tile, int lane, bool live, u32 row, u32 wp, u32 rp, u32 len, const Ctx& c, Owned& o) {
     U4 h;
-    h[0] = live ? row : c.ring_sink_row; h[1] = live ? wp : 0u; h[2] = live ? rp : 0u; h[3] = live ? len : 0x7FFFFFFFu;
+    // (the sink row is read before the select, not inside it: in `live ? row : c.ring_sink_row` each arm is a load of its own,
+    // the compiler merges the two into one load through a pointer chosen between the stage's registers and the context, and
+    // neither is promoted to registers any more -- the D3 kernels in f32 and a voice of three f64 delays or more kept their
+    // whole chain, every stage's state, in scratch memory: 640 and 464 to 1 040 bytes per lane)
+    const u32 sink = c.ring_sink_row;
+    h[0] = live ? row : sink; h[1] = live ? wp : 0u; h[2] = live ? rp : 0u; h[3] = live ? len : 0x7FFFFFFFu;
     *reinterpret_cast<lds_u4>(tile + lane * kRow + kLine) = h;
     fence();
     U4 g[8];
@@ -2040,7 +2045,11 @@ struct RingLines {
 // (0..len), 2 len, 3 the voice's ring row.  A tile whose reads cannot meet its own writes (delay >= T) and that does not
 // cross the end of the ring moves its T samples with 16-byte loads, then 16-byte stores; any other tile runs sample by
 // sample in the reference's order (store, then load).
-struct SampleDelay : StageDefaults {
+// AHEAD: the stage keeps the next tile read ahead in registers (64 VGPRs of lines in f32, the tile itself in the forms without
+// a RingLines tile).  The only delay stage of a voice does; where a voice holds several (up to KNH_MAX_DELAY_STAGES) none
+// does -- twelve read-ahead tiles are more registers than a wavefront has, and a kernel with delays must not spill.
+template <bool AHEAD>
+struct SampleDelayT : StageDefaults {
   static constexpr int kSlots = 4;
   static constexpr u32 kMutableMask = 0b1u;
   static constexpr bool kUsesSine = false;
@@ -2054,8 +2063,8 @@ struct SampleDelay : StageDefaults {
     u32 wp, off, len, row;
     F* ring;
     u32 pre_pos;       // ring position the tile in `pre` / `lines` was read from, 0xFFFFFFFF: none
-    F pre[kPrefetch];  // the next tile's samples, requested while this tile is being processed
-    typename RingLines<F>::Lines lines[kLinesAhead];  // the same where the wavefront moves its rings as lines: this lane's share of them
+    F pre[AHEAD ? kPrefetch : 1];  // the next tile's samples, requested while this tile is being processed
+    typename RingLines<F>::Lines lines[AHEAD ? kLinesAhead : 1];  // the same where the wavefront moves its rings as lines: this lane's share of them
   };
   template <typename F, typename W>
   static __device__ __forceinline__ void load(Regs<F>& r, const W* s, long st) {
@@ -2104,26 +2113,30 @@ struct SampleDelay : StageDefaults {
             const int lane = (int)(threadIdx.x & 63u);
             u32 np = rp + (u32)T;
             if (np >= r.len) np -= r.len;
-            const bool have = !dead && r.pre_pos == rp;
-            const bool ahead = !dead && r.len >= 2u * (u32)T && r.off <= r.len - 2u * (u32)T;
-            const bool all_have = __builtin_amdgcn_ballot_w64(!(have || dead)) == 0;
-            const bool all_ahead = __builtin_amdgcn_ballot_w64(!(ahead || dead)) == 0;
+            const bool have = AHEAD && !dead && r.pre_pos == rp;
+            const bool ahead = AHEAD && !dead && r.len >= 2u * (u32)T && r.off <= r.len - 2u * (u32)T;
+            const bool all_have = AHEAD && __builtin_amdgcn_ballot_w64(!(have || dead)) == 0;
+            const bool all_ahead = AHEAD && __builtin_amdgcn_ballot_w64(!(ahead || dead)) == 0;
             typename RL::Owned own;
             RL::exchange(c.ring_tile, lane, !dead, r.row, r.wp, rp, r.len, c, own);
             F y[T];
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
-              if (all_have) {
-                RL::to_samples(c.ring_tile, lane, r.lines[s], &y[s * RL::TS]);
-              } else {
+              bool from_regs = false;
+              if constexpr (AHEAD) {
+                if (all_have) { RL::to_samples(c.ring_tile, lane, r.lines[s], &y[s * RL::TS]); from_regs = true; }
+              }
+              if (!from_regs) {
                 typename RL::Lines l;
                 RL::load(own, (u32)(s * RL::TS), l);
                 RL::to_samples(c.ring_tile, lane, l, &y[s * RL::TS]);
               }
             }
-            if (all_ahead) {
+            if constexpr (AHEAD) {
+              if (all_ahead) {
 #pragma unroll
-              for (int s = 0; s < NS; ++s) RL::load(own, (u32)(T + s * RL::TS), r.lines[s]);
+                for (int s = 0; s < NS; ++s) RL::load(own, (u32)(T + s * RL::TS), r.lines[s]);
+              }
             }
             r.pre_pos = all_ahead && !dead ? np : 0xFFFFFFFFu;
 #pragma unroll
@@ -2150,7 +2163,7 @@ struct SampleDelay : StageDefaults {
       // Large tiles (the pipelined kernels, one wavefront per SIMD: nothing else hides HBM latency) are read one
       // tile ahead: this tile comes out of registers filled during the previous one, and the next tile's loads go
       // out before this tile's stores.  They cannot meet those stores when delay >= 2T (off <= len - 2T).
-      constexpr bool kAhead = T >= 16 && T <= kPrefetch;
+      constexpr bool kAhead = AHEAD && T >= 16 && T <= kPrefetch;
       bool have = false, ahead = false;
       u32 np = 0;
       if constexpr (kAhead) {
@@ -2214,6 +2227,8 @@ struct SampleDelay : StageDefaults {
     else if (rel == 0) r.wp = (u32)bits;
   }
 };
+typedef SampleDelayT<true> SampleDelay;
+typedef SampleDelayT<false> SampleDelayNoAhead;
 
 // AllpassDelay -- delay.rs:93-206: out = allpass(buffer[read]); read += 1; buffer[write] = x; write += 1 (both modulo the
 // ring), with a first-order allpass interpolator (delay.rs:53-90: out = coeff * (in - prev_out) + prev_in) for the

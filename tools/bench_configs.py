@@ -26,6 +26,8 @@ def run(name, n_voices=None, launches=16, blocks=32, allow_fma=False, host_threa
         b.param_apply_many(v, w.restart[0], w.restart[1], L.VALUE_TRIGGER)
     if w.delay_times is not None:
         b.param_apply_many(v, 3, 0, L.VALUE_FLOAT, w.delay_times)
+    for stage, param, values in w.param_sets:  # D4: every delay stage's delay_time and feedback
+        b.param_apply_many(v, stage, param, L.VALUE_FLOAT, values)
     step = [0]
     # the application's own work of deciding what changes when is not the engine's: C5's event arrays are made up front
     c5 = {}
@@ -66,6 +68,14 @@ def run(name, n_voices=None, launches=16, blocks=32, allow_fma=False, host_threa
         rd += 4 * w.block_size
         wr += 4 * w.block_size
     extra = {}
+    n_delays = sum(s.kind in (L.STAGE_SAMPLE_DELAY, L.STAGE_ALLPASS_DELAY, L.STAGE_ALLPASS_FB_DELAY) for s in w.stages)
+    if n_delays:  # ring traffic alone: a sample read and one written per delay stage and voice-sample (8 bytes in f32)
+        word = 8 if w.sample_type else 4
+        if n_delays > 1:
+            rd += n_delays * word * w.block_size
+            wr += n_delays * word * w.block_size
+        extra = {"delay_stages": n_delays, "signature": b.debug_signature(), "form": int(b.debug_words()[2]),
+                 "ring_TBps": 2 * word * n_delays * float(w.n_voices) * w.block_size * blocks * n / (kms * 1e-3) / 1e12}
     if name == "G1":  # 24 long rings + the two short ones, one sample read and one written per frame each; the staged input; two outputs
         word = 8 if w.sample_type else 4
         rd += (24 + 2 + 1) * word * w.block_size
@@ -199,6 +209,13 @@ if __name__ == "__main__":
         run("C3", n_voices=262144, launches=4)
         run("D3")
         run("D3", n_voices=65536)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "D4":  # five delay stages per voice, and D3's one beside them: BASELINE.md section 4, the D4 rows
+        for _ in range(int(sys.argv[2]) if len(sys.argv) > 2 else 1):
+            run("D3")
+            run("D3", n_voices=65536)
+            run("D4")
+            run("D4", n_voices=65536)
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "G1":  # the reverb: 4 096 voices, 64 blocks per launch; the same with no detune; D3 beside it
         run("G1", launches=8, blocks=64)
