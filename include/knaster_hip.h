@@ -664,7 +664,10 @@ int32_t knh_bank_param_apply_many_at(knh_bank* bank, uint32_t block_offset, size
 int32_t knh_bank_read_done_frames(knh_bank* bank, uint32_t* done_frames);
 /* Diagnostics: 16 device words of the last launch (0,1: the done/running summary; 4..8: per-role busy
  * cycles per tile when the library was built with -DKNH_DAG_STAMPS, zero otherwise).  Word 2 is filled in by the host: the
- * kernel form the bank's launches take (KNH_DEBUG_FORM_*; a bank cut into voice ranges reports its first range's). */
+ * kernel form the bank's launches take (KNH_DEBUG_FORM_*; a bank cut into voice ranges reports its first range's).
+ * Word 3 is filled in by the host too: in the two lane-per-frame forms the voices per workgroup that a launch over a whole
+ * block takes (a call over part of a block may take another number in the interpreted form), 0 in every other form;
+ * again the first range's for a bank cut into voice ranges. */
 enum {
   KNH_DEBUG_FORM_WHOLE_CHAIN = 0,       /* pre-built kernel, a wavefront runs a voice group's whole chain */
   KNH_DEBUG_FORM_PIPELINE = 1,          /* pre-built wave pipeline */

@@ -38,7 +38,7 @@ SVF_LOW, SVF_HIGH, SVF_BAND, SVF_NOTCH, SVF_PEAK, SVF_ALL, SVF_BELL, SVF_LOW_SHE
 # knh_mix_mode
 MIX_TREE, MIX_LEFT_FOLD = 0, 1
 FLAG_ANY_DONE, FLAG_ALL_DONE = 1, 2
-# KNH_DEBUG_FORM_*: word 2 of knh_bank_debug_words
+# KNH_DEBUG_FORM_*: word 2 of knh_bank_debug_words (word 3: voices per workgroup in the two FRAME forms, else 0)
 (DEBUG_FORM_WHOLE_CHAIN, DEBUG_FORM_PIPELINE, DEBUG_FORM_MANY_WAVE, DEBUG_FORM_WHOLE_CHAIN_FUSED, DEBUG_FORM_PIPELINE_FUSED,
  DEBUG_FORM_FRAME_INTERP, DEBUG_FORM_FRAME_JIT) = range(7)
 

@@ -118,6 +118,8 @@ const WideEntry* find_wide(const char* signature);
 // Voices that are large graphs of SinWt oscillators and arithmetic, a lane per frame (kernels_interp.hip).  rows:
 // [n_blocks][n_voices][block_size], every voice's signal (the fold kernels take it from there).
 size_t interp_lds_bytes(unsigned n_ops, unsigned n_state_words, unsigned n_sig, unsigned n_frames, bool f64, unsigned voices_per_workgroup = 1);
+// the voices per workgroup a launch over n_frames frames of n_voices voices takes (the launch and knh_bank_debug_words ask here)
+unsigned interp_voices_per_workgroup(unsigned n_voices, unsigned n_ops, unsigned n_state_words, unsigned n_sig, unsigned n_frames, bool f64);
 hipError_t launch_interp_f32(const knh_dev::VoiceKernelArgs<float>& a, const knh_dev::InterpOp* prog, unsigned n_ops, unsigned n_state_words,
                              unsigned n_sig, unsigned out_sig, float* rows, hipStream_t s);
 hipError_t launch_interp_f64(const knh_dev::VoiceKernelArgs<double>& a, const knh_dev::InterpOp* prog, unsigned n_ops, unsigned n_state_words,

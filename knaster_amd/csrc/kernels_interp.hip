@@ -141,17 +141,24 @@ size_t interp_lds_bytes(unsigned n_ops, unsigned n_state_words, unsigned n_sig, 
   return 16384 * sizeof(float) + (size_t)n_ops * sizeof(InterpOp) + (size_t)vpw * ((((size_t)n_state_words * w + 15u) & ~(size_t)15u) + (size_t)n_sig * n_frames * w);
 }
 
+// voices per workgroup (each on tpv = n_frames rounded up to whole wavefronts threads): as many as keep every CU busy (256
+// workgroups), fit 1 024 threads and the 160 KiB of LDS
+unsigned interp_voices_per_workgroup(unsigned n_voices, unsigned n_ops, unsigned n_state_words, unsigned n_sig, unsigned n_frames, bool f64) {
+  const unsigned tpv = ((n_frames + 63u) / 64u) * 64u;
+  unsigned vpw = n_voices / 256u;
+  if (vpw < 1u) vpw = 1u;
+  if (vpw > 1024u / tpv) vpw = 1024u / tpv;
+  while (vpw > 1u && interp_lds_bytes(n_ops, n_state_words, n_sig, n_frames, f64, vpw) > 158u * 1024u) --vpw;
+  return vpw;
+}
+
 template <typename F>
 static hipError_t launch_interp(const VoiceKernelArgs<F>& a, const InterpOp* prog, unsigned n_ops, unsigned n_state_words, unsigned n_sig,
                                 unsigned out_sig, F* rows, hipStream_t s) {
   const unsigned n_frames = a.frame_end - a.frame_begin;
   if (a.n_voices == 0 || n_frames == 0) return hipSuccess;
   const unsigned tpv = ((n_frames + 63u) / 64u) * 64u;  // threads per voice
-  // voices per workgroup: as many as keep every CU busy (256 workgroups), fit 1 024 threads and the 160 KiB of LDS
-  unsigned vpw = a.n_voices / 256u;
-  if (vpw < 1u) vpw = 1u;
-  if (vpw > 1024u / tpv) vpw = 1024u / tpv;
-  while (vpw > 1u && interp_lds_bytes(n_ops, n_state_words, n_sig, n_frames, sizeof(F) == 8, vpw) > 158u * 1024u) --vpw;
+  const unsigned vpw = interp_voices_per_workgroup(a.n_voices, n_ops, n_state_words, n_sig, n_frames, sizeof(F) == 8);
   const size_t lds = interp_lds_bytes(n_ops, n_state_words, n_sig, n_frames, sizeof(F) == 8, vpw);
   if (lds > 64 * 1024) {  // more than 64 KiB of dynamic LDS has to be asked for (per device: set where the launch goes)
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&voice_interp_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

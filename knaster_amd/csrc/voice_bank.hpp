@@ -2235,6 +2235,10 @@ struct Bank final : knh_bank {
     out16[2] = interp ? (frame_jit ? KNH_DEBUG_FORM_FRAME_JIT : KNH_DEBUG_FORM_FRAME_INTERP)
              : jit ? (jit_pipe ? KNH_DEBUG_FORM_PIPELINE_FUSED : KNH_DEBUG_FORM_WHOLE_CHAIN_FUSED)
              : wide_waves != 0 ? KNH_DEBUG_FORM_MANY_WAVE : pipe ? KNH_DEBUG_FORM_PIPELINE : KNH_DEBUG_FORM_WHOLE_CHAIN;
+    // word 3 (no kernel writes it): the voices per workgroup of a whole-block launch in the lane-per-frame forms, 0 in every other
+    out16[3] = !interp ? 0u
+             : frame_jit ? frame_vpw
+             : knh::interp_voices_per_workgroup(nv, static_cast<unsigned>(h_prog.size()), static_cast<unsigned>(n_slots), interp_sigs, static_cast<unsigned>(block_size), sizeof(F) == 8);
     return KNH_OK;
   }
   int synchronize() override {
