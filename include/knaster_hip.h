@@ -596,6 +596,14 @@ int32_t knh_bank_process_block_channels(knh_bank* bank, size_t frames_to_process
  * next call launches it again.  Results are those of a launch per call, bit for bit.  KNH_RESIDENT=0: a launch per call.
  * calls: process calls served by a resident kernel so far; launches: how many times one was launched.  Either may be NULL. */
 int32_t knh_bank_resident_stats(knh_bank* bank, uint64_t* calls, uint64_t* launches);
+/* How the bank's ordinary (non-resident) launches have been handed their parameter events so far.  A launch of a pipelined
+ * kernel form whose events are nothing but a few changes addressed to runs of neighbouring voices -- a bank's note-on and
+ * note-off, knh_bank_param_apply_range or a batch in rising voice order -- and all due inside the launch takes them as RANGE
+ * events in its kernel arguments (up to 16 of them); every other launch with events reads per-voice lists from pinned host
+ * memory.  range_launches / list_launches: launches of either kind; list_bytes: bytes of per-voice lists (events and their
+ * index) handed to kernels.  Results are the same bit for bit; KNH_RANGE_LAUNCHES=0 (read when the bank is created) keeps
+ * every launch on per-voice lists.  Any pointer may be NULL. */
+int32_t knh_bank_event_stats(knh_bank* bank, uint64_t* range_launches, uint64_t* list_launches, uint64_t* list_bytes);
 /* Diagnostics of the last call a resident kernel served, on the device's constant 100 MHz clock (ticks of 10 ns): [0] the
  * voice kernel saw the command, [1] the fold server's root did, [2] the first tile's rows had all arrived, [3] the last
  * tile's, [4] the root had written the block and the flags.  Zeros when no resident kernel has served a call. */

@@ -354,6 +354,12 @@ class VoiceBank:
         self._check(self._lib.knh_bank_resident_stats(self._h, C.byref(c), C.byref(n)))
         return int(c.value), int(n.value)
 
+    def event_stats(self):
+        """(launches that took range events, launches that took per-voice lists, bytes of those lists): knh_bank_event_stats"""
+        r, l, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.knh_bank_event_stats(self._h, C.byref(r), C.byref(l), C.byref(b)))
+        return int(r.value), int(l.value), int(b.value)
+
     def debug_words(self) -> np.ndarray:
         d = np.zeros(16, dtype=np.uint32)
         self._check(self._lib.knh_bank_debug_words(self._h, d.ctypes.data_as(C.c_void_p)))

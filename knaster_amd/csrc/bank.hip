@@ -627,6 +627,17 @@ int32_t knh_bank_resident_stats(knh_bank* bank, uint64_t* calls, uint64_t* launc
     return KNH_OK;
   });
 }
+int32_t knh_bank_event_stats(knh_bank* bank, uint64_t* range_launches, uint64_t* list_launches, uint64_t* list_bytes) {
+  return guarded(bank, [&]() -> int32_t {
+    if (!bank) return KNH_ERR_INVALID_ARGUMENT;
+    uint64_t three[3] = {0, 0, 0};
+    bank->event_stats(three);
+    if (range_launches) *range_launches = three[0];
+    if (list_launches) *list_launches = three[1];
+    if (list_bytes) *list_bytes = three[2];
+    return KNH_OK;
+  });
+}
 int32_t knh_bank_resident_trace(knh_bank* bank, uint64_t* ticks5) {
   return guarded(bank, [&]() -> int32_t {
     if (!bank || !ticks5) return KNH_ERR_INVALID_ARGUMENT;

@@ -116,6 +116,8 @@ struct knh_bank {
   virtual uint32_t ranks() const { return 1; }
   virtual void resident_stats(uint64_t* calls, uint64_t* launches) { if (calls) *calls = 0; if (launches) *launches = 0; }
   virtual void resident_trace(uint64_t* five) { for (int k = 0; k < 5; ++k) five[k] = 0; }
+  // knh_bank_event_stats: [0] launches that took range events, [1] launches that took per-voice lists, [2] bytes of those lists
+  virtual void event_stats(uint64_t* three) { for (int k = 0; k < 3; ++k) three[k] = 0; }
 
   int fail(int code, const std::string& msg) {
     err = msg;

@@ -502,6 +502,14 @@ struct ShardedBank final : knh_bank {
     if (launches) *launches = count;
     return KNH_OK;
   }
+  void event_stats(uint64_t* three) override {  // the shards' launches, summed
+    for (int j = 0; j < 3; ++j) three[j] = 0;
+    for (int k = 0; k < n(); ++k) {
+      uint64_t t[3] = {0, 0, 0};
+      shard[k]->event_stats(t);
+      for (int j = 0; j < 3; ++j) three[j] += t[j];
+    }
+  }
 };
 
 }  // namespace

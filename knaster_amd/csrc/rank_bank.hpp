@@ -406,6 +406,10 @@ struct RankBank final : knh_bank {
     if (!local) { if (ms) *ms = 0.0; if (launches) *launches = 0; return KNH_OK; }
     return adopt(local->timing_read(ms, launches));
   }
+  void event_stats(uint64_t* three) override {
+    if (local) local->event_stats(three);
+    else knh_bank::event_stats(three);
+  }
 };
 
 }  // namespace

@@ -82,7 +82,8 @@ struct Bank final : knh_bank {
   // The same change for a run of neighbouring voices (a whole bank's note-on or note-off in one knh_bank_param_apply_many):
   // one record instead of an event per voice.  `at` = how many events `pending` held when it arrived (its place in the
   // application order).  A resident call whose events are nothing but a few of these passes them on as they are (ResCall,
-  // voice_chain.hpp: 32 bytes each over PCIe instead of 16 per voice); anything else turns them into per-voice events first.
+  // voice_chain.hpp: 32 bytes each over PCIe instead of 16 per voice), and so does an ordinary launch of a pipelined kernel
+  // (in its kernel arguments: upload_events); anything else turns them into per-voice events first.
   struct RangeEvent { uint32_t v0, v1, frame, op, slot; uint64_t bits; size_t at; };
   std::vector<RangeEvent> pending_ranges, sent_ranges;
   uint32_t res_n_ranges = 0;         // the list upload_events has just made holds this many range events (0: per-voice lists)
@@ -104,6 +105,16 @@ struct Bank final : knh_bank {
   }
   // the bank's resident kernel form walks range events: the pipelined kernels (voice_pipe.hpp), not the one-wavefront kernel
   bool res_ranges_ok() const { return jit ? jit_pipe : pipe != nullptr; }
+  // ... and so does an ORDINARY launch of one (launch_voice: the fused kernel first, then the many-wavefront forms, then the
+  // pipeline): its range events travel in the kernel arguments.  KNH_RANGE_LAUNCHES=0, read when the bank is made: every
+  // launch takes per-voice lists, as before (A/B runs, tests).
+  bool launch_ranges_ok() const { return !interp && (jit ? jit_pipe : (wide_waves == 0 && pipe != nullptr)); }
+  bool range_launches = [] { const char* e = std::getenv("KNH_RANGE_LAUNCHES"); return !(e && e[0] == '0'); }();
+  uint32_t launch_n_ranges = 0;      // the launch upload_events has just prepared takes this many range events (0: per-voice lists, or none)
+  Event launch_range_recs[2 * knh_dev::LAUNCH_RANGES_MAX];
+  // knh_bank_event_stats: launches that took range events, launches that took per-voice lists, bytes of lists handed to kernels
+  uint64_t ev_range_launches = 0, ev_list_launches = 0, ev_list_bytes = 0;
+  void event_stats(uint64_t* three) override { three[0] = ev_range_launches; three[1] = ev_list_launches; three[2] = ev_list_bytes; }
   uint32_t frame_base = 0;           // absolute frame of frame 0 of the block being assembled
   // param_apply / set_delay calls addressed to later blocks of the next multi-block launch
   struct Call { uint8_t is_delay; uint16_t delay; uint32_t voice, stage, param, kind; double f; int64_t i; };
@@ -310,6 +321,7 @@ struct Bank final : knh_bank {
     a.done_frames = d_done;
     a.flags = d_flags;
     a.res = knh_dev::Resident{};
+    a.n_ranges = 0;
   }
   // timing
   bool timing = false;
@@ -1818,15 +1830,35 @@ struct Bank final : knh_bank {
   // Events addressed past the blocks of this launch (a call for block k of a later launch, turned into patches at once):
   // they stay in `pending`, k launches' worth of blocks earlier, for the next launch.
   std::vector<HostEvent> later;
-  int upload_events(hipStream_t s, bool* have_events, uint32_t n_blocks, bool allow_ranges = false) {
+  // allow_ranges: the call goes to a resident launch of a pipelined kernel (up to 15 range events ride with its command);
+  // launch_ranges: to an ordinary launch of one, which takes up to LAUNCH_RANGES_MAX in its kernel arguments (launch_n_ranges,
+  // launch_range_recs) -- nothing is written to the pinned lists then, and no workgroup reads host memory for its events.
+  int upload_events(hipStream_t s, bool* have_events, uint32_t n_blocks, bool allow_ranges = false, bool launch_ranges = false) {
     *have_events = false;
     later.clear();
     res_n_ranges = 0;
+    launch_n_ranges = 0;
     const uint64_t horizon = static_cast<uint64_t>(n_blocks) * block_size;
     if (!pending_ranges.empty()) {
-      bool as_ranges = allow_ranges && pending.empty() && pending_ranges.size() <= 15;
+      bool as_ranges = (allow_ranges || launch_ranges) && pending.empty() && pending_ranges.size() <= (allow_ranges ? 15u : static_cast<size_t>(knh_dev::LAUNCH_RANGES_MAX));
       for (const RangeEvent& r : pending_ranges) as_ranges = as_ranges && r.frame < horizon;
       if (!as_ranges) expand_ranges();
+    }
+    if (!allow_ranges && launch_ranges && !pending_ranges.empty()) {  // (pending is empty: see above)
+      // Every voice walks the records in order and applies those due: in frame order, then, calls for one frame in the order
+      // they arrived -- the order the per-voice lists are sorted into below.
+      std::stable_sort(pending_ranges.begin(), pending_ranges.end(), [](const RangeEvent& x, const RangeEvent& y) { return x.frame < y.frame; });
+      for (size_t j = 0; j < pending_ranges.size(); ++j) {
+        const RangeEvent& r = pending_ranges[j];
+        launch_range_recs[2 * j] = Event{r.frame, (r.slot & 0xFFFFFFu) | (r.op << 24), r.bits};
+        launch_range_recs[2 * j + 1] = Event{r.v0, r.v1, 0ull};
+      }
+      launch_n_ranges = static_cast<uint32_t>(pending_ranges.size());
+      pending_ranges.clear();
+      pending_needs_sort = false;
+      pending_max_frame = 0;
+      *have_events = true;
+      return KNH_OK;
     }
     if (pending_max_frame >= horizon && !pending.empty()) {
       size_t w = 0;
@@ -1990,7 +2022,9 @@ struct Bank final : knh_bank {
     const bool res_now = sync && out_host && !out_device && !voices_host && !stream && n_blocks == 1 && fe > fb && !accumulate && !timing &&
                          !resolver.pending() && res_possible() && resident.enabled() && resident.ready();
     bool have_events = false;
-    int rc = upload_events(s, &have_events, n_blocks, res_now && res_ranges_ok());
+    // (the device's resolver merges the host's per-voice lists into its own: lists it is, then)
+    const bool ranges_now = !res_now && range_launches && launch_ranges_ok() && !resolver.pending();
+    int rc = upload_events(s, &have_events, n_blocks, res_now && res_ranges_ok(), ranges_now);
     if (rc != KNH_OK) return rc;
     if (!future.empty()) {  // calls addressed beyond this launch move up; those now due for the next
                             // block are applied right away, ahead of anything that arrives later
@@ -2078,14 +2112,23 @@ struct Bank final : knh_bank {
       }
       in_blocks_set = 0;  // one set_input per process call
     }
-    a.ev_start = have_events ? h_ev_start : nullptr;  // pinned host memory, device-visible
+    a.ev_start = have_events && !launch_n_ranges ? h_ev_start : nullptr;  // pinned host memory, device-visible
     a.events = h_events;
+    if (launch_n_ranges) {  // the launch's events are range events: they travel in the kernel arguments
+      a.n_ranges = launch_n_ranges;
+      std::copy(launch_range_recs, launch_range_recs + 2 * launch_n_ranges, a.ranges);
+      ev_range_launches += 1;
+    } else if (have_events) {
+      ev_list_launches += 1;
+      ev_list_bytes += static_cast<uint64_t>(h_ev_start[nv]) * sizeof(Event) + (static_cast<uint64_t>(nv) + 1u) * sizeof(uint32_t);
+    }
     if (resolver.pending()) {  // calls to nodes whose queues the device resolves: the lists are made there, the host's merged in
       DevEventResolver::Lists lists{};
       int r2 = resolver.resolve(s, n_blocks, fb, fe, have_events ? h_ev_start : nullptr, h_events, have_events ? h_ev_start[nv] : 0u, &lists);
       if (r2 != KNH_OK) return r2;
       a.ev_start = lists.ev_start;
       a.events = lists.events;
+      if (!have_events) ev_list_launches += 1;  // (lists the device made: a per-voice list launch all the same)
     }
     a.voices_out = want_voices ? (stage_out ? stage_out : d_voices) : nullptr;
     a.flags = flags_now;

@@ -569,6 +569,9 @@ __device__ __forceinline__ ResCall res_wait(const Resident& r, u32 expect, u32* 
   const u64 c = (u64)slot[0] | ((u64)slot[1] << 32);
   return res_unpack(c);
 }
+// Range events an ordinary launch takes in its kernel arguments (VoiceKernelArgs::ranges): 16 of them are 512 bytes of
+// arguments and of LDS staging, which every pipelined form has beside its tiles (voice_pipe_kernel, Lds::ev_stage).
+enum : u32 { LAUNCH_RANGES_MAX = 16 };
 template <typename F>
 struct VoiceKernelArgs {
   typename WordOf<F>::type* state;  // [n_slots][stride]
@@ -598,6 +601,11 @@ struct VoiceKernelArgs {
   u32* done_frames;                 // [n_voices]
   u32* flags;                       // [0] |= any-done, [1] += voices whose last envelope is not Stopped
   Resident res;                     // res.bell != null: a resident launch (one block per command; frame_begin / frame_end / ev_start / events come with each command)
+  // An ordinary launch of a pipelined kernel whose events are nothing but a few RANGE events (ResCall above: the same change for
+  // a run of neighbouring voices, a bank's note-on and note-off) carries them in the kernel arguments themselves: n_ranges of
+  // them, two records each as in a resident call's list; ev_start is null then and no workgroup reads an event from host memory.
+  u32 n_ranges;
+  Event ranges[2 * LAUNCH_RANGES_MAX];
 };
 
 constexpr int kWave = 64;

@@ -117,6 +117,7 @@ template <typename F> struct PipeShared {
   // during which the wave -- and at the next barrier its whole pipeline -- stands still).  ev_lds_n == 0: read in place.
   const Event* ev_lds;
   u32 ev_lds_first, ev_lds_n;
+  u32 launch_ranges;  // an ordinary launch: its events are this many range events, staged as records 0 .. 2 n - 1 of ev_lds (0: per-voice lists)
   // a resident launch (voice_chain.hpp, Resident): two words for the command, and where the stage groups leave what the
   // mixer wavefront reports per call: [group wavefront][lane] the group's done mark, then [lane] "the voice's last envelope is running"
   u32* res_slot;
@@ -203,8 +204,9 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
   // tile reads that were just issued; the wait belongs where the event is fetched, not where its frame is looked at).
   u32 next_frame = 0xFFFFFFFFu;
   auto note_next = [&]() { asm volatile("v_mov_b32 %0, %1" : "=v"(next_frame) : "v"(nxt.frame)); };
-  // a resident call whose events are range events (ResCall): event i is record 2 i of the list, record 2 i + 1 says which
-  // voices it is for; ev_i walks all of them and stops at those that cover this lane's voice
+  // a resident call or an ordinary launch whose events are range events (ResCall, VoiceKernelArgs::ranges): event i is record
+  // 2 i of the list, record 2 i + 1 says which voices it is for; ev_i walks all of them and stops at those that cover this
+  // lane's voice
   bool ev_ranged = false;
   auto take_next = [&]() {  // ev_i: the next candidate
     if (ev_ranged) {
@@ -245,6 +247,9 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
     ev_lds_first = st.first;
     ev_ranged = call.has_events && call.n_ranges != 0u;
     if (ev_ranged) { evs = nullptr; ev_i = 0; ev_end = call.n_ranges; }
+  } else if (sh.launch_ranges != 0u) {  // an ordinary launch with range events: the kernel has staged its 2 n records (ev_staged, first record 0)
+    ev_ranged = true;
+    ev_i = 0; ev_end = sh.launch_ranges;
   }
   if (!ev_ranged) {
     ev_i = 0; ev_end = 0;
@@ -718,7 +723,7 @@ __global__ void __launch_bounds__((GPW * PipeWaves<T, MODE, Gs...>::value * 64))
   struct Lds {
     float sine[kSine ? 16384 : 4];
     __attribute__((aligned(16))) F edge[GPW * kEdgeElems];
-    __attribute__((aligned(16))) Event ev_stage[kEvCap > 0 ? kEvCap : 1];
+    __attribute__((aligned(16))) Event ev_stage[kEvCap > 2 * (int)LAUNCH_RANGES_MAX ? kEvCap : 2 * (int)LAUNCH_RANGES_MAX];  // (a launch's range events always fit)
     __attribute__((aligned(16))) char ring_tiles[GPW * kRingTiles > 0 ? GPW * kRingTiles * RingLines<F>::kTileBytes : 16];
     u32 res_marks[16 * 64];  // a resident launch: the groups' done marks and running flags of the call (PipeShared)
     u32 res_slot[16];        // ... and its command word
@@ -740,7 +745,17 @@ __global__ void __launch_bounds__((GPW * PipeWaves<T, MODE, Gs...>::value * 64))
   // instructions (tools/micro/valu_issue.hip: with two waves on a SIMD scalar ops keep their rate, packed f32 ops do not).
   const int wave = GPW > 1 ? (wave_all + (grp ? WAVES / 2 : 0)) % WAVES : wave_all;
   u32 ev_first = 0, ev_count = 0;
-  if (kEvCap > 0 && a.ev_start && !a.res.bell) {  // (the groups' voices are neighbours: one contiguous piece of the list, which is sorted by voice)
+  const u32 launch_ranges = a.res.bell ? 0u : (a.n_ranges < (u32)LAUNCH_RANGES_MAX ? a.n_ranges : (u32)LAUNCH_RANGES_MAX);
+  if (launch_ranges != 0u) {
+    // Range events: every workgroup stages the same 2 n records, out of the kernel arguments (scalar loads at constant
+    // offsets; one lane stores them) -- no ev_start, no read of host memory.
+    ev_count = 2u * launch_ranges;
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (u32 j = 0; j < 2u * (u32)LAUNCH_RANGES_MAX; ++j)
+        if (j < ev_count) ev_stage[j] = a.ranges[j];
+    }
+  } else if (kEvCap > 0 && a.ev_start && !a.res.bell) {  // (the groups' voices are neighbours: one contiguous piece of the list, which is sorted by voice)
     const u32 gv0 = blockIdx.x * (u32)(GPW * 64);
     const u32 gnv = a.n_voices - gv0 < (u32)(GPW * 64) ? a.n_voices - gv0 : (u32)(GPW * 64);
     ev_first = a.ev_start[gv0];
@@ -768,6 +783,7 @@ __global__ void __launch_bounds__((GPW * PipeWaves<T, MODE, Gs...>::value * 64))
   sh.ev_lds = ev_stage;
   sh.ev_lds_first = ev_first;
   sh.ev_lds_n = ev_count;
+  sh.launch_ranges = launch_ranges;
   sh.res_slot = lds.res_slot;
   sh.res_marks = lds.res_marks;
   sh.ev_stage = ev_stage;
