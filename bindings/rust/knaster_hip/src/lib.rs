@@ -82,6 +82,16 @@ pub fn stage(kind: u16) -> Stage {
 pub fn galactic(replace: f64, detune: f64, brightness: f64, bigness: f64, wet: f64, fpd_l: u32, fpd_r: u32) -> (Stage, [f64; 7]) {
     (stage(KNH_STAGE_GALACTIC), [replace, detune, brightness, bigness, wet, fpd_l as f64, fpd_r as f64])
 }
+/// `(l | r) >> g.push(Galactic::new(..))`: the reverb with two different signals of the voice on its inputs.  `l` and `r` are
+/// the 0-based indices, in the stage list, of the stages whose node outputs feed input 0 and input 1 (`input = l + 1`,
+/// `input2 = r + 1`); neither may be a `KNH_STAGE_INPUT` stage (put a bank input through `* 1.0`).  Arguments as `galactic`.
+#[allow(clippy::too_many_arguments)]
+pub fn galactic_stereo(l: u16, r: u16, replace: f64, detune: f64, brightness: f64, bigness: f64, wet: f64, fpd_l: u32, fpd_r: u32) -> (Stage, [f64; 7]) {
+    let (mut s, ctor) = galactic(replace, detune, brightness, bigness, wet, fpd_l, fpd_r);
+    s.input = l + 1;
+    s.input2 = r + 1;
+    (s, ctor)
+}
 /// The six `Math1UGen` stages, named as the reference's factories are (knaster/src/math_ugens.rs): `x >> sqrt()` is
 /// `[.., sqrt()]` in the stage list.  No constructor arguments, no parameters.
 pub fn fract() -> Stage {

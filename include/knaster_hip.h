@@ -188,7 +188,20 @@ typedef enum knh_value_kind {
  * KNH_STAGE_GALACTIC        (voice).out([0, 0]) >> g.push(Galactic::new(replace, detune, brightness, bigness, wet))
  *                                                               knaster_airwindows/src/galactic.rs:14-400   1    replace, detune, brightness, bigness, wet, fpd_l, fpd_r
  *     the stereo reverb (Inputs = U2, Outputs = U2), one per voice: both inputs are the voice's running mono signal, the two
- *     outputs go to graph out 0 and out 1.  Must be the LAST stage, the bank must have out_channels = 2, and the chain holds
+ *     outputs go to graph out 0 and out 1.
+ *     STEREO INPUT, `(l | r) >> g.push(Galactic::new(..))`: input = l + 1 AND input2 = r + 1 (both non-zero, ar_param = 0) --
+ *     the output of stage l feeds the reverb's input 0, the output of stage r its input 1, each with its own 256-sample detune
+ *     ring, first filter, faint-input dither floor (tested per channel, galactic.rs:210-219) and dry path.  "The output of
+ *     stage k" is the node's output, behind the wrapper stages that follow it (knh_stage_desc.input); a
+ *     KNH_STAGE_FLAG_READER_CH1 stage may be named (the stereo sampler through the reverb); l == r is allowed, and naming
+ *     the last stage before the reverb twice is the mono form.  The chain before the reverb is then the voice with two
+ *     connected outputs (l, r) that knh_bank_connect_outputs makes of that stage list: the same signature, the same fused
+ *     kernel.  Refused (KNH_ERR_INVALID_ARGUMENT): input2 without input; input alone unless it names the stage before (the
+ *     mono form); either operand naming a KNH_STAGE_INPUT stage (put the input through `* 1.0`); a forward reference.
+ *     Parameter addressing, calls addressed to a block of a launch, partial blocks, both mix modes, per-voice output and done
+ *     frames are those of the mono form; knh_bank_algorithmic_bytes_per_voice_block counts the second staging plane (after
+ *     knh_bank_init: it is block_size samples written and read).
+ *     Must be the LAST stage, the bank must have out_channels = 2, and the chain holds
  *     no other delay-ring stage and no Pan2; delayed_changes_per_block = 0 and ar_param = 0 (its parameters take effect at
  *     the next process call, as in the reference).  Per-voice output is [2][n_voices][block_size] and the mix planes are the
  *     two channels, as for a Pan2 chain; both mix modes.  A bank with this stage is one voice range on one device (no host
@@ -332,7 +345,8 @@ typedef struct knh_stage_desc {
    * chain on one running signal.  k > 0: the output of stage k - 1 of this list (an earlier one), so that a signal can feed
    * several stages and stages need not follow their input directly.  Source stages read nothing (except SIN_WT with
    * KNH_STAGE_FLAG_AR_FREQ, whose frequency this signal drives); wrapper stages (KNH_STAGE_WR_*) wrap the stage before
-   * them and keep 0.  `input2` is the second operand of the KNH_STAGE_MATH_* stages and 0 everywhere else.
+   * them and keep 0.  `input2` is the second operand of the KNH_STAGE_MATH_* stages, the driver of an audio-rate parameter
+   * (ar_param) and, together with `input`, the right input of KNH_STAGE_GALACTIC (`input` its left one); 0 everywhere else.
    * (A voice with several envelope stages reports, as its done frame, the mark of the last of them in the reference's
    * TASK order that finished in the block -- one UGenFlags for all tasks of a graph, graph_gen.rs:196-200.  For a chain
    * that is list order; for a graph it is the order Graph::calculate_node_order gives: depth first from the voice's output,
@@ -478,7 +492,7 @@ uint32_t knh_bank_buffer_count(const knh_bank* bank, uint32_t stage);
  * like any graph: at most 512 stages -- also when it is made of SinWt oscillators and arithmetic only (the lane-per-frame
  * kernels, which take up to 4 096 stages, hand out one signal per voice and do not run a connected voice).
  * Refused, each with a knh_last_error text and leaving the bank as it was: a null argument, n_channels != 2, a bank whose
- * out_channels is not 2, a chain that ends in KNH_STAGE_PAN2 or KNH_STAGE_GALACTIC, a named stage of kind KNH_STAGE_INPUT
+ * out_channels is not 2, a chain that ends in KNH_STAGE_PAN2 or KNH_STAGE_GALACTIC (with or without a stereo input), a named stage of kind KNH_STAGE_INPUT
  * (an output connection starts at a node: put the input through `* 1.0`), a call after knh_bank_init
  * (KNH_ERR_INVALID_ARGUMENT); a named stage >= n_stages (KNH_ERR_OUT_OF_RANGE); a connected voice of more than 512 stages
  * (KNH_ERR_UNSUPPORTED_CHAIN). */

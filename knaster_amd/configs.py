@@ -73,6 +73,7 @@ class Workload:
     buffer: tuple = None  # (stage, samples, sample_rate): the Buffer of a BufferReader stage
     in_channels: int = 0  # UGen::Inputs of the bank node (KNH_STAGE_INPUT stages read them)
     param_sets: tuple = ()  # D4: (stage, param, per-voice float values) set on every voice before block 0
+    restart_more: tuple = ()  # G2: further (stage, param) triggers fired on every voice together with `restart`
 
 
 def config(name: str, n_voices: int | None = None, block_size: int | None = None, sample_type: int | None = None,
@@ -82,7 +83,8 @@ def config(name: str, n_voices: int | None = None, block_size: int | None = None
     defaults = {"C1": (1, 64, L.F32), "C2": (1024, 256, L.F32), "C3": (16384, 512, L.F32),
                 "C4": (65536, 512, L.F64), "C5": (4096, 128, L.F32),
                 "D3": (16384, 512, L.F32), "B3": (16384, 512, L.F32), "M1": (600, 64, L.F32), "P3": (16384, 512, L.F32),
-                "G1": (4096, 512, L.F32), "D4": (16384, 512, L.F32)}
+                "G1": (4096, 512, L.F32), "D4": (16384, 512, L.F32),
+                "G2": (4096, 512, L.F32)}
     nv, bs, st = defaults[name]
     nv = n_voices or nv
     bs = block_size or bs
@@ -122,6 +124,15 @@ def config(name: str, n_voices: int | None = None, block_size: int | None = None
                         unit(p["release"], 0.05, 0.3), unit(p["fm_ratio"], 1.0, 4.0), seeds[:, 0], seeds[:, 1]], axis=1)
         w.ctor = {0: col(p["freq"]), 1: col(np.full(nv, 0.25)), 2: np.tile([0.001, 0.002], (nv, 1)), 3: gal}
         w.restart = (2, 2)
+    elif name == "G2":  # not a BASELINE.json config: G1 with two plucked sines 7 cents apart on the reverb's left and right input
+        w = Workload(name, [Stage(L.STAGE_SIN_WT), Stage(L.STAGE_WR_MUL), Stage(L.STAGE_MUL_ENV_AR),
+                            Stage(L.STAGE_SIN_WT), Stage(L.STAGE_WR_MUL), Stage(L.STAGE_MUL_ENV_AR),
+                            Stage(L.STAGE_GALACTIC, input=3, input2=6)], nv, bs, st,
+                     description="(SinWt.wr_mul(0.25) * EnvAr | SinWt(7 cents up).wr_mul(0.25) * EnvAr) >> Galactic(replace, detune, brightness, bigness, wet)")
+        g1 = config("G1", n_voices=nv, block_size=bs, sample_type=st)  # the reverb's settings and seeds
+        w.ctor = {0: g1.ctor[0], 1: g1.ctor[1], 2: g1.ctor[2], 3: g1.ctor[0] * 2.0 ** (7.0 / 1200.0), 4: g1.ctor[1], 5: g1.ctor[2], 6: g1.ctor[3]}
+        w.restart = (2, 2)
+        w.restart_more = ((5, 2),)
     elif name == "P3":  # not a BASELINE.json config: the C3 voice panned (Pan2 behind the envelope)
         w = Workload(name, [Stage(L.STAGE_SIN_WT), Stage(L.STAGE_WR_MUL), Stage(L.STAGE_SVF),
                             Stage(L.STAGE_MUL_ENV_ASR, delayed_changes_per_block=precise), Stage(L.STAGE_PAN2)], nv, bs, st,

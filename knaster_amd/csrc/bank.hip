@@ -220,15 +220,23 @@ knh_bank* make_galactic(const knh_bank_desc& d, const std::string& inner_sig) {
   std::unique_ptr<GalacticBank<F>> b(new GalacticBank<F>());
   knh_bank_desc di = d;
   di.n_stages = d.n_stages - 1;
-  di.out_channels = 1;
+  // (l | r) >> Galactic: the chain before the reverb is a voice with two connected outputs, the reverb's left and right input
+  // (naming the last stage twice is the mono spelling: one signal, one staging plane)
+  uint32_t outs[2];
+  const bool stereo_in = galactic_inputs(d.stages, d.n_stages, outs);
+  di.out_channels = stereo_in ? 2 : 1;
   di.mix_mode = KNH_MIX_TREE;
   b->inner.reset(static_cast<Bank<F>*>(make_bank<F>(di, knh::find_kernel(inner_sig.c_str()), inner_sig)));
+  if (stereo_in) b->inner->set_outputs(true, outs[0], outs[1], inner_sig);
+  b->stereo_in = stereo_in;
   b->desc = d;
   b->nv = d.n_voices;
   b->gstage = d.n_stages - 1;
   b->stages = b->inner->stages;
   const KindInfo& k = kKinds[KNH_STAGE_GALACTIC];
-  b->stages.push_back(StageInfo{KNH_STAGE_GALACTIC, 0, 0, b->inner->n_slots, k.n_slots, k.n_params, k.n_ctor, b->inner->n_params_total, 0, 0, 0});
+  const knh_stage_desc& g = d.stages[d.n_stages - 1];
+  b->stages.push_back(StageInfo{KNH_STAGE_GALACTIC, 0, 0, b->inner->n_slots, k.n_slots, k.n_params, k.n_ctor, b->inner->n_params_total,
+                                 static_cast<uint16_t>(stereo_in ? g.input : 0), static_cast<uint16_t>(stereo_in ? g.input2 : 0), 0});
   b->n_slots = b->inner->n_slots;
   b->n_params_total = b->inner->n_params_total + k.n_params;
   b->gctor.assign(static_cast<size_t>(d.n_voices) * 7, 0.0);
@@ -340,7 +348,10 @@ static int32_t check_desc(const knh_bank_desc* desc, knh_bank** out_bank, std::s
       if (desc->out_channels != 2) { g_create_error = "a chain ending in Galactic has two output channels (out_channels = 2)"; return KNH_ERR_INVALID_ARGUMENT; }
       if (desc->n_stages < 2) { g_create_error = "stage needs a preceding signal"; return KNH_ERR_INVALID_ARGUMENT; }
       // the signature the kernels are looked up by is that of the chain BEFORE the reverb (galactic_bank.hpp)
-      rc = build_signature(desc->stages, desc->n_stages - 1, sig, &why);
+      // ... with the reverb's left and right input as its two connected outputs, if they are named (knh_bank_connect_outputs' signature)
+      uint32_t outs[2];
+      const bool stereo_in = galactic_inputs(desc->stages, desc->n_stages, outs);
+      rc = build_signature(desc->stages, desc->n_stages - 1, sig, &why, stereo_in ? outs : nullptr);
       if (rc != KNH_OK) { g_create_error = why; return rc; }
     }
     return KNH_OK;
@@ -819,6 +830,10 @@ int32_t knh_bank_algorithmic_bytes_per_voice_block(const knh_bank* bank, uint32_
         case KNH_STAGE_POLYBLEP: w += word; break;
         case KNH_STAGE_BUFFER_READER: w += s.ch1() ? 0 : word * 3; break;  // + two Buffer samples read per frame (two frames of two with a second output)
         case KNH_STAGE_ALLPASS_DELAY: case KNH_STAGE_ALLPASS_FB_DELAY: w += word * 4; break;  // + one sample read and one written per frame (ring in HBM)  // + one sample read and one written per frame (ring in HBM)
+        // (l | r) >> Galactic: the second staging plane, written by the chain before the reverb and read by it (0 before knh_bank_init)
+        case KNH_STAGE_GALACTIC:
+          if (s.input2 != 0) { r += word * static_cast<uint32_t>(bank->block_size); w += word * static_cast<uint32_t>(bank->block_size); }
+          break;
         default: break;
       }
     }

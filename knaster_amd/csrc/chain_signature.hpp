@@ -53,7 +53,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     // operands: `input` / `input2` name the stage whose output is read (1 + its index), 0 = the stage before this one
     if (st[i].input > i || st[i].input2 > i) { *why = "a stage reads the output of an earlier stage"; return KNH_ERR_INVALID_ARGUMENT; }
     if (math2 && (st[i].input == 0 || st[i].input2 == 0)) { *why = "a KNH_STAGE_MATH_* stage names both of its operands (input, input2)"; return KNH_ERR_INVALID_ARGUMENT; }
-    if (!math2 && st[i].input2 != 0 && st[i].ar_param == 0) { *why = "input2 is the second operand of the KNH_STAGE_MATH_* stages and the driver of an audio-rate parameter (ar_param)"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (!math2 && st[i].input2 != 0 && st[i].ar_param == 0 && st[i].kind != KNH_STAGE_GALACTIC) { *why = "input2 is the second operand of the KNH_STAGE_MATH_* stages, the driver of an audio-rate parameter (ar_param) and the right input of Galactic"; return KNH_ERR_INVALID_ARGUMENT; }
     if (math2 && st[i].ar_param != 0) { *why = "a KNH_STAGE_MATH_* stage has no parameters"; return KNH_ERR_INVALID_ARGUMENT; }
     if (is_math1_kind(st[i].kind)) {  // Math1UGen (math.rs:167-305): one operand (`input`), no parameters -- nothing an audio-rate link, WrPreciseTiming or WrSmoothParams could act on
       if (st[i].ar_param != 0 || st[i].input2 != 0) { *why = "a KNH_STAGE_MATH1_* stage has no parameters (ar_param = 0, input2 = 0)"; return KNH_ERR_INVALID_ARGUMENT; }
@@ -75,9 +75,15 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     if (st[i].kind == KNH_STAGE_GALACTIC) {  // the reverb ends a chain of its own kind (galactic_bank.hpp)
       if (i + 1 != n) { *why = "Galactic ends the chain: it must be the last stage"; return KNH_ERR_INVALID_ARGUMENT; }
       if (st[i].delayed_changes_per_block > 0) { *why = "Galactic cannot be wrapped in WrPreciseTiming here (its parameters take effect at the next process call)"; return KNH_ERR_INVALID_ARGUMENT; }
-      if (st[i].ar_param != 0 || st[i].input2 != 0) { *why = "Galactic has no audio-rate parameter (ar_param = 0, input2 = 0)"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (st[i].ar_param != 0) { *why = "Galactic has no audio-rate parameter (ar_param = 0)"; return KNH_ERR_INVALID_ARGUMENT; }
       if (st[i].flags != 0) { *why = "Galactic takes no stage flags"; return KNH_ERR_INVALID_ARGUMENT; }
-      if (st[i].input != 0 && st[i].input != i) { *why = "both inputs of Galactic are the voice's running signal (input = 0)"; return KNH_ERR_INVALID_ARGUMENT; }
+      // (l | r) >> Galactic: input and input2 name the stages that feed its left and right input; neither: the running signal on both
+      if (st[i].input2 != 0 && st[i].input == 0) { *why = "Galactic's right input (input2) is named together with its left one (input)"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (st[i].input2 == 0 && st[i].input != 0 && st[i].input != i) { *why = "Galactic names both of its inputs (input, input2) or neither (both are the voice's running signal then)"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (st[i].input2 != 0 && (st[st[i].input - 1].kind == KNH_STAGE_INPUT || st[st[i].input2 - 1].kind == KNH_STAGE_INPUT)) {
+        *why = "an input of Galactic starts at a node, not at a bank input (put the input through `* 1.0`)";
+        return KNH_ERR_INVALID_ARGUMENT;
+      }
       if (sig->find_first_of("DYZ") != std::string::npos) { *why = "a chain that ends in Galactic holds no other delay stage"; return KNH_ERR_INVALID_ARGUMENT; }
     }
     if (st[i].ar_param != 0) {  // an audio-rate parameter: the node's float parameter ar_param - 1 is driven by the signal input2 names
@@ -172,6 +178,20 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     if (connected) *sig += ":" + std::to_string(slot[outs[0]]) + "," + std::to_string(slot[outs[1]]);  // "#R:l,r": the slots of the two connected outputs
   }
   return KNH_OK;
+}
+
+// A chain that ends in KNH_STAGE_GALACTIC (checked by build_signature): the node-output stages, in the chain before the
+// reverb, of the signals on its left and right input.  False: the mono spelling, both inputs are the last stage's signal.
+inline bool galactic_inputs(const knh_stage_desc* st, uint32_t n, uint32_t outs[2]) {
+  const knh_stage_desc& g = st[n - 1];
+  outs[0] = outs[1] = n - 2;
+  if (g.input2 == 0) return false;
+  const uint32_t op[2] = {g.input, g.input2};
+  for (int c = 0; c < 2; ++c) {
+    outs[c] = op[c] - 1u;
+    while (outs[c] + 1 < n - 1 && is_wrapper_kind(st[outs[c] + 1].kind)) ++outs[c];
+  }
+  return !(outs[0] == n - 2 && outs[1] == n - 2);
 }
 
 // The signature of a voice made of SinWt oscillators and arithmetic alone, Math1UGen's functions included (interp_can_run) -> the program of the

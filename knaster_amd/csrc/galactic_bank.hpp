@@ -3,7 +3,11 @@
 // untouched) that renders each block's per-voice signals into a staging buffer, [n_voices][block_size] -- 8 bytes per
 // voice-sample against the ~200 the reverb's rings move -- and the reverb kernel (voice_galactic.hpp) reads them, one
 // wavefront per voice, and writes the voice's left and right signals, [2][n_voices][block_size], which the fold kernels mix
-// as they mix a Pan2 chain's two planes.  A launch of n blocks is n such pairs of kernels in stream order: the reverb's
+// as they mix a Pan2 chain's two planes.  (l | r) >> Galactic (the stage names both of its inputs): the chain before the
+// reverb is that ordinary bank with two connected outputs (l, r) -- knh_bank_connect_outputs' machinery and signature -- the
+// staging buffer is its two planes, [2][n_voices][block_size], and the reverb kernel's stereo-input variant reads the left
+// plane on its left side and the right plane on its right; everything else is the same.
+// A launch of n blocks is n such pairs of kernels in stream order: the reverb's
 // parameters take effect at a block boundary (at the next `process`, galactic.rs:172-201), so a call addressed to block b of
 // the launch is applied on the host between the kernels of block b - 1 and b.  Included by bank.hip only.
 //
@@ -50,7 +54,8 @@ struct GalacticBank final : knh_bank {
   F overallscale = 0;
   struct Call { uint32_t voice, param; double f; };
   std::vector<std::vector<Call>> future;  // calls addressed to later blocks of the next launch
-  F* d_stage = nullptr;    // [nv][block]
+  bool stereo_in = false;  // (l | r) >> Galactic: the inner bank has two connected outputs, the staging buffer two planes
+  F* d_stage = nullptr;    // [nv][block]; stereo_in: [2][nv][block]
   F* d_gvoices = nullptr;  // [2][nv][block]
   F* d_rings = nullptr;
   knh_dev::GalParams<F>* d_params = nullptr;
@@ -154,14 +159,15 @@ struct GalacticBank final : knh_bank {
       overallscale = static_cast<F>(os);
     }
     const size_t ring_bytes = static_cast<size_t>(nv) * ring_stride * sizeof(F);
-    const size_t other = static_cast<size_t>(nv) * (3 * bs * sizeof(F) + sizeof(knh_dev::GalState<F>) + sizeof(knh_dev::GalParams<F>)) + (1u << 20);
+    const size_t stage_planes = stereo_in ? 2 : 1;
+    const size_t other = static_cast<size_t>(nv) * ((2 + stage_planes) * bs * sizeof(F) + sizeof(knh_dev::GalState<F>) + sizeof(knh_dev::GalParams<F>)) + (1u << 20);
     size_t free_b = 0, total_b = 0;
     KNH_HIP(hipMemGetInfo(&free_b, &total_b));
     if (ring_bytes + other > free_b) return fail(KNH_ERR_DEVICE, "Galactic: the delay rings do not fit in device memory");
     KNH_HIP(hipMalloc(&d_rings, ring_bytes));
     KNH_HIP(hipMemset(d_rings, 0, ring_bytes));  // vec![F::ZERO; len]
-    KNH_HIP(hipMalloc(&d_stage, static_cast<size_t>(nv) * bs * sizeof(F)));
-    KNH_HIP(hipMemset(d_stage, 0, static_cast<size_t>(nv) * bs * sizeof(F)));
+    KNH_HIP(hipMalloc(&d_stage, stage_planes * nv * bs * sizeof(F)));
+    KNH_HIP(hipMemset(d_stage, 0, stage_planes * nv * bs * sizeof(F)));
     KNH_HIP(hipMalloc(&d_gvoices, 2 * static_cast<size_t>(nv) * bs * sizeof(F)));
     KNH_HIP(hipMemset(d_gvoices, 0, 2 * static_cast<size_t>(nv) * bs * sizeof(F)));
     KNH_HIP(hipMalloc(&d_params, static_cast<size_t>(nv) * sizeof(knh_dev::GalParams<F>)));
@@ -339,7 +345,7 @@ struct GalacticBank final : knh_bank {
       a.block_size = static_cast<uint32_t>(block_size);
       a.frame_begin = fb;
       a.frame_end = fe;
-      KNH_HIP(launch(a, s));
+      KNH_HIP(launch(a, stereo_in, s));
       // the two planes are the two channels: the fold sees two "blocks" of one channel each (as for a Pan2 chain)
       KNH_HIP(launch_fold(desc.mix_mode != KNH_MIX_LEFT_FOLD, d_gvoices, nv, static_cast<unsigned>(block_size), fb, fe, dst + static_cast<size_t>(b) * blk, 1u,
                           static_cast<unsigned>(block_size), 2u, accumulate, s));
@@ -369,15 +375,15 @@ struct GalacticBank final : knh_bank {
     if (out_flags) *out_flags = 0;  // a reverb tail does not end with its input: the bank never reports itself done
     return KNH_OK;
   }
-  F* d_inner_mix = nullptr;  // where the inner bank's own mono mix goes (not used)
+  F* d_inner_mix = nullptr;  // where the inner bank's own mix goes (not used): one block of each of its output channels
   F* inner_mix() {
     if (!d_inner_mix) {
-      if (hipMalloc(&d_inner_mix, block_size * sizeof(F)) != hipSuccess) return nullptr;
+      if (hipMalloc(&d_inner_mix, (stereo_in ? 2 : 1) * block_size * sizeof(F)) != hipSuccess) return nullptr;
     }
     return d_inner_mix;
   }
-  static hipError_t launch(const knh_dev::GalacticArgs<float>& a, hipStream_t s) { return knh::launch_galactic_f32(a, s); }
-  static hipError_t launch(const knh_dev::GalacticArgs<double>& a, hipStream_t s) { return knh::launch_galactic_f64(a, s); }
+  static hipError_t launch(const knh_dev::GalacticArgs<float>& a, bool stereo, hipStream_t s) { return knh::launch_galactic_f32(a, stereo, s); }
+  static hipError_t launch(const knh_dev::GalacticArgs<double>& a, bool stereo, hipStream_t s) { return knh::launch_galactic_f64(a, stereo, s); }
   static hipError_t launch_fold(bool tree, const float* rows, unsigned n, unsigned len, unsigned fb, unsigned fe, float* out, unsigned ch, unsigned os, unsigned nb, bool acc, hipStream_t s) {
     return knh::launch_fold_f32(tree, rows, n, len, fb, fe, out, ch, os, nb, acc, nullptr, s, nullptr);
   }

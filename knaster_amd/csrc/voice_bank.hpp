@@ -1035,7 +1035,7 @@ struct Bank final : knh_bank {
   }
   bool can_finish = false;   // the chain has a stage that can end a voice (ALL_DONE is reported only then)
   bool pan = false;          // the chain ends in a Pan2, or has two connected outputs
-  F* stage_out = nullptr;    // set by a bank that wraps this one (galactic_bank.hpp): the voices' signals of the block go here, [n_voices][block_size]
+  F* stage_out = nullptr;    // set by a bank that wraps this one (galactic_bank.hpp): the voices' signals of the block go here, [n_voices][block_size] -- [2][n_voices][block_size], left plane then right, when two outputs are connected
   unsigned fold_planes = 1;  // channel planes of the partial rows and of the per-voice output: 2 for a Pan2 chain and for connected outputs
   hipError_t ensure_voices() {
     if (d_voices) return hipSuccess;
@@ -2151,7 +2151,8 @@ struct Bank final : knh_bank {
     if (interp) KNH_HIP(launch_interp(a, s));
     else KNH_HIP(launch_voice(a, n_waves, s));
     if (tp) KNH_HIP(hipEventRecord(tp->second, s));
-    if (stage_out && interp)  // (the interpreter's rows are the voices' signals)
+    // (the interpreter's rows are the voices' signals; one plane: a voice with two connected outputs never runs there, init)
+    if (stage_out && interp)
       KNH_HIP(hipMemcpyAsync(stage_out, d_partials, static_cast<size_t>(nv) * block_size * sizeof(F), hipMemcpyDeviceToDevice, s));
     { int r2 = resolver.kernel_enqueued(s); if (r2 != KNH_OK) return r2; }
     if (have_events && list_in_use >= 0) {

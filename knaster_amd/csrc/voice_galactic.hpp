@@ -63,7 +63,8 @@ struct GalState {
 };
 template <typename F>
 struct GalacticArgs {
-  const F* in;           // [n_voices][block_size]: the voice's mono signal (both inputs of the reverb)
+  const F* in;           // [n_voices][block_size]: the voice's mono signal (both inputs of the reverb); the stereo-input
+                         // variant: [2][n_voices][block_size], the left input's plane, then the right input's
   F* out;                // [2][n_voices][block_size]
   F* rings;              // [n_voices][ring_stride]: per voice, left rings 0..11 then right rings 0..11
   const GalParams<F>* params;
@@ -95,7 +96,9 @@ __device__ __forceinline__ double gal_dither_scale(float s) {
   return 0.0;                                   // 2^64 and beyond wrap to 0
 }
 
-template <typename F>
+// StereoIn: (l | r) >> Galactic -- the two inputs are different signals: a load, a faint-input test and a dry term per side
+// (galactic.rs:208-219, :350-357).  false: one signal on both inputs, one load and one test (what x_l == x_r makes of them).
+template <typename F, bool StereoIn>
 __global__ void __launch_bounds__(64) galactic_kernel(GalacticArgs<F> a) {
   __shared__ F hist[2][GAL_DETUNE + GAL_RUN];
   __shared__ F ser[2][GAL_RUN];
@@ -158,7 +161,14 @@ __global__ void __launch_bounds__(64) galactic_kernel(GalacticArgs<F> a) {
     F x = active ? in[n + lane] : (F)0;
     const bool faint = (double)(x < (F)0 ? -x : x) < 1.18e-23;
     const F x_l = faint ? (F)((double)fl0 * 1.18e-17) : x;
-    const F x_r = faint ? (F)((double)fr0 * 1.18e-17) : x;
+    F x_r;
+    if constexpr (StereoIn) {  // the right input's plane, its own test (galactic.rs:215-219)
+      const F xr = active ? in[(unsigned long long)a.n_voices * a.block_size + n + lane] : (F)0;
+      const bool faint_r = (double)(xr < (F)0 ? -xr : xr) < 1.18e-23;
+      x_r = faint_r ? (F)((double)fr0 * 1.18e-17) : xr;
+    } else {
+      x_r = faint ? (F)((double)fr0 * 1.18e-17) : x;
+    }
     if (active) {
       hist[0][GAL_DETUNE + lane] = x_l * attenuate;
       hist[1][GAL_DETUNE + lane] = x_r * attenuate;
@@ -292,6 +302,7 @@ __global__ void __launch_bounds__(64) galactic_kernel(GalacticArgs<F> a) {
 
 namespace knh {
 // one wavefront per voice, frames [frame_begin, frame_end) of one block (kernels_galactic.hip)
-hipError_t launch_galactic_f32(const knh_dev::GalacticArgs<float>& a, hipStream_t s);
-hipError_t launch_galactic_f64(const knh_dev::GalacticArgs<double>& a, hipStream_t s);
+// stereo_in: the variant that reads a left and a right input plane
+hipError_t launch_galactic_f32(const knh_dev::GalacticArgs<float>& a, bool stereo_in, hipStream_t s);
+hipError_t launch_galactic_f64(const knh_dev::GalacticArgs<double>& a, bool stereo_in, hipStream_t s);
 }  // namespace knh

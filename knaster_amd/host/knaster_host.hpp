@@ -98,6 +98,7 @@ struct UGenSpec {
   uint16_t precise_timing_ = 0;
   bool is_constant = false, is_env = false;
   uint16_t outputs = 1;              // UGen::Outputs (Pan2: 2)
+  uint16_t inputs = 1;               // UGen::Inputs of a node that reads signals (Galactic: 2)
   // BufferReader: the Buffer the node is constructed on (the Arc<Buffer<F>> of buffer.rs:43, kept alive by the spec)
   std::shared_ptr<const void> buffer;
   const void* buffer_samples = nullptr;
@@ -134,6 +135,17 @@ inline UGenSpec floor() { return UGenSpec(KNH_STAGE_MATH1_FLOOR, {}); }
 inline UGenSpec sqrt() { return UGenSpec(KNH_STAGE_MATH1_SQRT, {}); }
 // Pan2::new(pan) -- pan.rs:18-23: one input, two outputs; `(voice >> pan).to_graph_out()` sends them to graph outputs 0 and 1
 inline UGenSpec Pan2(double pan) { UGenSpec s(KNH_STAGE_PAN2, {pan}); s.outputs = 2; return s; }
+// Galactic::new(replace, detune, brightness, bigness, wet) -- knaster_airwindows/src/galactic.rs:145-170: two inputs, two
+// outputs.  The reference draws the states of its two dither streams from fastrand in `new`; here they are arguments
+// (integers 1 .. 2^32 - 1, KNH_STAGE_GALACTIC in knaster_hip.h).  `voice.out({0, 0}) >> g.push(Galactic(..))` puts one signal
+// on both inputs, `(l | r) >> g.push(Galactic(..))` two; `.to_graph_out()` sends its outputs to graph outputs 0 and 1.  It
+// ends the voice: nothing reads it but the graph outputs.
+inline UGenSpec Galactic(double replace, double detune, double brightness, double bigness, double wet, uint32_t fpd_l, uint32_t fpd_r) {
+  UGenSpec s(KNH_STAGE_GALACTIC, {replace, detune, brightness, bigness, wet, static_cast<double>(fpd_l), static_cast<double>(fpd_r)});
+  s.inputs = 2;
+  s.outputs = 2;
+  return s;
+}
 // noise.rs:11-22: every randomness UGen takes its seed from one process-wide counter, in construction order, so a
 // graph built in the same order makes the same noise.  WhiteNoise / PinkNoise / BrownNoise::new() -- noise.rs:33,65,133
 inline uint64_t next_randomness_seed() {
@@ -347,6 +359,7 @@ inline const char* const* stage_param_names(uint16_t kind, int* n) {
     case KNH_STAGE_BUFFER_READER: *n = 6; return rdr;
     case KNH_STAGE_PHASOR: case KNH_STAGE_RANDOM_LIN: *n = 1; return frq;
     case KNH_STAGE_PAN2: { static const char* pan[] = {"pan"}; *n = 1; return pan; }
+    case KNH_STAGE_GALACTIC: { static const char* gal[] = {"replace", "detune", "brightness", "bigness", "wet"}; *n = 5; return gal; }
     case KNH_STAGE_POLYBLEP: { static const char* pb[] = {"freq", "pulse_width", "waveform"}; *n = 3; return pb; }
     case KNH_STAGE_SAFETY_LIMITER: case KNH_STAGE_WHITE_NOISE: case KNH_STAGE_PINK_NOISE: case KNH_STAGE_BROWN_NOISE: *n = 0; return frq;
     case KNH_STAGE_MATH1_CEIL: case KNH_STAGE_MATH1_SQRT: case KNH_STAGE_MATH1_FLOOR: case KNH_STAGE_MATH1_TRUNC: case KNH_STAGE_MATH1_FRACT:
@@ -478,6 +491,23 @@ class Graph {
     }
     const UGenSpec& s = n.spec;
     if (s.is_env || s.is_constant) throw GraphError("an envelope/constant must be an operand of * + - /");
+    if (s.kind == KNH_STAGE_GALACTIC) {
+      // the reverb ends the voice (only the graph outputs read it: it is the first node met) and reads two signals of it:
+      // one signal on both inputs is the mono descriptor, two are named by `input` / `input2` (knh_stage_desc)
+      if (visited.size() != 1) throw GraphError("Galactic ends the voice: only the graph outputs read it");
+      if (!s.wrappers.empty() || s.ar_params_ || s.smooth_params_ || s.precise_timing_) throw GraphError("Galactic takes no wrappers");
+      if (n.in0 < 0 || n.in1 < 0) throw GraphError("Galactic has two inputs: `voice.out({0, 0}) >> galactic` or `(l | r) >> galactic`");
+      for (int in : {n.in0, n.in1}) {
+        const NodeRec& x = nodes_[static_cast<size_t>(in)];
+        if (x.type == NodeRec::UGEN && x.spec.kind == KNH_STAGE_INPUT)
+          throw GraphError("an input of Galactic starts at a node, not at a bank input (put the input through `* 1.0`)");
+      }
+      const uint16_t l = trace_channel(n.in0, n.in0_ch, p, visited, done);
+      const uint16_t r = trace_channel(n.in1, n.in1_ch, p, visited, done);
+      if (l == r) push_stage(p, s.kind, 0, 0, node, s.args, in_of(l));
+      else push_stage(p, s.kind, 0, 0, node, s.args, l, r);
+      return finish();
+    }
     const bool source = s.kind == KNH_STAGE_SIN_WT || s.kind == KNH_STAGE_SIN_NUMERIC || s.kind == KNH_STAGE_PHASOR || s.kind == KNH_STAGE_POLYBLEP ||
                         s.kind == KNH_STAGE_BUFFER_READER || s.kind == KNH_STAGE_WHITE_NOISE || s.kind == KNH_STAGE_PINK_NOISE ||
                         s.kind == KNH_STAGE_BROWN_NOISE || s.kind == KNH_STAGE_RANDOM_LIN;
@@ -539,22 +569,23 @@ class Graph {
       // (`(l | r).to_graph_out()`): one voice holding both subgraphs, a shared node traced once, its two outputs connected
       if (conn.size() != outputs_) throw GraphError("to_graph_out(): channel count does not match the graph outputs");
       // ... or the two channels of a two-channel BufferReader, directly or through a `* value` each
+      // (a Galactic's two outputs likewise: `pan` below is "one stage makes both graph outputs")
       bool pan = false, same_node = true, same = true;
       for (size_t c = 0; c < conn.size(); ++c) {
         if (conn[c].first < 0) throw GraphError("to_graph_out_channels(): a graph output of the voice has no signal");
         const NodeRec& x = nodes_[static_cast<size_t>(conn[c].first)];
-        pan = pan || (x.type == NodeRec::UGEN && x.spec.kind == KNH_STAGE_PAN2);
+        pan = pan || (x.type == NodeRec::UGEN && (x.spec.kind == KNH_STAGE_PAN2 || x.spec.kind == KNH_STAGE_GALACTIC));
         same_node = same_node && conn[c].first == conn[0].first;
         same = same && conn[c] == conn[0];
       }
       for (size_t c = 0; c < conn.size(); ++c) {
         const NodeRec& x = nodes_[static_cast<size_t>(conn[c].first)];
         const bool reader2 = x.type == NodeRec::UGEN && x.spec.kind == KNH_STAGE_BUFFER_READER && x.spec.outputs == 2;
-        if (pan && (conn[c].second != static_cast<int>(c) || !same_node)) throw GraphError("a Pan2's outputs go to graph outputs 0 and 1, in order");
+        if (pan && (conn[c].second != static_cast<int>(c) || !same_node)) throw GraphError("the outputs of a Pan2 or a Galactic go to graph outputs 0 and 1, in order");
         if (!pan && conn[c].second != 0 && !(reader2 && conn[c].second == 1))
           throw GraphError("to_graph_out(): the node has no such output channel (a two-channel BufferReader has channels 0 and 1, every other node one signal)");
       }
-      if (pan && outputs_ != 2) throw GraphError("a Pan2 voice needs a stereo graph");
+      if (pan && outputs_ != 2) throw GraphError("a voice that ends in Pan2 or Galactic needs a stereo graph");
       if (pan) same = true;  // (one stage makes both graph outputs)
       Voice v;
       std::map<int, uint16_t> done;
@@ -727,6 +758,14 @@ class GraphEdit {
   Sig<F> connect(const Sig<F>& src, const Sig<F>& sink) {
     NodeRec& n = graph_->nodes_[static_cast<size_t>(sink.node())];
     if (n.type != NodeRec::UGEN) throw GraphError(">>: the sink must be a pushed UGen");
+    if (n.spec.inputs == 2) {  // channel c of the source handle to input c (graph_edit.rs:1347-1417)
+      if (src.nodes().size() != 2) throw GraphError(">>: the sink has two inputs: the source handle needs two channels (`x.out({0, 0})` or `(l | r)`)");
+      n.in0 = src.nodes()[0];
+      n.in0_ch = src.channels()[0];
+      n.in1 = src.nodes()[1];
+      n.in1_ch = src.channels()[1];
+      return sink;
+    }
     n.in0 = src.node();
     return sink;
   }

@@ -15,8 +15,8 @@ from knaster_amd import _lib as L, configs
 
 def run(name, n_voices=None, launches=16, blocks=32, allow_fma=False, host_threads=0, detune=None):
     w = configs.config(name, n_voices=n_voices)
-    if detune is not None and name == "G1":  # G1 with one detune everywhere (0: no f64 phase, no sin)
-        w.ctor[3][:, 1] = detune
+    if detune is not None and name in ("G1", "G2"):  # with one detune everywhere (0: no f64 phase, no sin)
+        w.ctor[len(w.stages) - 1][:, 1] = detune
     b = knaster_amd.VoiceBank(w.stages, w.n_voices, w.sample_type, w.out_channels, L.MIX_TREE, -1, allow_fma, host_threads)
     for s, a in w.ctor.items():
         b.set_ctor_args(s, a)
@@ -24,6 +24,8 @@ def run(name, n_voices=None, launches=16, blocks=32, allow_fma=False, host_threa
     v = np.arange(w.n_voices, dtype=np.uint32)
     if w.restart:
         b.param_apply_many(v, w.restart[0], w.restart[1], L.VALUE_TRIGGER)
+    for stage, param in w.restart_more:
+        b.param_apply_many(v, stage, param, L.VALUE_TRIGGER)
     if w.delay_times is not None:
         b.param_apply_many(v, 3, 0, L.VALUE_FLOAT, w.delay_times)
     for stage, param, values in w.param_sets:  # D4: every delay stage's delay_time and feedback
@@ -46,6 +48,8 @@ def run(name, n_voices=None, launches=16, blocks=32, allow_fma=False, host_threa
                 b.param_apply_many(v, w.release[0], w.release[1], L.VALUE_TRIGGER, block_offset=i)
             elif w.restart and (step[0] + i) % 64 == 0 and step[0] + i > 0:
                 b.param_apply_many(v, w.restart[0], w.restart[1], L.VALUE_TRIGGER, block_offset=i)
+                for stage, param in w.restart_more:
+                    b.param_apply_many(v, stage, param, L.VALUE_TRIGGER, block_offset=i)
         step[0] += k
     for _ in range(3):  # untimed: first-use allocations (both of the alternating record / list buffers), the clock
         events(blocks)
@@ -76,7 +80,8 @@ def run(name, n_voices=None, launches=16, blocks=32, allow_fma=False, host_threa
             wr += n_delays * word * w.block_size
         extra = {"delay_stages": n_delays, "signature": b.debug_signature(), "form": int(b.debug_words()[2]),
                  "ring_TBps": 2 * word * n_delays * float(w.n_voices) * w.block_size * blocks * n / (kms * 1e-3) / 1e12}
-    if name == "G1":  # 24 long rings + the two short ones, one sample read and one written per frame each; the staged input; two outputs
+    if name in ("G1", "G2"):  # 24 long rings + the two short ones, one sample read and one written per frame each; the staged input; two outputs
+        # (G2's second staging plane is in algorithmic_bytes_per_voice_block already)
         word = 8 if w.sample_type else 4
         rd += (24 + 2 + 1) * word * w.block_size
         wr += (24 + 2 + 1 + 2) * word * w.block_size
@@ -221,6 +226,11 @@ if __name__ == "__main__":
         run("G1", launches=8, blocks=64)
         run("G1", launches=8, blocks=64, detune=0.0)
         run("D3", n_voices=65536)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "G2":  # the reverb with a stereo input beside G1, in turn: tools/bench_configs.py G2 [repeats]
+        for _ in range(int(sys.argv[2]) if len(sys.argv) > 2 else 3):
+            run("G1", launches=8, blocks=64)
+            run("G2", launches=8, blocks=64)
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "only":  # tools/bench_configs.py only C5 C3 C2:1024 ...
         for spec in sys.argv[2:]:
