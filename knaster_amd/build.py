@@ -20,7 +20,7 @@ SOURCES = ["kernels_pipe.hip", "kernels_single.hip", "kernels_wide.hip", "kernel
 UNITS = [("kernels_pipe.hip", "kernels_pipe_mixer.o", ["-DKNH_PIPE_PART=0"]), ("kernels_pipe.hip", "kernels_pipe_fold.o", ["-DKNH_PIPE_PART=1"]),
          ("kernels_pipe.hip", "kernels_pipe_inplace.o", ["-DKNH_PIPE_PART=2"])] + [(s, s.replace(".hip", ".o"), []) for s in SOURCES[1:]]
 HELPER = os.path.join(CSRC, "knh_jit_helper")  # the process hiprtc runs in (jit_cache.hpp): host code, links hiprtc only
-HEADERS = ["jit_cache.hpp", "stage_table.hpp", "bank_base.hpp", "voice_bank.hpp", "resident_call.hpp", "event_resolver.hpp", "chain_signature.hpp", "voice_stages.hpp", "voice_chain.hpp", "voice_pipe.hpp", "voice_frame.hpp", "kernel_registry.hpp", "jit.hpp", "host_shards.hpp", "shard_workers.hpp", "rank_bank.hpp", "galactic_bank.hpp", "voice_galactic.hpp", os.path.join("..", "..", "include", "knaster_hip.h"),
+HEADERS = ["jit_cache.hpp", "stage_table.hpp", "bank_base.hpp", "kernel_form.hpp", "voice_bank.hpp", "resident_call.hpp", "event_resolver.hpp", "chain_signature.hpp", "voice_stages.hpp", "voice_chain.hpp", "voice_pipe.hpp", "voice_frame.hpp", "kernel_registry.hpp", "jit.hpp", "host_shards.hpp", "shard_workers.hpp", "rank_bank.hpp", "galactic_bank.hpp", "voice_galactic.hpp", os.path.join("..", "..", "include", "knaster_hip.h"),
            os.path.join("..", "build.py")]
 FLAGS = [
     "--offload-arch=gfx950",

@@ -30,6 +30,7 @@
 
 #include "../../include/knaster_hip.h"
 #include "jit.hpp"
+#include "kernel_form.hpp"
 #include "kernel_registry.hpp"
 
 using knh_dev::Event;
@@ -44,82 +45,11 @@ using knh_dev::VoiceKernelArgs;
 
 namespace {
 
-// The pre-built kernel forms of a bank: at creation, and again when knh_bank_connect_outputs changes the voice's signature.
 template <typename F>
-void choose_forms(Bank<F>* b, const knh::KernelEntry* entry, const std::string& sig) {
-  const knh_bank_desc& d = b->desc;
-  b->entry = entry;
-  b->signature = sig;
-  b->pipe = nullptr;
-  b->pipe_pair = false;
-  b->wide = nullptr;
-  b->wide_waves = 0;
-  {  // KNH_PIPELINE=0 forces the single-wave kernel (A/B measurements); KNH_JIT=1 forces run-time fusion
-    const char* jit_env = std::getenv("KNH_JIT");
-    if (jit_env && jit_env[0] == '1') b->entry = nullptr;
-    // KNH_PIPELINE: 0 = single-wave kernel, 1 (default) or 2 = linear wave pipeline
-    const char* env = std::getenv("KNH_PIPELINE");
-    const int level = env && env[0] >= '0' && env[0] <= '2' ? env[0] - '0' : 1;
-    b->pipeline_level = level;
-    // The 64-sample-tile form with the fold in the last stage group is used where one is built (kernels.hip): measured
-    // 3 % faster than the 32-sample form over C3's note cycle, 12 % with every envelope at rest.  KNH_PIPE_BIG=0 keeps the
-    // 32-sample tiles and the mixer wavefront (A/B runs).
-    // KNH_PIPE_BIG=1: 64-sample tiles with the fold in the last stage group (round 1's form); default: 64-sample tiles, the
-    // last group in place and a mixer wavefront on the fourth SIMD.
-    const char* big_env = std::getenv("KNH_PIPE_BIG");
-    const unsigned forms = big_env && big_env[0] == '0' ? 1u : (big_env && big_env[0] == '1' ? 3u : 7u);
-    if (b->entry && level >= 1) b->pipe = knh::find_pipe(sig.c_str(), forms);
-    // Occupancy regime: the wave pipeline minimises latency when every 64-voice group can have a CU to
-    // itself (<= ~1.5 groups per CU); beyond that throughput wins and the groups are packed 4 or 8 to a
-    // workgroup (one or two wavefronts per SIMD) sharing one staged sine table.  KNH_WIDE=0/4/8 overrides.
-    // Banks of more 64-voice groups than the chip has CUs: two groups per workgroup, each with its own pipeline, sharing the
-    // staged sine table -- two wavefronts per SIMD (voice_pipe.hpp, GPW).  One round of it renders 512 groups; KNH_PAIR=0
-    // keeps the forms of round 2 (A/B runs), KNH_PAIR=1 uses it for every bank it is built for.
-    {
-      const unsigned groups = (d.n_voices + 63u) / 64u;
-      const char* penv = std::getenv("KNH_PAIR");
-      const knh::PipeEntry* pair = b->entry && level >= 1 ? knh::find_pipe(sig.c_str(), 1u << 2 /* PIPE_INPLACE */, 2) : nullptr;
-      // Measured (us per 512-frame block, profiles/r03_form_sweep.txt): C3 f32 at 320 / 512 groups 17.8 / 18.5 against 23.5 / 23.8
-      // for one group per workgroup and 25.5 / 25.8 for four whole-chain wavefronts per workgroup; from 640 groups on the latter
-      // win (26.1-27.1 up to 1 024 groups against 34.7-35.1).  f64 gains nothing from it (38.6-39.1 against 37.0-37.2: an f64
-      // wavefront alone already keeps its SIMD's f64 pipe busy).  So: f32 banks of 257-512 groups.
-      const bool want = penv ? penv[0] == '1' : (groups > 256u && groups <= 512u && d.sample_type != KNH_F64);
-      if (pair && want && !(penv && penv[0] == '0')) { b->pipe = pair; b->pipe_pair = true; }
-    }
-    b->wide = b->entry && !b->pipe_pair ? knh::find_wide(sig.c_str()) : nullptr;
-    if (b->wide) {
-      const unsigned groups = (d.n_voices + 63u) / 64u;
-      // The pipeline takes ceil(groups / 256 CUs) rounds of its one-group-per-CU time, the 4-group kernel one round of the
-      // whole chain's single-wavefront time up to 1 024 groups, the 8-group kernel one of two wavefronts per SIMD up to 2 048.
-      // Measured on C3 / C4 (us per 512-frame block, profiles/r03_form_sweep.txt): f32 pipeline 23.5 at 257-512 groups, 35 at
-      // 513-768, against 25.5-27.1 flat for four groups per workgroup and 37-40 for eight (79.6 at 4 096 groups, where sixteen
-      // take 85.6 -- their tiles are too short for the 32-sample visits the others make); f64 pipeline 39.6-40.1 at 257-512
-      // groups against 37.0-38.7 flat for four per workgroup, 68-72 for eight up to 2 048.  So: the pipeline for two rounds in
-      // f32, one in f64; four groups per workgroup up to 1 024 groups, eight beyond.
-      const unsigned pipe_max = d.sample_type == KNH_F64 ? 256u : 512u;
-      int ww = groups <= pipe_max && b->pipe ? 0 : (groups <= 1024 ? 4 : 8);
-      if (!b->pipe && groups <= 256) ww = 0;
-      // A chain with a delay (rings in HBM, moved as whole lines: voice_stages.hpp RingLines) is bound by memory, and the
-      // pipeline has one wavefront per voice group to keep requests in flight: beyond one round of it the whole-chain forms
-      // win (D3, us per block, profiles/r04_delay_forms.txt: 20 480 voices 57.8 / 51.8, 65 536 117 / 67.9 for four per
-      // workgroup, 131 072 233 / 126 / 118 for eight).  (Rounds 1-3 kept every delay chain on the pipeline: a lane per
-      // voice's 16-byte pieces ran at 2.0 TB/s in any form.)
-      if (b->pipe && sig.find_first_of("DYZ") != std::string::npos) ww = groups <= 256 ? 0 : (groups <= 1024 ? 4 : 8);
-      // Several delay stages per voice: four wavefronts per workgroup at any size -- a wavefront that shares its SIMD's
-      // registers has no room for four delays' tiles (kernels_wide.hip KNH_WIDE_RINGS)
-      if (ww == 8 && std::count_if(sig.begin(), sig.end(), [](char c) { return c == 'D' || c == 'Y' || c == 'Z'; }) > 1) ww = 4;
-      const char* wenv = std::getenv("KNH_WIDE");
-      if (wenv) ww = std::atoi(wenv);
-      if (ww == 4 || ww == 8 || ww == 16) b->wide_waves = ww;
-    }
-  }
-}
-
-template <typename F>
-knh_bank* make_bank(const knh_bank_desc& d, const knh::KernelEntry* entry, const std::string& sig) {
+knh_bank* make_bank(const knh_bank_desc& d, const std::string& sig) {
   std::unique_ptr<Bank<F>> b(new Bank<F>());
   b->desc = d;
-  choose_forms(b.get(), entry, sig);
+  b->signature = sig;  // (which kernel form runs it is decided at knh_bank_init: kernel_form.hpp)
   b->nv = d.n_voices;
   int slot = 0, pbase = 0;
   for (uint32_t i = 0; i < d.n_stages; ++i) {
@@ -153,7 +83,7 @@ namespace {
 // K host threads: the bank is cut into K voice ranges of whole 64-voice groups (fewer when there are fewer groups).
 // devices (or null): range k lives on devices[k] (knh_bank_create_multi_device); host_threads == the number of devices then
 template <typename F>
-knh_bank* make_sharded(const knh_bank_desc& d, const knh::KernelEntry* entry, const std::string& sig, uint32_t host_threads,
+knh_bank* make_sharded(const knh_bank_desc& d, const std::string& sig, uint32_t host_threads,
                        const int32_t* devices = nullptr) {
   const uint32_t groups = (d.n_voices + 63u) / 64u;
   const uint32_t k = std::min(host_threads, groups);
@@ -170,7 +100,7 @@ knh_bank* make_sharded(const knh_bank_desc& d, const knh::KernelEntry* entry, co
       b->shard_device.push_back(dk.device);
     }
     b->base.push_back(v);
-    b->shard.emplace_back(make_bank<F>(dk, entry, sig));
+    b->shard.emplace_back(make_bank<F>(dk, sig));
   }
   b->base.push_back(d.n_voices);
   b->stages = b->shard[0]->stages;
@@ -183,7 +113,7 @@ knh_bank* make_sharded(const knh_bank_desc& d, const knh::KernelEntry* entry, co
 
 namespace {
 template <typename F>
-knh_bank* make_rank_bank(const knh_bank_desc& d, const knh::KernelEntry* entry, const std::string& sig, uint32_t rank, uint32_t world,
+knh_bank* make_rank_bank(const knh_bank_desc& d, const std::string& sig, uint32_t rank, uint32_t world,
                                 const uint8_t* comm_id, knh_reduce_fn reduce, void* user) {
   std::unique_ptr<RankBank<F>> b(new RankBank<F>());
   b->desc = d;
@@ -202,7 +132,7 @@ knh_bank* make_rank_bank(const knh_bank_desc& d, const knh::KernelEntry* entry, 
   dl.n_voices = count ? count : 1;
   const char* env = std::getenv("KNH_HOST_THREADS");
   const long k = env ? std::strtol(env, nullptr, 10) : 0;
-  std::unique_ptr<knh_bank> proto(k >= 2 && k <= 64 && dl.n_voices > 64 ? make_sharded<F>(dl, entry, sig, static_cast<uint32_t>(k)) : make_bank<F>(dl, entry, sig));
+  std::unique_ptr<knh_bank> proto(k >= 2 && k <= 64 && dl.n_voices > 64 ? make_sharded<F>(dl, sig, static_cast<uint32_t>(k)) : make_bank<F>(dl, sig));
   b->stages = proto->stages;
   b->n_slots = proto->n_slots;
   b->n_params_total = proto->n_params_total;
@@ -226,7 +156,7 @@ knh_bank* make_galactic(const knh_bank_desc& d, const std::string& inner_sig) {
   const bool stereo_in = galactic_inputs(d.stages, d.n_stages, outs);
   di.out_channels = stereo_in ? 2 : 1;
   di.mix_mode = KNH_MIX_TREE;
-  b->inner.reset(static_cast<Bank<F>*>(make_bank<F>(di, knh::find_kernel(inner_sig.c_str()), inner_sig)));
+  b->inner.reset(static_cast<Bank<F>*>(make_bank<F>(di, inner_sig)));
   if (stereo_in) b->inner->set_outputs(true, outs[0], outs[1], inner_sig);
   b->stereo_in = stereo_in;
   b->desc = d;
@@ -370,8 +300,7 @@ int32_t knh_bank_create_multi_device(const knh_bank_desc* desc, const int32_t* d
     (void)hipGetDeviceCount(&visible);
     for (uint32_t k = 0; k < n_devices; ++k)
       if (devices[k] < 0 || devices[k] >= std::max(visible, 1)) { g_create_error = "devices: ordinal out of range"; return KNH_ERR_INVALID_ARGUMENT; }
-    const knh::KernelEntry* entry = knh::find_kernel(sig.c_str());
-    *out_bank = desc->sample_type == KNH_F64 ? make_sharded<double>(*desc, entry, sig, n_devices, devices) : make_sharded<float>(*desc, entry, sig, n_devices, devices);
+    *out_bank = desc->sample_type == KNH_F64 ? make_sharded<double>(*desc, sig, n_devices, devices) : make_sharded<float>(*desc, sig, n_devices, devices);
     return KNH_OK;
   });
 }
@@ -394,9 +323,8 @@ static int32_t create_rank_bank(const knh_bank_desc* desc, uint32_t rank, uint32
     if (world == 0 || rank >= world) { g_create_error = "rank must be below world"; return KNH_ERR_INVALID_ARGUMENT; }
     if (world > 1 && !comm_id && !reduce) { g_create_error = "more than one rank needs a communicator id (knh_comm_unique_id) or a reduce function"; return KNH_ERR_INVALID_ARGUMENT; }
     if (desc->mix_mode != KNH_MIX_TREE) { g_create_error = "a bank sharded over several GPUs mixes with KNH_MIX_TREE (the sum over GPUs re-associates)"; return KNH_ERR_INVALID_ARGUMENT; }
-    const knh::KernelEntry* entry = knh::find_kernel(sig.c_str());
-    *out_bank = desc->sample_type == KNH_F64 ? make_rank_bank<double>(*desc, entry, sig, rank, world, comm_id, reduce, user)
-                                            : make_rank_bank<float>(*desc, entry, sig, rank, world, comm_id, reduce, user);
+    *out_bank = desc->sample_type == KNH_F64 ? make_rank_bank<double>(*desc, sig, rank, world, comm_id, reduce, user)
+                                            : make_rank_bank<float>(*desc, sig, rank, world, comm_id, reduce, user);
     return KNH_OK;
   });
 }
@@ -423,13 +351,11 @@ static int32_t create_bank(const knh_bank_desc* desc, uint32_t host_threads, knh
       *out_bank = desc->sample_type == KNH_F64 ? make_galactic<double>(*desc, sig) : make_galactic<float>(*desc, sig);
       return KNH_OK;
     }
-    // a chain without a pre-built kernel is fused at knh_bank_init time (hiprtc); entry == nullptr marks it
-    const knh::KernelEntry* entry = knh::find_kernel(sig.c_str());
     // the reference's exact mix order (KNH_MIX_LEFT_FOLD) and banks of a single voice group keep one range
     if (host_threads >= 2 && desc->mix_mode == KNH_MIX_TREE && desc->n_voices > 64)
-      *out_bank = desc->sample_type == KNH_F64 ? make_sharded<double>(*desc, entry, sig, host_threads) : make_sharded<float>(*desc, entry, sig, host_threads);
+      *out_bank = desc->sample_type == KNH_F64 ? make_sharded<double>(*desc, sig, host_threads) : make_sharded<float>(*desc, sig, host_threads);
     else
-      *out_bank = desc->sample_type == KNH_F64 ? make_bank<double>(*desc, entry, sig) : make_bank<float>(*desc, entry, sig);
+      *out_bank = desc->sample_type == KNH_F64 ? make_bank<double>(*desc, sig) : make_bank<float>(*desc, sig);
     return KNH_OK;
   });
 }

@@ -1,44 +1,40 @@
 // voice_bank.hpp -- Bank<F>: one voice range on one GPU.  The host keeps a shadow of every *parameter-derived* quantity
 // (never of audio-evolving state) and turns each UGen::param_apply into device state patches: all transcendental work (tan /
 // pow / sqrt / exp for filter coefficients, the f64 phase-increment product) happens here with the same libm the reference's
-// std-backed num-traits would call; WrPreciseTiming's queues, WrSmoothParams' ramps, the per-launch event lists, the kernel
-// choice and the launch itself.  Two protocols with the device live behind types of their own, each owning its resources:
-// the per-block call on a resident launch (resident_call.hpp) and the change queues the device resolves (event_resolver.hpp).
+// std-backed num-traits would call; WrPreciseTiming's queues, WrSmoothParams' ramps, the per-launch event lists and the
+// launch itself.  Which kernel form the bank runs in is decided in one place, kernel_form.hpp: init asks it for the
+// candidates, builds what the first that stands needs and keeps it as one value (`form`); nothing else looks further.  Two
+// protocols with the device live behind types of their own, each owning its resources: the per-block call on a resident
+// launch (resident_call.hpp) and the change queues the device resolves (event_resolver.hpp).
 // Included by bank.hip only.
 #pragma once
 
 namespace {
 
-template <typename F> struct Bank;
-// which of the pre-built kernel forms a bank of this signature takes (bank.hip)
-template <typename F> void choose_forms(Bank<F>* b, const knh::KernelEntry* entry, const std::string& sig);
-
 template <typename F>
 struct Bank final : knh_bank {
   typedef typename knh_dev::WordOf<F>::type W;
-  const knh::KernelEntry* entry = nullptr;
-  const knh::PipeEntry* pipe = nullptr;  // wave-specialised variant, used when built for this chain
-  bool pipe_pair = false;                // ... in its two-groups-per-workgroup form (banks of more groups than CUs)
-  const knh::WideEntry* wide = nullptr;  // 4/8 voice groups per workgroup, for banks larger than the chip's SIMD count
-  int wide_waves = 0;                    // 0 = not used, else 4 or 8
-  // a graph-shaped voice of SinWt oscillators and arithmetic run by the frame-parallel interpreter (kernels_interp.hip)
-  bool interp = false;
+  // The kernel form the bank's launches take, chosen at init (kernel_form.hpp): its kind and variant, how it is launched --
+  // a pre-built kernel's launch function, or the kernel hiprtc built at init -- and what the launch path asks of it.
+  struct ChosenForm {
+    knh::FormCandidate is;
+    knh::FormFacts facts;
+    knh::VoiceLaunchFn<F> fn = nullptr;   // the pre-built forms
+    const knh::JitKernel* jit = nullptr;  // the fused forms, and the lane-per-frame kernel built at init (voice_frame.hpp, jit_frame_kernel)
+  } form;
+  // a voice of SinWt oscillators and arithmetic run a lane per frame: its program (the interpreter, kernels_interp.hip, reads it
+  // on the device; the kernel built at init is written from it), the SinWt stages' slots, the built kernel's voices per workgroup
   std::vector<knh_dev::InterpOp> h_prog;
   knh_dev::InterpOp* d_prog = nullptr;
   unsigned interp_sigs = 0, interp_out = 0;
-  // ... or, by default, as one frame-parallel kernel hiprtc builds from the stages written out as straight-line code
-  // (voice_frame.hpp, jit_frame_kernel); KNH_FRAME_JIT=0 keeps the interpreter
-  const knh::JitKernel* frame_jit = nullptr;
   uint32_t* d_sin_slots = nullptr;
   unsigned frame_vpw = 1, n_sin = 0;
   uint64_t env_ranks = 0;  // VoiceKernelArgs::env_ranks (graph-shaped voices with several envelope stages)
-  const knh::JitKernel* jit = nullptr;   // run-time fused kernel (hiprtc) for chains without a pre-built one
-  int pipeline_level = 1;                // KNH_PIPELINE
   std::string signature;
   const char* debug_signature() const override { return signature.c_str(); }
   void set_outputs(bool conn, uint32_t left, uint32_t right, const std::string& sig) override {
     knh_bank::set_outputs(conn, left, right, sig);
-    choose_forms(this, knh::find_kernel(sig.c_str()), sig);  // (no pre-built kernel has two connected outputs: such a voice is fused at init)
+    signature = sig;  // (no pre-built kernel has two connected outputs: such a voice is fused at init)
   }
   uint32_t nv = 0;
   long stride = 0;
@@ -103,12 +99,9 @@ struct Bank final : knh_bank {
     pending.swap(out);
     pending_ranges.clear();
   }
-  // the bank's resident kernel form walks range events: the pipelined kernels (voice_pipe.hpp), not the one-wavefront kernel
-  bool res_ranges_ok() const { return jit ? jit_pipe : pipe != nullptr; }
-  // ... and so does an ORDINARY launch of one (launch_voice: the fused kernel first, then the many-wavefront forms, then the
-  // pipeline): its range events travel in the kernel arguments.  KNH_RANGE_LAUNCHES=0, read when the bank is made: every
-  // launch takes per-voice lists, as before (A/B runs, tests).
-  bool launch_ranges_ok() const { return !interp && (jit ? jit_pipe : (wide_waves == 0 && pipe != nullptr)); }
+  // The pipelined kernels (voice_pipe.hpp) walk range events, resident or launched (form.facts.walks_ranges): an ordinary
+  // launch's range events travel in the kernel arguments.  KNH_RANGE_LAUNCHES=0, read when the bank is made: every launch
+  // takes per-voice lists, as before (A/B runs, tests).
   bool range_launches = [] { const char* e = std::getenv("KNH_RANGE_LAUNCHES"); return !(e && e[0] == '0'); }();
   uint32_t launch_n_ranges = 0;      // the launch upload_events has just prepared takes this many range events (0: per-voice lists, or none)
   Event launch_range_recs[2 * knh_dev::LAUNCH_RANGES_MAX];
@@ -274,25 +267,12 @@ struct Bank final : knh_bank {
   ResidentCall<F> resident;
   void resident_stats(uint64_t* calls, uint64_t* launches) override { resident.stats(calls, launches); }
   void resident_trace(uint64_t* five) override { resident.trace(five); }
-  bool jit_pipe = false;  // the run-time fused kernel is a pipeline (mixer form, short tiles), not a one-wavefront kernel
   bool res_possible() const {
-    // Kernel forms in which every workgroup can be resident at once and the fold server can take the rows: the pipelined forms
-    // with a mixer wavefront and one voice group per workgroup, and the one-wavefront kernel (pre-built or fused at run time);
-    // up to 256 voice groups (the server folds 8 x 32 rows), tree mix, no bank inputs (their upload rides in a stream).
-    if (interp || uses_input || desc.mix_mode != KNH_MIX_TREE) return false;
-    if ((nv + 63u) / 64u > 256u || block_size > 4096) return false;
-    if (wide_waves != 0) return false;
-    if (jit) return true;
-    if (pipe) return !pipe_pair && pipe->form != 1 /* PIPE_FOLD: no mixer wavefront */ && pipe->gpw == 1;
-    return entry != nullptr;
-  }
-  // frames per tile of the bank's pipelined kernel form (voice_pipe.hpp, PipeTile: the forms with the long tiles, and the
-  // Fan pipelines, 64 -- f64: 32; the mixer form 32 / 16)
-  uint32_t res_tile_frames() const {
-    if (jit && jit_pipe) return sizeof(F) == 8 ? 16u : 32u;  // (jit.hip fuses pipelines in the mixer form with the short tiles)
-    if (jit || !pipe) return 64u;                             // the one-wavefront kernel hands its rows over in 64-frame tiles
-    const bool big = pipe->long_tiles != 0;
-    return sizeof(F) == 8 ? (big ? 32u : 16u) : (big ? 64u : 32u);
+    // Kernel forms in which every workgroup can be resident at once and the fold server can take the rows (kernel_form.hpp
+    // form_facts: the pipelined forms with a mixer wavefront and one voice group per workgroup, and the one-wavefront kernel,
+    // pre-built or fused at run time); up to 256 voice groups (the server folds 8 x 32 rows), tree mix, no bank inputs (their
+    // upload rides in a stream).
+    return form.facts.can_be_resident && !uses_input && desc.mix_mode == KNH_MIX_TREE && (nv + 63u) / 64u <= 256u && block_size <= 4096;
   }
   void fill_launch_args(VoiceKernelArgs<F>& a, uint32_t n_blocks, uint32_t fb, uint32_t fe) {
     a.state = d_state;
@@ -767,111 +747,101 @@ struct Bank final : knh_bank {
     KNH_HIP(hipSetDevice(device));
     // The pool's channel count is known now.  A reader's second output needs a second channel (in the reference it reads the
     // neighbouring sample and runs off the end); a mono reader on a pool of two-channel Buffers plays channel 0 of the
-    // interleaved frames (BufferReader<F, U1> on a stereo Buffer: index * num_channels + 0) -- a stage of its own
-    // (knh_dev::BufferReaderCh0, 'C' for 'F'), so the voice is fused now whatever was pre-built for its mono form.
+    // interleaved frames (BufferReader<F, U1> on a stereo Buffer: index * num_channels + 0) -- a stage of its own, 'C' for 'F'
+    // in the plan's signature below.
     for (const StageInfo& S : stages)
       if (S.ch1() && pool_channels() == 1) return fail(KNH_ERR_INVALID_ARGUMENT, "a KNH_STAGE_FLAG_READER_CH1 stage needs a pool of two-channel Buffers (knh_bank_add_buffer_interleaved with n_channels = 2)");
-    // (a refused init changes nothing: the signature and the pre-built forms it drops come back unless init gets to its end)
-    struct KeepForms {
-      Bank* b;
-      std::string signature;
-      const knh::KernelEntry* entry;
-      const knh::PipeEntry* pipe;
-      bool pipe_pair;
-      const knh::WideEntry* wide;
-      int wide_waves;
-      bool armed;
-      ~KeepForms() {
-        if (!armed) return;
-        b->signature.swap(signature);
-        b->entry = entry; b->pipe = pipe; b->pipe_pair = pipe_pair; b->wide = wide; b->wide_waves = wide_waves;
-      }
-    } keep{this, signature, entry, pipe, pipe_pair, wide, wide_waves, false};
-    if (pool_channels() == 2 && signature.find('F') != std::string::npos) {
-      keep.armed = true;
-      std::replace(signature.begin(), signature.end(), 'F', 'C');
-      entry = nullptr; pipe = nullptr; pipe_pair = false; wide = nullptr; wide_waves = 0;
-    }
-    // Chains without a pre-built pipelined kernel are fused now (hiprtc).  Up to two voice groups per CU the
-    // pipelined form wins by a wide margin, so the chain is cut into at most three stage groups of similar cost
-    // (estimated instructions per sample) and instantiated as voice_pipe_kernel; KNH_JIT_PIPE=0 keeps the
-    // single-wave form.
-    // The 64-sample-tile pipeline only where the block is made of whole tiles: a partial tile runs sample by sample,
-    // and a 32- or 96-frame block would be half partial tiles (its 32-sample form has none).
-    if (pipe && !pipe_pair && pipe->form != 0 && bs % (sizeof(F) == 4 ? 64u : 32u) != 0) pipe = knh::find_pipe(signature.c_str(), 1u);
-    const unsigned n_groups = (nv + 63u) / 64u;
-    {  // Voices made of SinWt oscillators and arithmetic alone (graphs, or chains without a pre-built kernel) are not run a
-       // lane per voice at all: every stage is a pure function of the frame index, so a lane per FRAME it is (voice_frame.hpp)
-       // -- measured 10-27 times the lane-per-voice form from one voice to 65 536 (tools/bench_fm_cascade.py), and the only
-       // form that takes the reference's 1 531-stage cascade.  KNH_INTERP=0: never (the lane-per-voice form, A/B runs).
-      const char* ie = std::getenv("KNH_INTERP");
-      // (a voice with two connected outputs is not one of them: the frame kernels hand out one signal; it is fused like any graph)
-      bool can = !entry && bs <= 1024 && stages.size() <= 4096 && !connected;
-      for (const StageInfo& S : stages) can = can && frame_eligible(S.kind, S.flags, S.dcpb, S.ar_param);
-      if (can && !(ie && ie[0] == '0')) {
-        if (!parse_frame_program(signature, stages, &h_prog, &interp_sigs, &interp_out)) return fail(KNH_ERR_UNSUPPORTED_CHAIN, "interpreter: malformed graph signature");
-        if (knh::interp_lds_bytes(static_cast<unsigned>(h_prog.size()), static_cast<unsigned>(n_slots), interp_sigs, static_cast<unsigned>(bs), sizeof(F) == 8) <= 158u * 1024u)
-          interp = true;
-        const char* fj = std::getenv("KNH_FRAME_JIT");
-        if (interp && !(fj && fj[0] == '0')) {
+    // The kernel form (kernel_form.hpp): what the decision reads, the candidates in its order, the first that stands.  The
+    // plan's signature becomes the bank's when init gets to its end: a refused init changes nothing.
+    const bool f64 = sizeof(F) == 8, fma = desc.allow_fma != 0;
+    knh::FormInputs in;
+    in.signature = signature;
+    in.n_voices = nv;
+    in.f64 = f64;
+    in.block_size = bs;
+    in.connected = connected;
+    in.n_stages = stages.size();
+    in.frame_eligible = std::all_of(stages.begin(), stages.end(), [](const StageInfo& S) { return frame_eligible(S.kind, S.flags, S.dcpb, S.ar_param); });
+    in.dag = signature_is_dag(signature);
+    in.n_delays = static_cast<unsigned>(std::count_if(signature.begin(), signature.end(), [](char c) { return c == 'D' || c == 'Y' || c == 'Z'; }));
+    in.two_channel_pool = pool_channels() == 2;
+    const char* const prebuilt_key = signature.c_str();
+    in.prebuilt.one_wave = knh::find_kernel(prebuilt_key) != nullptr;
+    for (int l = 0; l < 3; ++l)
+      if (const knh::PipeEntry* p = knh::find_pipe(prebuilt_key, 1u << l)) in.prebuilt.pipe[l] = {true, p->long_tiles != 0};
+    in.prebuilt.pair = knh::find_pipe(prebuilt_key, 1u << 2 /* PIPE_INPLACE */, 2) != nullptr;
+    in.prebuilt.wide = knh::find_wide(prebuilt_key) != nullptr;
+    const knh::FormPlan plan = knh::plan_forms(in, knh::form_switches_from_env());
+    const std::string& sig = plan.signature;
+    env_ranks = envelope_task_ranks(sig, stages, connected ? out_stage : nullptr);
+    bool chosen = false, frame_asked = false, frame_fits = false;
+    for (int k = 0; k < plan.n && !chosen; ++k) {
+      ChosenForm f;
+      f.is = plan.candidate[k];
+      f.facts = knh::form_facts(f.is, f64);
+      std::string why;
+      switch (f.is.kind) {
+        case KNH_DEBUG_FORM_FRAME_JIT:
+        case KNH_DEBUG_FORM_FRAME_INTERP: {
+          if (!frame_asked) {  // the parsed program says whether a voice fits the LDS a lane per frame
+            frame_asked = true;
+            if (!parse_frame_program(sig, stages, &h_prog, &interp_sigs, &interp_out)) return fail(KNH_ERR_UNSUPPORTED_CHAIN, "interpreter: malformed graph signature");
+            frame_fits = knh::interp_lds_bytes(static_cast<unsigned>(h_prog.size()), static_cast<unsigned>(n_slots), interp_sigs, static_cast<unsigned>(bs), f64) <= 158u * 1024u;
+          }
+          if (!frame_fits) continue;
+          if (f.is.kind == KNH_DEBUG_FORM_FRAME_INTERP) break;
           const unsigned tpv = ((static_cast<unsigned>(bs) + 63u) / 64u) * 64u;
           const size_t nwp = (static_cast<size_t>(n_slots) + 3u) & ~size_t(3);
           // voices per workgroup: as many as keep every CU busy, fit 1 024 threads and (beside the 64 KiB table) the LDS
           unsigned vpw = std::max(1u, nv / 256u);
           vpw = std::min(vpw, 1024u / tpv);
           while (vpw > 1u && 65536u + vpw * nwp * sizeof(W) > 156u * 1024u) --vpw;
-          if (65536u + vpw * nwp * sizeof(W) <= 156u * 1024u) {
-            std::vector<knh::FrameOp> fops(h_prog.size());
-            for (size_t k = 0; k < h_prog.size(); ++k) fops[k] = knh::FrameOp{h_prog[k].kind, h_prog[k].a, h_prog[k].b, h_prog[k].o, h_prog[k].slot};
-            std::string why;
-            frame_jit = knh::jit_frame_kernel(fops.data(), static_cast<unsigned>(fops.size()), interp_sigs, interp_out, static_cast<unsigned>(n_slots), vpw, tpv,
-                                              sizeof(F) == 8, &why);
-            if (frame_jit) frame_vpw = vpw;
-            else warnings.push_back("frame-parallel kernel not built (" + why.substr(0, 300) + "): the interpreter runs the voice");
+          if (65536u + vpw * nwp * sizeof(W) > 156u * 1024u) continue;
+          std::vector<knh::FrameOp> fops(h_prog.size());
+          for (size_t i = 0; i < h_prog.size(); ++i) fops[i] = knh::FrameOp{h_prog[i].kind, h_prog[i].a, h_prog[i].b, h_prog[i].o, h_prog[i].slot};
+          f.jit = knh::jit_frame_kernel(fops.data(), static_cast<unsigned>(fops.size()), interp_sigs, interp_out, static_cast<unsigned>(n_slots), vpw, tpv, f64, &why);
+          if (!f.jit) {
+            warnings.push_back("frame-parallel kernel not built (" + why.substr(0, 300) + "): the interpreter runs the voice");
+            continue;
           }
-        }
+          frame_vpw = vpw;
+        } break;
+        case KNH_DEBUG_FORM_PIPELINE_FUSED: {
+          // the chain is cut into at most three stage groups of similar cost (estimated instructions per sample) and
+          // instantiated as voice_pipe_kernel
+          unsigned cuts[2];
+          const unsigned n_cuts = partition_chain(sig, cuts);
+          f.jit = knh::jit_pipe_kernel(sig.c_str(), cuts, n_cuts, f64, fma, &why);
+          if (!f.jit) {
+            // A chain of several delay stages for which the pipeline has no room is not refused: the next candidate takes it.
+            const bool crashed = why.rfind("JIT_CRASH: ", 0) == 0;
+            if (crashed || in.n_delays <= 1 || k + 1 == plan.n) return fail(crashed ? KNH_ERR_INTERNAL : KNH_ERR_UNSUPPORTED_CHAIN, "run-time fusion of chain '" + sig + "' (pipelined) failed: " + why);
+            warnings.push_back("pipelined kernel not built (" + why.substr(0, 300) + "): the whole-chain form runs the voice");
+            continue;
+          }
+        } break;
+        case KNH_DEBUG_FORM_WHOLE_CHAIN_FUSED:
+          f.jit = knh::jit_voice_kernel(sig.c_str(), f64, fma, &why, f.is.waves);
+          if (!f.jit) return fail(why.rfind("JIT_CRASH: ", 0) == 0 ? KNH_ERR_INTERNAL : KNH_ERR_UNSUPPORTED_CHAIN, "run-time fusion of chain '" + sig + "' failed: " + why);
+          break;
+        case KNH_DEBUG_FORM_PIPELINE: {
+          const knh::PipeEntry* p = knh::find_pipe(prebuilt_key, 1u << f.is.pipe_layout, f.is.pair ? 2 : 1);
+          f.fn = launch_fn(p->f32, p->f64);
+        } break;
+        case KNH_DEBUG_FORM_MANY_WAVE: {
+          const knh::WideEntry* w = knh::find_wide(prebuilt_key);
+          f.fn = f.is.waves == 4 ? launch_fn(w->f32_w4, w->f64_w4) : f.is.waves == 8 ? launch_fn(w->f32_w8, w->f64_w8) : launch_fn(w->f32_w16, w->f64_w16);
+        } break;
+        default: {  // KNH_DEBUG_FORM_WHOLE_CHAIN
+          const knh::KernelEntry* e = knh::find_kernel(prebuilt_key);
+          f.fn = launch_fn(e->f32, e->f64);
+        } break;
       }
+      form = f;
+      chosen = true;
     }
-    env_ranks = envelope_task_ranks(signature, stages, connected ? out_stage : nullptr);
-    const char* jp = std::getenv("KNH_JIT_PIPE");
-    // (a single voice group with a pre-built kernel stays on it: nothing to gain, and no compile at init)
-    // (a voice that is a graph, not a chain, runs in the single-wave form: the pipeline's edges carry one signal)
-    // (the pipeline covers two rounds of 256 voice groups in f32; one in f64 and for chains with a delay, whose rings want as
-    // many wavefronts as there are to keep requests in flight: the thresholds of the pre-built chains, bank.hip make_bank)
-    // (a chain with a pre-built one-wavefront kernel but no pre-built wide form keeps the fused pipeline up to 512 groups)
-    const unsigned jit_pipe_max = !entry && (sizeof(F) == 8 || signature.find_first_of("DYZ") != std::string::npos) ? 256u : 512u;
-    const bool pipe_jit = !interp && !pipe && wide_waves == 0 && pipeline_level >= 1 && n_groups <= jit_pipe_max && !(jp && jp[0] == '0') &&
-                          !(entry && n_groups == 1) && !signature_is_dag(signature);
-    if (pipe_jit) {
-      std::string why;
-      unsigned cuts[2];
-      const unsigned n_cuts = partition_chain(signature, cuts);
-      jit = knh::jit_pipe_kernel(signature.c_str(), cuts, n_cuts, sizeof(F) == 8, desc.allow_fma != 0, &why);
-      jit_pipe = jit != nullptr;
-      // A chain of several delay stages for which the pipeline has no room (a RingLines tile per stage group beside the
-      // table and the edges: voice_pipe.hpp's LDS sum) is not refused: it takes the whole-chain form below.
-      const bool crashed = why.rfind("JIT_CRASH: ", 0) == 0;
-      const bool several_delays = std::count_if(signature.begin(), signature.end(), [](char c) { return c == 'D' || c == 'Y' || c == 'Z'; }) > 1;
-      if (!jit && (crashed || !several_delays)) return fail(crashed ? KNH_ERR_INTERNAL : KNH_ERR_UNSUPPORTED_CHAIN, "run-time fusion of chain '" + signature + "' (pipelined) failed: " + why);
-      if (!jit) warnings.push_back("pipelined kernel not built (" + why.substr(0, 300) + "): the whole-chain form runs the voice");
-    }
-    if (jit || (pipe_jit && entry)) {
-      // (fused as a pipeline, or a pre-built whole-chain kernel stands in for the pipeline that was not built)
-    } else if (!entry && !interp) {  // no pre-built kernel at all
-      std::string why;
-      // Beyond the pipeline's reach (more than 512 voice groups) a fused chain runs as whole-chain wavefronts sharing a staged
-      // sine table, four to a workgroup (one per SIMD) up to 1 024 groups, eight beyond -- the forms of the pre-built
-      // chains (make_bank); round 3 gave every fused voice group a workgroup, and a 64 KiB table staging, of its own.
-      // A voice that is a graph keeps the one-wavefront form (its signals' registers leave no room to share a SIMD).
-      // KNH_JIT_WAVES=1|4|8|16 overrides (tests: the filter's steps at one, two and four wavefronts per SIMD).
-      unsigned jw = !signature_is_dag(signature) && n_groups > jit_pipe_max ? (n_groups <= 1024 ? 4u : 8u) : 1u;
-      // (several delay stages: four per workgroup at any size, as the pre-built chains -- at eight, four delays' tiles spill)
-      if (jw == 8u && std::count_if(signature.begin(), signature.end(), [](char c) { return c == 'D' || c == 'Y' || c == 'Z'; }) > 1) jw = 4u;
-      if (const char* e = std::getenv("KNH_JIT_WAVES")) { const int v = std::atoi(e); if ((v == 1 || v == 4 || v == 8 || v == 16) && !signature_is_dag(signature)) jw = static_cast<unsigned>(v); }
-      if (sizeof(F) == 8 && jw == 16) jw = 8;  // (sixteen f64 tiles do not fit beside the table)
-      jit = knh::jit_voice_kernel(signature.c_str(), sizeof(F) == 8, desc.allow_fma != 0, &why, jw);
-      if (!jit) return fail(why.rfind("JIT_CRASH: ", 0) == 0 ? KNH_ERR_INTERNAL : KNH_ERR_UNSUPPORTED_CHAIN, "run-time fusion of chain '" + signature + "' failed: " + why);
-    }
+    if (!chosen) return fail(KNH_ERR_INTERNAL, "no kernel form stands for chain '" + sig + "'");
+    const bool rows_per_voice = form.facts.rows_per_voice;
     sample_rate = sr;
     block_size = bs;
     stride = (static_cast<long>(nv) + 63) / 64 * 64;
@@ -936,8 +906,8 @@ struct Bank final : knh_bank {
       KNH_HIP(hipMalloc(&d_seg_table, seg_rows.size() * sizeof(double)));
       KNH_HIP(hipMemcpy(d_seg_table, seg_rows.data(), seg_rows.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    const size_t n_waves = interp ? nv : (nv + 63) / 64;  // rows the fold kernels take: one per wavefront, or (interpreter) one per voice
-    if (interp) {
+    const size_t n_waves = rows_per_voice ? nv : (nv + 63) / 64;  // rows the fold kernels take: one per wavefront, or (a lane per frame) one per voice
+    if (rows_per_voice) {
       KNH_HIP(hipMalloc(&d_prog, h_prog.size() * sizeof(knh_dev::InterpOp)));
       KNH_HIP(hipMemcpy(d_prog, h_prog.data(), h_prog.size() * sizeof(knh_dev::InterpOp), hipMemcpyHostToDevice));
       std::vector<uint32_t> sins;
@@ -947,7 +917,7 @@ struct Bank final : knh_bank {
       KNH_HIP(hipMalloc(&d_sin_slots, std::max<size_t>(1, sins.size()) * sizeof(uint32_t)));
       if (!sins.empty()) KNH_HIP(hipMemcpy(d_sin_slots, sins.data(), sins.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
-    pan = !signature.empty() && (stages.back().kind == KNH_STAGE_PAN2 || connected);  // a Pan2 ends the chain, or two outputs are connected: every voice has a left and a right signal
+    pan = !sig.empty() && (stages.back().kind == KNH_STAGE_PAN2 || connected);  // a Pan2 ends the chain, or two outputs are connected: every voice has a left and a right signal
     fold_planes = pan ? 2u : 1u;
     KNH_HIP(hipMalloc(&d_partials, fold_planes * n_waves * bs * sizeof(F)));
     KNH_HIP(hipMalloc(&d_out, desc.out_channels * bs * sizeof(F)));
@@ -1016,7 +986,7 @@ struct Bank final : knh_bank {
       rs.fold_planes = fold_planes;
       rs.out_channels = desc.out_channels;
       rs.block_size = static_cast<uint32_t>(bs);
-      rs.tile_frames = res_tile_frames();
+      rs.tile_frames = form.facts.tile_frames;
       rs.can_finish = can_finish;
       rs.ev_start = h_ev_start2;
       rs.events = h_events2;
@@ -1029,7 +999,7 @@ struct Bank final : knh_bank {
       };
       resident.setup(rs);
     }
-    keep.armed = false;
+    signature = sig;
     initialised = true;
     return KNH_OK;
   }
@@ -2023,8 +1993,8 @@ struct Bank final : knh_bank {
                          !resolver.pending() && res_possible() && resident.enabled() && resident.ready();
     bool have_events = false;
     // (the device's resolver merges the host's per-voice lists into its own: lists it is, then)
-    const bool ranges_now = !res_now && range_launches && launch_ranges_ok() && !resolver.pending();
-    int rc = upload_events(s, &have_events, n_blocks, res_now && res_ranges_ok(), ranges_now);
+    const bool ranges_now = !res_now && range_launches && form.facts.walks_ranges && !resolver.pending();
+    int rc = upload_events(s, &have_events, n_blocks, res_now && form.facts.walks_ranges, ranges_now);
     if (rc != KNH_OK) return rc;
     if (!future.empty()) {  // calls addressed beyond this launch move up; those now due for the next
                             // block are applied right away, ahead of anything that arrives later
@@ -2066,7 +2036,8 @@ struct Bank final : knh_bank {
       return fail(KNH_ERR_INVALID_ARGUMENT, "KNH_MIX_LEFT_FOLD processes one block per call");
     if (stage_out && n_blocks > 1) return fail(KNH_ERR_INTERNAL, "a bank that feeds a following stage renders one block per launch");
     if (want_voices && !stage_out) KNH_HIP(ensure_voices());
-    const unsigned n_waves = interp ? nv : (nv + 63) / 64;
+    const bool rows_per_voice = form.facts.rows_per_voice;  // (a lane per frame: the rows are the voices' signals)
+    const unsigned n_waves = rows_per_voice ? nv : (nv + 63) / 64;
     if (n_blocks > partials_blocks) {
       KNH_HIP(hipStreamSynchronize(s));
       KNH_HIP(hipFree(d_partials));
@@ -2148,11 +2119,10 @@ struct Bank final : knh_bank {
       tp = &timing_pool[timing_used++];
       KNH_HIP(hipEventRecord(tp->first, s));
     }
-    if (interp) KNH_HIP(launch_interp(a, s));
-    else KNH_HIP(launch_voice(a, n_waves, s));
+    KNH_HIP(rows_per_voice ? launch_frames(a, s) : launch_voice(a, n_waves, s));
     if (tp) KNH_HIP(hipEventRecord(tp->second, s));
     // (the interpreter's rows are the voices' signals; one plane: a voice with two connected outputs never runs there, init)
-    if (stage_out && interp)
+    if (stage_out && rows_per_voice)
       KNH_HIP(hipMemcpyAsync(stage_out, d_partials, static_cast<size_t>(nv) * block_size * sizeof(F), hipMemcpyDeviceToDevice, s));
     { int r2 = resolver.kernel_enqueued(s); if (r2 != KNH_OK) return r2; }
     if (have_events && list_in_use >= 0) {
@@ -2175,7 +2145,7 @@ struct Bank final : knh_bank {
     const unsigned fold_channels = pan ? 1u : desc.out_channels;
     // (the interpreter's rows ARE the voices' signals: one buffer serves both mix orders and the per-voice debug output)
     if (desc.mix_mode == KNH_MIX_LEFT_FOLD)
-      KNH_HIP(launch_fold(false, interp ? d_partials : d_voices, nv, static_cast<unsigned>(block_size), fb, fe, dst, fold_channels, static_cast<unsigned>(block_size), fold_planes, accumulate, flags_next, s, hand_over ? &hd : nullptr));
+      KNH_HIP(launch_fold(false, rows_per_voice ? d_partials : d_voices, nv, static_cast<unsigned>(block_size), fb, fe, dst, fold_channels, static_cast<unsigned>(block_size), fold_planes, accumulate, flags_next, s, hand_over ? &hd : nullptr));
     else
       KNH_HIP(launch_fold(true, d_partials, n_waves, static_cast<unsigned>(block_size), fb, fe, dst, fold_channels, static_cast<unsigned>(block_size), n_blocks * fold_planes, accumulate, flags_next, s, hand_over ? &hd : nullptr));
 
@@ -2209,7 +2179,7 @@ struct Bank final : knh_bank {
       if (out_host) KNH_HIP(hipMemcpyAsync(h_out, dst, out_bytes, hipMemcpyDeviceToHost, s));
       KNH_HIP(hipMemcpyAsync(h_flags, flags_now, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
       if (voices_host)
-        KNH_HIP(hipMemcpyAsync(voices_host, interp ? d_partials : d_voices, static_cast<size_t>(fold_planes) * nv * block_size * sizeof(F), hipMemcpyDeviceToHost, s));
+        KNH_HIP(hipMemcpyAsync(voices_host, rows_per_voice ? d_partials : d_voices, static_cast<size_t>(fold_planes) * nv * block_size * sizeof(F), hipMemcpyDeviceToHost, s));
       KNH_HIP(hipStreamSynchronize(s));
     }
     if (out_host) {
@@ -2224,33 +2194,24 @@ struct Bank final : knh_bank {
     return KNH_OK;
   }
   uint32_t partials_blocks = 1, out_blocks = 1;
-  template <typename FF> hipError_t launch_frame(const VoiceKernelArgs<FF>& a, hipStream_t s) {
-    struct { VoiceKernelArgs<FF> a; FF* rows; const uint32_t* sin_slots; uint32_t n_sin; } args{a, reinterpret_cast<FF*>(d_partials), d_sin_slots, n_sin};
-    return knh::jit_frame_launch(frame_jit, &args, sizeof(args), (a.n_voices + frame_vpw - 1u) / frame_vpw, s);
+  // a lane per frame: the kernel built at init, or the interpreter
+  hipError_t launch_frames(const VoiceKernelArgs<F>& a, hipStream_t s) {
+    F* const rows = d_partials;
+    if (form.jit) {
+      struct { VoiceKernelArgs<F> a; F* rows; const uint32_t* sin_slots; uint32_t n_sin; } args{a, rows, d_sin_slots, n_sin};
+      return knh::jit_frame_launch(form.jit, &args, sizeof(args), (a.n_voices + frame_vpw - 1u) / frame_vpw, s);
+    }
+    const unsigned n_ops = static_cast<unsigned>(h_prog.size()), n_words = static_cast<unsigned>(n_slots);
+    if constexpr (sizeof(F) == 4) return knh::launch_interp_f32(a, d_prog, n_ops, n_words, interp_sigs, interp_out, rows, s);
+    else return knh::launch_interp_f64(a, d_prog, n_ops, n_words, interp_sigs, interp_out, rows, s);
   }
-  hipError_t launch_interp(const VoiceKernelArgs<float>& a, hipStream_t s) {
-    if (frame_jit) return launch_frame<float>(a, s);
-    return knh::launch_interp_f32(a, d_prog, static_cast<unsigned>(h_prog.size()), static_cast<unsigned>(n_slots), interp_sigs, interp_out, reinterpret_cast<float*>(d_partials), s);
+  hipError_t launch_voice(const VoiceKernelArgs<F>& a, unsigned n_waves, hipStream_t s) {
+    return form.jit ? knh::jit_launch(form.jit, &a, sizeof(a), n_waves, s) : form.fn(a, n_waves, s);
   }
-  hipError_t launch_interp(const VoiceKernelArgs<double>& a, hipStream_t s) {
-    if (frame_jit) return launch_frame<double>(a, s);
-    return knh::launch_interp_f64(a, d_prog, static_cast<unsigned>(h_prog.size()), static_cast<unsigned>(n_slots), interp_sigs, interp_out, reinterpret_cast<double*>(d_partials), s);
-  }
-  hipError_t launch_voice(const VoiceKernelArgs<float>& a, unsigned n_waves, hipStream_t s) {
-    if (jit) return knh::jit_launch(jit, &a, sizeof(a), n_waves, s);
-    if (wide_waves == 4) return wide->f32_w4[desc.allow_fma ? 1 : 0](a, n_waves, s);
-    if (wide_waves == 8) return wide->f32_w8[desc.allow_fma ? 1 : 0](a, n_waves, s);
-    if (wide_waves == 16) return wide->f32_w16[desc.allow_fma ? 1 : 0](a, n_waves, s);
-    if (pipe) return pipe->f32[desc.allow_fma ? 1 : 0](a, n_waves, s);
-    return entry->f32[desc.allow_fma ? 1 : 0](a, n_waves, s);
-  }
-  hipError_t launch_voice(const VoiceKernelArgs<double>& a, unsigned n_waves, hipStream_t s) {
-    if (jit) return knh::jit_launch(jit, &a, sizeof(a), n_waves, s);
-    if (wide_waves == 4) return wide->f64_w4[desc.allow_fma ? 1 : 0](a, n_waves, s);
-    if (wide_waves == 8) return wide->f64_w8[desc.allow_fma ? 1 : 0](a, n_waves, s);
-    if (wide_waves == 16) return wide->f64_w16[desc.allow_fma ? 1 : 0](a, n_waves, s);
-    if (pipe) return pipe->f64[desc.allow_fma ? 1 : 0](a, n_waves, s);
-    return entry->f64[desc.allow_fma ? 1 : 0](a, n_waves, s);
+  // a pre-built kernel's launch function for the bank's sample type and allow_fma
+  knh::VoiceLaunchFn<F> launch_fn(const knh::VoiceLaunchFn<float> (&f32)[2], const knh::VoiceLaunchFn<double> (&f64)[2]) const {
+    if constexpr (sizeof(F) == 4) return f32[desc.allow_fma ? 1 : 0];
+    else return f64[desc.allow_fma ? 1 : 0];
   }
   static hipError_t launch_fold(bool tree, const float* rows, unsigned n, unsigned len, unsigned fb, unsigned fe, float* out, unsigned ch, unsigned os, unsigned nb, bool acc, uint32_t* zf, hipStream_t s, const knh_dev::HostDone* hd) {
     return knh::launch_fold_f32(tree, rows, n, len, fb, fe, out, ch, os, nb, acc, zf, s, hd);
@@ -2275,13 +2236,11 @@ struct Bank final : knh_bank {
     KNH_HIP(hipSetDevice(device));
     KNH_HIP(hipDeviceSynchronize());
     KNH_HIP(hipMemcpy(out16, flags_last ? flags_last : d_flags, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    // word 2 (no kernel writes it): the kernel form the bank's launches take, in the order launch_interp / launch_voice decide it
-    out16[2] = interp ? (frame_jit ? KNH_DEBUG_FORM_FRAME_JIT : KNH_DEBUG_FORM_FRAME_INTERP)
-             : jit ? (jit_pipe ? KNH_DEBUG_FORM_PIPELINE_FUSED : KNH_DEBUG_FORM_WHOLE_CHAIN_FUSED)
-             : wide_waves != 0 ? KNH_DEBUG_FORM_MANY_WAVE : pipe ? KNH_DEBUG_FORM_PIPELINE : KNH_DEBUG_FORM_WHOLE_CHAIN;
+    // word 2 (no kernel writes it): the kernel form the bank's launches take
+    out16[2] = form.is.kind;
     // word 3 (no kernel writes it): the voices per workgroup of a whole-block launch in the lane-per-frame forms, 0 in every other
-    out16[3] = !interp ? 0u
-             : frame_jit ? frame_vpw
+    out16[3] = !form.facts.rows_per_voice ? 0u
+             : form.jit ? frame_vpw
              : knh::interp_voices_per_workgroup(nv, static_cast<unsigned>(h_prog.size()), static_cast<unsigned>(n_slots), interp_sigs, static_cast<unsigned>(block_size), sizeof(F) == 8);
     return KNH_OK;
   }

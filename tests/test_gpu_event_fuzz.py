@@ -24,7 +24,7 @@ BOOLS = {"looping"}
 @pytest.mark.parametrize("seed", range(int(os.environ.get("KNH_TEST_SEEDS", "32"))))
 def test_random_parameter_traffic(knh, oracle, monkeypatch, seed):
     rng = np.random.default_rng(7000 + seed)
-    # every kernel form gets its share of the seeds (the switches are read when a bank is created)
+    # every kernel form gets its share of the seeds (the switches are read when a bank is created and initialised)
     form = [{}, {"KNH_PIPE_BIG": "0"}, {"KNH_PIPE_BIG": "1"}, {"KNH_PIPELINE": "0"}, {"KNH_PIPELINE": "0", "KNH_WIDE": "4"}, {"KNH_JIT": "1"},
             {"KNH_JIT": "1", "KNH_JIT_PIPE": "0"}][(seed // 8) % 7]
     for k_, v_ in form.items():

@@ -27,7 +27,7 @@ PAIR = {"pair": {"KNH_PIPELINE": "1", "KNH_PAIR": "1"}}  # two voice groups per 
 
 
 def _bank(knh, monkeypatch, w, env, mix=L.MIX_TREE):
-    with monkeypatch.context() as m:  # (the switches are read when a bank is created)
+    with monkeypatch.context() as m:  # (the switches are read when a bank is created and initialised)
         for k, v in env.items():
             m.setenv(k, v)
         return make_gpu(knh, w, mix)

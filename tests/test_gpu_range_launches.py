@@ -37,7 +37,7 @@ forms = pytest.mark.parametrize("form", list(FORMS))
 
 
 def _bank(knh, monkeypatch, w, env, mix=L.MIX_TREE, **kw):
-    with monkeypatch.context() as m:  # (the switches are read when a bank is created)
+    with monkeypatch.context() as m:  # (the switches are read when a bank is created and initialised)
         for k, v in env.items():
             m.setenv(k, v)
         return make_gpu(knh, w, mix, **kw)

@@ -47,3 +47,12 @@ def test_shard_worker_pool_plain_and_under_thread_sanitizer():
             cmd = ["setarch", platform.machine(), "-R"] + cmd
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
         assert res.returncode == 0 and "ok   shard_workers" in res.stdout, name + ":\n" + res.stdout + res.stderr
+
+
+def test_kernel_form_decision_table():
+    """knaster_amd/csrc/kernel_form.hpp (which kernel form a bank takes) has no HIP in it either: tests/cpp/kernel_form_test.cpp
+    holds the decision to a hand-written table of (inputs, switches) -> candidate forms, on the CPU, with no library."""
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    subprocess.run(["make", "-C", cpp, "bin/kernel_form_test"], check=True, capture_output=True)
+    res = subprocess.run([os.path.join(cpp, "bin", "kernel_form_test")], capture_output=True, text=True, timeout=60)
+    assert res.returncode == 0 and "ok   kernel_form" in res.stdout, res.stdout + res.stderr

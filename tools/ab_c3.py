@@ -73,7 +73,7 @@ def run(libt, h, w, launches):
 
 def main():
     # "lib.so@KNH_PIPE_BIG=1": that environment switch is set while the bank of that side is created (the library reads its
-    # switches in knh_bank_create / knh_bank_init), so two forms of one build can be compared too
+    # form switches in knh_bank_init, the others in knh_bank_create), so two forms of one build can be compared too
     specs = [a.split("@") for a in sys.argv[1:3]]
     paths = [sp[0] for sp in specs]
     name = sys.argv[3] if len(sys.argv) > 3 else "C3"
