@@ -134,6 +134,7 @@ pub const KNH_SVF_HIGH_SHELF: u32 = 8;
 pub const KNH_STAGE_FLAG_AR_FREQ: u16 = 1 << 0;
 pub const KNH_STAGE_FLAG_SMOOTH_PARAMS: u16 = 1 << 1;
 pub const KNH_STAGE_FLAG_READER_CH1: u16 = 1 << 2;
+pub const KNH_STAGE_FLAG_WAVETABLE: u16 = 1 << 3;
 
 // knh_mix_mode
 pub const KNH_MIX_TREE: u32 = 0;
@@ -167,6 +168,9 @@ unsafe extern "C" {
     pub fn knh_bank_set_voice_ctor_args(bank: *mut knh_bank, stage: u32, count: usize, voices: *const u32, args: *const f64, n_args: u32) -> i32;
     pub fn knh_bank_restart_voices(bank: *mut knh_bank, count: usize, voices: *const u32) -> i32;
     pub fn knh_bank_buffer_count(bank: *const knh_bank, stage: u32) -> u32;
+    pub fn knh_bank_add_wavetable(bank: *mut knh_bank, stage: u32, samples: *const c_void, n_tables: u32, out_index: *mut u32) -> i32;
+    pub fn knh_bank_wavetable_count(bank: *const knh_bank, stage: u32) -> u32;
+    pub fn knh_bank_assign_wavetables(bank: *mut knh_bank, stage: u32, count: usize, voices: *const u32, entries: *const u32, ctor: *const f64) -> i32;
     pub fn knh_bank_connect_outputs(bank: *mut knh_bank, n_channels: u32, stages: *const u32) -> i32;
     pub fn knh_bank_output_stage(bank: *const knh_bank, channel: u32) -> u32;
     pub fn knh_bank_init(bank: *mut knh_bank, sample_rate: u32, block_size: usize) -> i32;

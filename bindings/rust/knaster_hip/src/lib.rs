@@ -299,6 +299,31 @@ impl<F: Float, I: Size> GpuVoiceBank<F, I> {
     pub fn buffer_count(&self, stage: usize) -> u32 {
         unsafe { knh_bank_buffer_count(self.h, stage as u32) }
     }
+    /// One more `Wavetable<F>` in the pool of the `KNH_STAGE_FLAG_WAVETABLE` stage (an `OscWt`); returns its pool index.
+    /// `tables`: 17 x 16384 samples (the partial tables in order) or 16384 (one table that serves as all seventeen,
+    /// `Wavetable::from_buffer`).  Before the bank is pushed.
+    pub fn add_wavetable(&mut self, stage: usize, tables: &[F]) -> Result<u32, BankError> {
+        if tables.len() % 16384 != 0 {
+            return Err(BankError("add_wavetable: tables holds whole tables of 16384 samples".into()));
+        }
+        let mut index = 0u32;
+        let rc = unsafe { knh_bank_add_wavetable(self.h, stage as u32, tables.as_ptr() as *const c_void, (tables.len() / 16384) as u32, &mut index) };
+        if rc != KNH_OK { Err(last_error(self.h)) } else { Ok(index) }
+    }
+    pub fn wavetable_count(&self, stage: usize) -> u32 {
+        unsafe { knh_bank_wavetable_count(self.h, stage as u32) }
+    }
+    /// Voice `voices[i]` plays pool entry `entries[i]`.  `ctor`: the new oscillator's `freq` per voice.  Before the bank is
+    /// pushed it may be `None`; afterwards it is required, and the voice's node is a new `OscWt` on that entry from the
+    /// next block on.
+    pub fn assign_wavetables(&mut self, stage: usize, voices: &[u32], entries: &[u32], ctor: Option<&[f64]>) -> Result<(), BankError> {
+        if voices.len() != entries.len() || ctor.map_or(false, |c| c.len() != voices.len()) {
+            return Err(BankError("assign_wavetables: voices, entries and ctor must have one length".into()));
+        }
+        let c = ctor.map_or(core::ptr::null(), |c| c.as_ptr());
+        let rc = unsafe { knh_bank_assign_wavetables(self.h, stage as u32, voices.len(), voices.as_ptr(), entries.as_ptr(), c) };
+        if rc != KNH_OK { Err(last_error(self.h)) } else { Ok(()) }
+    }
     /// Graph output 0 carries the signal of stage `left`'s node, output 1 that of stage `right`'s: what
     /// `l.to_graph_out_channels([0]); r.to_graph_out_channels([1])` connects.  Before the bank is pushed; naming the last
     /// stage twice restores the voice with one signal.

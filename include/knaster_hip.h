@@ -74,6 +74,8 @@ typedef enum knh_value_kind {
  *     with KNH_STAGE_FLAG_AR_FREQ: pushed as SinWt::new(freq).ar_params() and
  *     `.link("freq", x)` -- the running signal drives param 0 every sample
  *     (audio_rate.rs:42-57, graph_edit.rs:735-754); x is replaced by its output.
+ *     with KNH_STAGE_FLAG_WAVETABLE: g.push(OscWt) on a Wavetable<F> of the stage's pool (osc.rs:28-87,
+ *     wavetable.rs:327-610) -- the same three parameters, one node, one constructor argument (freq); below, at the flag.
  * KNH_STAGE_SIN_NUMERIC     g.push(SinNumeric::new(freq))       osc.rs:222-271       1    freq
  *     params: 0 freq, 1 phase_offset, 2 reset_phase(trigger)
  * KNH_STAGE_SVF             x >> SvfFilter::new(ty,cutoff,q,gain_db)  svf.rs:44-281  1    type, cutoff, q, gain_db
@@ -311,7 +313,29 @@ enum {
    * would have to act on both channels -- use a MUL_CONST per channel, which is what `play * amp.out([0, 0])` is);
    * a pool of single-channel Buffers under it (knh_bank_init: KNH_ERR_INVALID_ARGUMENT -- the reference reads the
    * neighbouring sample there and runs off the end); more than two channels. */
-  KNH_STAGE_FLAG_READER_CH1 = 1u << 2
+  KNH_STAGE_FLAG_READER_CH1 = 1u << 2,
+  /* kind = KNH_STAGE_SIN_WT with this flag: g.push(OscWt) -- the anti-aliased wavetable oscillator, osc.rs:28-87 -- on a
+   * Wavetable<F> of the stage's pool (knh_bank_add_wavetable; which entry a voice plays: knh_bank_assign_wavetables, entry 0
+   * otherwise).  On any other kind: KNH_ERR_INVALID_ARGUMENT at knh_bank_create.
+   * What the node does (restated from the reference): init sets phase = 0 and freq_to_phase_inc = 16384 * 65536 / sample_rate
+   * (f64, osc.rs:82-86); freq(v) keeps self.freq = F::new(v) and step = (freq as f64 * freq_to_phase_inc) as u32, a
+   * saturating cast (:44-47); phase_offset(v) = (v * 65536.0) as u32 (:50-52); every sample is
+   * wavetable.get(phase + phase_offset, self.freq), then phase = phase.wrapping_add(step) (:62-70).  Wavetable::get
+   * (wavetable.rs:606-609) reads entry (phase >> 16) & 16383, without interpolation, of the partial table
+   * freq_to_table_index(freq as f32) (:329-377): the number of the thresholds 32 * 1.5^k, k = 0..15 (as f32: 32, 48, 72, 108,
+   * 162, 243, 364.5, 546.75, 820.125, 1230.1875, 1845.28125, 2767.921875, 4151.8828125, 6227.82421875, 9341.736328125,
+   * 14012.6044921875) the frequency exceeds -- a frequency on a threshold stays below it, a negative one reads table 0 (a NaN
+   * table 16).  The tables hold samples of F.  No floating-point arithmetic lies between a table and the output: bit-exact.
+   * params: 0 freq, 1 phase_offset, 2 reset_phase(trigger) -- SinWt's three, in SinWt's order; knh_chain_ugen_count counts 1.
+   * A DECISION: the reference has no OscWt::new at the surveyed commit (the struct's fields are private and nothing
+   * constructs it), so there is no constructor argument to restate.  Here the stage takes ONE constructor argument, freq,
+   * applied as freq(v) right after init -- what SinWt::init does with the frequency its own constructor got (osc.rs:142-147).
+   * It combines exactly as plain SIN_WT does with delayed_changes_per_block (a sample-accurate freq change moves step and
+   * table at the same frame), KNH_STAGE_FLAG_SMOOTH_PARAMS, KNH_STAGE_FLAG_AR_FREQ and ar_param 1 (freq: step and table index
+   * per sample) and 2 (phase_offset), input / input2, knh_bank_connect_outputs, following KNH_STAGE_WR_* stages, Pan2 or
+   * Galactic at the end, restart, host-sharded / multi-device / rank banks.  A voice may hold several such stages, each with
+   * a pool of its own.  A voice with such a stage is fused at knh_bank_init (no pre-built kernel, never a lane per frame). */
+  KNH_STAGE_FLAG_WAVETABLE = 1u << 3
 };
 
 typedef struct knh_stage_desc {
@@ -475,6 +499,31 @@ int32_t knh_bank_assign_buffers(knh_bank* bank, uint32_t stage, size_t count, co
                                 const uint32_t* buffer_ids, const double* ctor);
 /* Entries in the pool of BufferReader stage `stage` (0 for any other stage). */
 uint32_t knh_bank_buffer_count(const knh_bank* bank, uint32_t stage);
+/* ---- Wavetables: the pool of a KNH_STAGE_FLAG_WAVETABLE stage ---------------------------------------------------------
+ * One more Wavetable<F> (dsp/wavetable.rs:396-610) in the pool of stage `stage`; *out_index (may be NULL) = its pool index
+ * (0, 1, 2, ... in call order).  samples = [n_tables][16384] of the bank's sample type.  n_tables = 17: the partial tables
+ * in order (table i is read at frequencies above 32 * 1.5^(i - 1) up to 32 * 1.5^i; the reference keeps them private, so a
+ * host builds them itself: knaster_host.hpp has the reference's builders).  n_tables = 1: one table that serves as all
+ * seventeen, which is what Wavetable::from_buffer builds (:428-442); it is stored once.  Before knh_bank_init only.
+ * Every pool of the bank lives in one device allocation of at most 2^32 - 1 samples; host-sharded, multi-device and rank
+ * banks give every range / rank the whole pool.  A refused call changes nothing: any other n_tables, a null pointer, a stage
+ * without the flag, a call after knh_bank_init (all KNH_ERR_INVALID_ARGUMENT), a pool too large. */
+int32_t knh_bank_add_wavetable(knh_bank* bank, uint32_t stage, const void* samples, uint32_t n_tables, uint32_t* out_index);
+/* Entries in the pool of stage `stage` (0 for a stage without KNH_STAGE_FLAG_WAVETABLE).  knh_bank_init with a flagged stage
+ * whose pool is empty is KNH_ERR_INVALID_ARGUMENT. */
+uint32_t knh_bank_wavetable_count(const knh_bank* bank, uint32_t stage);
+/* Voice voices[i] plays pool entry entries[i] (every voice: entry 0 until told otherwise).  ctor: NULL, or [count] = freq
+ * (the stage's constructor argument).
+ * Before knh_bank_init: the Wavetable the voice's OscWt is constructed on (a non-NULL ctor also replaces its freq).
+ * After knh_bank_init, ctor required: from the first frame of the next process call on the voice's node is a new OscWt on
+ * that entry -- phase 0, phase_offset 0, freq from ctor (the decision at KNH_STAGE_FLAG_WAVETABLE), a WrSmoothParams around
+ * it back to "no smoothing selected", a WrPreciseTiming around it with no delay armed and nothing queued (changes still waiting
+ * for the old node went with it).  ctor becomes the voice's constructor argument, as knh_bank_set_voice_ctor_args' would.
+ * knh_bank_restart_voices reconstructs a voice on the entry it currently has.
+ * Refused, changing nothing: a stage without the flag, a null array, ctor == NULL after init (KNH_ERR_INVALID_ARGUMENT); a
+ * voice or an entry that does not exist (KNH_ERR_OUT_OF_RANGE). */
+int32_t knh_bank_assign_wavetables(knh_bank* bank, uint32_t stage, size_t count, const uint32_t* voices,
+                                   const uint32_t* entries, const double* ctor);
 /* ---- Stereo voices: two of a voice's signals connected to graph outputs 0 and 1 ------------------------------------------
  * Which signal of a voice each graph output carries (to_graph_out_channels / `(l | r).to_graph_out()`,
  * graph_edit.rs:363-394, 1219-1368; one Add chain per output channel, graph.rs:827-872).  An output connection is an edge,

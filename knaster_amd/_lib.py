@@ -33,6 +33,8 @@ VALUE_FLOAT, VALUE_TRIGGER, VALUE_INTEGER, VALUE_BOOL, VALUE_SMOOTHING = 0, 1, 2
 STAGE_FLAG_AR_FREQ = 1
 STAGE_FLAG_SMOOTH_PARAMS = 2
 STAGE_FLAG_READER_CH1 = 4  # a STAGE_BUFFER_READER stage with it: output channel 1 of the reader stage `input` names
+STAGE_FLAG_WAVETABLE = 8  # a STAGE_SIN_WT stage with it: OscWt on a Wavetable of the stage's pool (add_wavetable)
+WAVETABLE_SIZE, WAVETABLE_TABLES = 16384, 17  # samples per partial table, partial tables per Wavetable
 # knh_svf_type
 SVF_LOW, SVF_HIGH, SVF_BAND, SVF_NOTCH, SVF_PEAK, SVF_ALL, SVF_BELL, SVF_LOW_SHELF, SVF_HIGH_SHELF = range(9)
 # knh_mix_mode
@@ -83,6 +85,9 @@ PROTOTYPES = {
     "knh_bank_set_voice_ctor_args": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32]),
     "knh_bank_restart_voices": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "knh_bank_buffer_count": (C.c_uint32, [C.c_void_p, C.c_uint32]),
+    "knh_bank_add_wavetable": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "knh_bank_wavetable_count": (C.c_uint32, [C.c_void_p, C.c_uint32]),
+    "knh_bank_assign_wavetables": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "knh_bank_connect_outputs": (C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "knh_bank_output_stage": (C.c_uint32, [C.c_void_p, C.c_uint32]),
     "knh_bank_init": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_size_t]),

@@ -189,6 +189,35 @@ class VoiceBank:
     def buffer_count(self, stage: int) -> int:
         return int(self._lib.knh_bank_buffer_count(self._h, stage))
 
+    def add_wavetable(self, stage: int, tables) -> int:
+        """One more Wavetable in the pool of the STAGE_FLAG_WAVETABLE stage -> its pool index; before init
+        (knh_bank_add_wavetable).  tables: [17, 16384] (the partial tables in order), or [16384] / [1, 16384] (one table
+        that serves as all seventeen, Wavetable::from_buffer), of the bank's sample type.  The table count is passed on as it
+        is: the library refuses any other."""
+        a = np.ascontiguousarray(np.asarray(tables, dtype=self.dtype))
+        if a.ndim == 1:
+            a = a.reshape(1, -1)
+        if a.ndim != 2 or a.shape[1] != L.WAVETABLE_SIZE:
+            raise ValueError(f"add_wavetable: tables must be [n_tables, {L.WAVETABLE_SIZE}], got {a.shape}")
+        index = C.c_uint32(0)
+        self._check(self._lib.knh_bank_add_wavetable(self._h, stage, a.ctypes.data_as(C.c_void_p), a.shape[0], C.byref(index)))
+        return int(index.value)
+
+    def wavetable_count(self, stage: int) -> int:
+        return int(self._lib.knh_bank_wavetable_count(self._h, stage))
+
+    def assign_wavetables(self, stage: int, voices, entries, ctor=None):
+        """Voice voices[i] plays pool entry entries[i]; ctor: None or [count] = freq (knh_bank_assign_wavetables).  After
+        init ctor is required: the voice gets a new OscWt on that entry at the next process call."""
+        v = np.ascontiguousarray(voices, dtype=np.uint32)
+        ids = np.ascontiguousarray(np.broadcast_to(np.asarray(entries, dtype=np.uint32), v.shape))
+        c = None
+        if ctor is not None:
+            c = np.ascontiguousarray(np.broadcast_to(np.asarray(ctor, dtype=np.float64).reshape(-1), v.shape))
+        self._check(self._lib.knh_bank_assign_wavetables(self._h, stage, v.shape[0], v.ctypes.data_as(C.c_void_p),
+                                                         ids.ctypes.data_as(C.c_void_p),
+                                                         None if c is None else c.ctypes.data_as(C.c_void_p)))
+
     def connect_outputs(self, left: int, right: int):
         """Graph output 0 carries the signal of stage `left`'s node, output 1 that of stage `right`'s
         (to_graph_out_channels; knh_bank_connect_outputs).  Before init; the last stage twice restores the default."""

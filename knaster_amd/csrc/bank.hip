@@ -62,6 +62,8 @@ knh_bank* make_bank(const knh_bank_desc& d, const std::string& sig) {
     if (s.kind == KNH_STAGE_BUFFER_READER && s.ar_param != 0) s.n_slots = 14;
     // the second output of a BufferReader (KNH_STAGE_FLAG_READER_CH1) is no node: no slots, no parameters, no constructor arguments
     if (s.ch1()) s.n_slots = s.n_params = s.n_ctor = 0;
+    // OscWt (KNH_STAGE_FLAG_WAVETABLE) keeps the table it reads and its pool entry beside SinWt's three words (knh_dev::OscWtT)
+    if (s.wavetable()) s.n_slots = 5;
     b->stages.push_back(s);
     b->ctor.emplace_back(static_cast<size_t>(d.n_voices) * (s.n_ctor > 0 ? s.n_ctor : 0), 0.0);
     slot += s.n_slots;
@@ -465,6 +467,21 @@ uint32_t knh_bank_output_stage(const knh_bank* bank, uint32_t channel) {
   if (!bank || channel >= bank->desc.out_channels || bank->stages.empty()) return 0xFFFFFFFFu;
   return bank->connected ? bank->out_stage[channel] : static_cast<uint32_t>(bank->stages.size()) - 1u;
 }
+int32_t knh_bank_add_wavetable(knh_bank* bank, uint32_t stage, const void* samples, uint32_t n_tables, uint32_t* out_index) {
+  if (!bank) return KNH_ERR_INVALID_ARGUMENT;
+  return guarded(bank, [&]() -> int32_t { return bank->add_wavetable(stage, samples, n_tables, out_index); });
+}
+int32_t knh_bank_assign_wavetables(knh_bank* bank, uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* entries, const double* ctor) {
+  if (!bank) return KNH_ERR_INVALID_ARGUMENT;
+  return guarded(bank, [&]() -> int32_t { return bank->assign_wavetables(stage, count, voices, entries, ctor); });
+}
+uint32_t knh_bank_wavetable_count(const knh_bank* bank, uint32_t stage) {
+  try {
+    return bank ? bank->wavetable_count(stage) : 0u;
+  } catch (...) {
+    return 0u;
+  }
+}
 uint32_t knh_bank_buffer_count(const knh_bank* bank, uint32_t stage) {
   try {
     return bank ? bank->buffer_count(stage) : 0u;
@@ -741,7 +758,11 @@ int32_t knh_bank_algorithmic_bytes_per_voice_block(const knh_bank* bank, uint32_
     for (const StageInfo& s : bank->stages) {
       r += word * s.n_slots;
       switch (s.kind) {
-        case KNH_STAGE_SIN_WT: w += word * ((s.flags & KNH_STAGE_FLAG_AR_FREQ) ? 2 : 1); break;
+        case KNH_STAGE_SIN_WT:
+          w += word * ((s.flags & KNH_STAGE_FLAG_AR_FREQ) ? (s.wavetable() ? 3 : 2) : 1);
+          // OscWt gathers its samples from the bank's wavetables in device memory: one table sample read per frame (0 before knh_bank_init)
+          if (s.wavetable()) r += word * static_cast<uint32_t>(bank->block_size);
+          break;
         case KNH_STAGE_SIN_NUMERIC: w += word; break;
         case KNH_STAGE_SVF: w += word * 2; break;
         case KNH_STAGE_ONEPOLE_LPF: case KNH_STAGE_ONEPOLE_HPF: w += word; break;

@@ -43,6 +43,12 @@ struct knh_bank {
   virtual void drop_last_buffer(uint32_t /*stage*/) {}  // undoes the add_buffer just made (a bank of several ranges keeping them alike)
   virtual int assign_buffers(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* buffer_ids, const double* ctor) = 0;
   virtual uint32_t buffer_count(uint32_t stage) const = 0;
+  // the pool of Wavetables of a KNH_STAGE_FLAG_WAVETABLE stage (OscWt): one more entry of n_tables (17 or 1) x 16384 samples; which
+  // entry each voice plays (ctor: null, or [count] = freq); how many there are
+  virtual int add_wavetable(uint32_t stage, const void* samples, uint32_t n_tables, uint32_t* out_index) = 0;
+  virtual void drop_last_wavetable(uint32_t /*stage*/) {}  // undoes the add_wavetable just made (a bank of several ranges keeping them alike)
+  virtual int assign_wavetables(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* entries, const double* ctor) = 0;
+  virtual uint32_t wavetable_count(uint32_t stage) const = 0;
   virtual int init(uint32_t sr, size_t bs) = 0;
   // knh_bank_set_voice_ctor_args / knh_bank_restart_voices: voices of a running bank become freshly constructed nodes
   // (keep = false: the call is checked and nothing is kept -- a bank of several ranges asks every range before any keeps its share)

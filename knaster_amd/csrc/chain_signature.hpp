@@ -45,8 +45,10 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
                         st[i].kind == KNH_STAGE_RANDOM_LIN ||
                         st[i].kind == KNH_STAGE_POLYBLEP || st[i].kind == KNH_STAGE_BUFFER_READER || st[i].kind == KNH_STAGE_INPUT);
     const bool ar = st[i].kind == KNH_STAGE_SIN_WT && (st[i].flags & KNH_STAGE_FLAG_AR_FREQ);
+    const bool wt = st[i].kind == KNH_STAGE_SIN_WT && (st[i].flags & KNH_STAGE_FLAG_WAVETABLE);  // OscWt: 'M' for 'W', 'k' for 'R'
     const bool math2 = is_math2_kind(st[i].kind);
-    if (st[i].flags & ~(KNH_STAGE_FLAG_AR_FREQ | KNH_STAGE_FLAG_SMOOTH_PARAMS | KNH_STAGE_FLAG_READER_CH1)) { *why = "unknown stage flag"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (st[i].flags & ~(KNH_STAGE_FLAG_AR_FREQ | KNH_STAGE_FLAG_SMOOTH_PARAMS | KNH_STAGE_FLAG_READER_CH1 | KNH_STAGE_FLAG_WAVETABLE)) { *why = "unknown stage flag"; return KNH_ERR_INVALID_ARGUMENT; }
+    if ((st[i].flags & KNH_STAGE_FLAG_WAVETABLE) && st[i].kind != KNH_STAGE_SIN_WT) { *why = "WAVETABLE is only defined for SIN_WT"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((st[i].flags & KNH_STAGE_FLAG_SMOOTH_PARAMS) && (st[i].flags & KNH_STAGE_FLAG_AR_FREQ)) { *why = "SMOOTH_PARAMS and AR_FREQ cannot be combined"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((st[i].flags & KNH_STAGE_FLAG_SMOOTH_PARAMS) && is_wrapper_kind(st[i].kind)) { *why = "SMOOTH_PARAMS applies to a node, not to a wrapper stage"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((st[i].flags & KNH_STAGE_FLAG_AR_FREQ) && st[i].kind != KNH_STAGE_SIN_WT) { *why = "AR_FREQ is only defined for SIN_WT"; return KNH_ERR_INVALID_ARGUMENT; }
@@ -95,7 +97,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       if (kKinds[st[i].kind].sig == 'I' || st[st[i].input2 - 1].kind == KNH_STAGE_INPUT) { *why = "an audio-rate parameter edge starts at a node, not at a bank input (put the input through `* 1.0`)"; return KNH_ERR_INVALID_ARGUMENT; }
     }
     // ('T': a reader with two outputs; '2': its second output, which is no device stage and leaves the signature below)
-    sig->push_back(ar ? 'R' : ch1 ? '2' : (st[i].kind == KNH_STAGE_BUFFER_READER && companion[i] >= 0) ? 'T' : kKinds[st[i].kind].sig);
+    sig->push_back(wt ? (ar ? 'k' : 'M') : ar ? 'R' : ch1 ? '2' : (st[i].kind == KNH_STAGE_BUFFER_READER && companion[i] >= 0) ? 'T' : kKinds[st[i].kind].sig);
     have_x = true;
   }
   // A voice that is a graph (a stage that names its operands, a MathUGen of two signals, a second source): every stage is
@@ -131,7 +133,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       return k;
     };
     for (uint32_t i = 0; i < n; ++i) {
-      const bool reads = i > 0 && !(std::strchr("WNPUKOGBFIT2", (*sig)[i]) != nullptr);  // 'R' reads, the plain sources do not (nor does a reader's second output: it IS the reader)
+      const bool reads = i > 0 && !(std::strchr("WMNPUKOGBFIT2", (*sig)[i]) != nullptr);  // 'R' reads, the plain sources do not (nor does a reader's second output: it IS the reader)
       if (is_math2_kind(st[i].kind)) { a[i] = node_output(st[i].input - 1); b[i] = node_output(st[i].input2 - 1); }
       else if (reads) a[i] = st[i].input ? node_output(st[i].input - 1) : static_cast<int>(i) - 1;
       if (st[i].ar_param != 0) b[i] = node_output(st[i].input2 - 1);  // the signal that drives the parameter

@@ -111,6 +111,15 @@ struct GalacticBank final : knh_bank {
     return adopt(inner->assign_buffers(stage, count, voices, ids, ctor));
   }
   uint32_t buffer_count(uint32_t stage) const override { return mine(stage) ? 0u : inner->buffer_count(stage); }
+  int add_wavetable(uint32_t stage, const void* samples, uint32_t n_tables, uint32_t* out_index) override {
+    if (mine(stage)) return fail(KNH_ERR_INVALID_ARGUMENT, "not a KNH_STAGE_FLAG_WAVETABLE stage");
+    return adopt(inner->add_wavetable(stage, samples, n_tables, out_index));
+  }
+  int assign_wavetables(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* ids, const double* ctor) override {
+    if (mine(stage)) return fail(KNH_ERR_INVALID_ARGUMENT, "not a KNH_STAGE_FLAG_WAVETABLE stage");
+    return adopt(inner->assign_wavetables(stage, count, voices, ids, ctor));
+  }
+  uint32_t wavetable_count(uint32_t stage) const override { return mine(stage) ? 0u : inner->wavetable_count(stage); }
   // The reverb's 24 rings and its state live here, not in the inner bank, and have no restart yet
   int set_voice_ctor(uint32_t, size_t, const uint32_t*, const double*, uint32_t, bool) override {
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");

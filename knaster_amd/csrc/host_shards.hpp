@@ -143,6 +143,48 @@ struct ShardedBank final : knh_bank {
     }
     return KNH_OK;
   }
+  // OscWt's pools of Wavetables: every range holds the whole pool, as with the Buffers above
+  int add_wavetable(uint32_t stage, const void* samples, uint32_t n_tables, uint32_t* out_index) override {
+    uint32_t index = 0;
+    int done = 0;
+    auto undo = [&] { for (int j = 0; j < done; ++j) shard[j]->drop_last_wavetable(stage); };
+    try {
+      for (; done < n(); ++done) {
+        int rc = shard[done]->add_wavetable(stage, samples, n_tables, &index);
+        if (rc != KNH_OK) { adopt(done, rc); undo(); return rc; }
+      }
+    } catch (...) {
+      undo();
+      throw;
+    }
+    if (out_index) *out_index = index;
+    return KNH_OK;
+  }
+  uint32_t wavetable_count(uint32_t stage) const override { return shard[0]->wavetable_count(stage); }
+  int assign_wavetables(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* ids, const double* ctor) override {
+    if (count && (!voices || !ids)) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
+    // checked as a whole first (a refused call changes nothing in any range): the stage and `ctor` by a range, on an empty call
+    { int rc = shard[0]->assign_wavetables(stage, 0, nullptr, nullptr, ctor); if (rc != KNH_OK) return adopt(0, rc); }
+    const uint32_t n_entries = shard[0]->wavetable_count(stage);
+    for (size_t i = 0; i < count; ++i) {
+      if (voices[i] >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
+      if (ids[i] >= n_entries) return fail(KNH_ERR_OUT_OF_RANGE, "wavetable index out of range");
+    }
+    if (initialised) flush_deferred();  // (earlier batched parameter calls come first, as they were made first)
+    for (int k = 0; k < n(); ++k) {
+      asg_voices.clear(); asg_ids.clear(); asg_ctor.clear();
+      for (size_t i = 0; i < count; ++i) {
+        if (voices[i] < base[k] || voices[i] >= base[k + 1]) continue;
+        asg_voices.push_back(voices[i] - base[k]);
+        asg_ids.push_back(ids[i]);
+        if (ctor) asg_ctor.push_back(ctor[i]);
+      }
+      if (asg_voices.empty()) continue;
+      int rc = shard[k]->assign_wavetables(stage, asg_voices.size(), asg_voices.data(), asg_ids.data(), ctor ? asg_ctor.data() : nullptr);
+      if (rc != KNH_OK) return adopt(k, rc);
+    }
+    return KNH_OK;
+  }
   // knh_bank_set_voice_ctor_args / knh_bank_restart_voices: by global voice index, each range its own voices.  Checked as a whole
   // first -- the ranges are alike, so what one refuses for a voice of its own the bank refuses here -- then handed out.
   std::vector<uint32_t> rs_voices;

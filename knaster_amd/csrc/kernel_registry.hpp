@@ -2,6 +2,9 @@
 //
 // Signature: one character per device stage, in chain order:
 //   W SinWt   R SinWt.ar_params() driven by the running signal   N SinNumeric
+//   M OscWt on a Wavetable of the stage's pool (SIN_WT with KNH_STAGE_FLAG_WAVETABLE)   k OscWt.ar_params() driven by the running signal
+//     (neither has a pre-built kernel: a voice with one is fused at init)
+//   g, h: M, k of a bank whose one f32 table is staged to LDS in the sine table's place (decided at init, voice_bank.hpp)
 //   S SvfFilter   L OnePoleLpf   H OnePoleHpf   A x*EnvAsr   E x*EnvAr   V x*Envelope (segments)   D SampleDelay   P Phasor   X SafetyLimiter   B PolyBlep   Y AllpassDelay   Z AllpassFeedbackDelay   F BufferReader   U WhiteNoise   K PinkNoise   O BrownNoise   G RandomLin
 //   Q Galactic (last stage only: the stereo reverb; never part of a fused kernel -- galactic_bank.hpp runs the chain before it
 //     through one of the kernels below and the reverb in kernels_galactic.hip)

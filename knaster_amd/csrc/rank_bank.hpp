@@ -129,6 +129,43 @@ struct RankBank final : knh_bank {
     // (an empty share still goes to the local bank: its refusals -- no constructor arguments, an envelope in the chain -- are every rank's)
     return adopt(local->assign_buffers(stage, asg_voices.size(), asg_voices.data(), asg_ids.data(), ctor ? (asg_ctor.empty() ? ctor : asg_ctor.data()) : nullptr));
   }
+  // OscWt's pools of Wavetables: every rank is handed the whole pool; a rank without voices holds none, but refuses what the
+  // ranks with voices refuse and counts the entries, so that every rank hands out the same indices
+  std::vector<uint32_t> wt_count;  // [stage], a rank without voices
+  int add_wavetable(uint32_t stage, const void* samples, uint32_t n_tables, uint32_t* out_index) override {
+    if (local) return adopt(local->add_wavetable(stage, samples, n_tables, out_index));
+    if (initialised) return fail(KNH_ERR_INVALID_ARGUMENT, "knh_bank_add_wavetable comes before knh_bank_init");
+    if (stage >= stages.size() || !stages[stage].wavetable()) return fail(KNH_ERR_INVALID_ARGUMENT, "not a KNH_STAGE_FLAG_WAVETABLE stage");
+    if (!samples) return fail(KNH_ERR_INVALID_ARGUMENT, "null wavetable");
+    if (n_tables != 1 && n_tables != kWavetableTables) return fail(KNH_ERR_INVALID_ARGUMENT, "a Wavetable is 17 partial tables of 16384 samples, or 1 that serves as all of them");
+    if (wt_count.size() < stages.size()) wt_count.resize(stages.size(), 0u);
+    if (out_index) *out_index = wt_count[stage];
+    wt_count[stage] += 1;
+    return KNH_OK;
+  }
+  uint32_t wavetable_count(uint32_t stage) const override {
+    if (local) return local->wavetable_count(stage);
+    return stage < wt_count.size() && stages[stage].wavetable() ? wt_count[stage] : 0u;
+  }
+  int assign_wavetables(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* ids, const double* ctor) override {
+    if (stage >= stages.size() || !stages[stage].wavetable()) return fail(KNH_ERR_INVALID_ARGUMENT, "not a KNH_STAGE_FLAG_WAVETABLE stage");
+    if (count && (!voices || !ids)) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
+    const uint32_t n_entries = wavetable_count(stage);
+    for (size_t i = 0; i < count; ++i) {  // voice numbers are the whole bank's: checked here, on every rank alike
+      if (voices[i] >= total) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
+      if (ids[i] >= n_entries) return fail(KNH_ERR_OUT_OF_RANGE, "wavetable index out of range");
+    }
+    if (!local) return initialised && !ctor ? fail(KNH_ERR_INVALID_ARGUMENT, "after knh_bank_init knh_bank_assign_wavetables needs the new oscillator's constructor argument") : KNH_OK;
+    asg_voices.clear(); asg_ids.clear(); asg_ctor.clear();
+    for (size_t i = 0; i < count; ++i) {
+      if (!mine(voices[i])) continue;
+      asg_voices.push_back(voices[i] - lo);
+      asg_ids.push_back(ids[i]);
+      if (ctor) asg_ctor.push_back(ctor[i]);
+    }
+    // (an empty share still goes to the local bank: its refusal of a missing constructor argument is every rank's)
+    return adopt(local->assign_wavetables(stage, asg_voices.size(), asg_voices.data(), asg_ids.data(), ctor ? (asg_ctor.empty() ? ctor : asg_ctor.data()) : nullptr));
+  }
   // knh_bank_set_voice_ctor_args / knh_bank_restart_voices: global voice indices, checked on every rank alike; the voices of
   // other ranks are their business, as with parameter calls
   std::vector<uint32_t> rs_voices;

@@ -85,7 +85,7 @@ bool interp_can_run(const knh_stage_desc* st, uint32_t n) {
 // stage groups of a run-time-built pipeline.
 inline int stage_cost(char c) {
   switch (c) {
-    case 'W': return 7;  case 'R': return 10; case 'N': return 25; case 'S': return 10; case 'L': return 3;
+    case 'W': return 7;  case 'R': return 10; case 'M': return 9; case 'k': return 30; case 'g': return 7; case 'h': return 10; case 'N': return 25; case 'S': return 10; case 'L': return 3;
     case 'H': return 4;  case 'A': return 5;  case 'E': return 5;  case 'V': return 14; case 'D': return 12;
     case 'd': case 'q': return 8;  case 'p': return 40; case 'i': return 10; case 'P': return 6; case 'U': return 14; case 'O': return 19; case 'K': return 50; case 'G': return 10; case 'X': return 4; case 'B': return 45; case 'Y': return 14; case 'Z': return 18; case 'F': case 'C': return 16;  // ('C': the mono reader on a two-channel pool, the same work)
     case 'r': return 12; case 'e': return 20;  // Math1: the correctly rounded sqrt sequence, the device library's exp (ceil floor trunc fract: 1-2)
@@ -134,6 +134,19 @@ inline uint32_t sat_u32(double v) {
   if (!(v > 0.0)) return 0u;
   if (v >= 4294967295.0) return 0xFFFFFFFFu;
   return static_cast<uint32_t>(v);
+}
+
+// freq_to_table_index -- dsp/wavetable.rs:329-377: which of a Wavetable's 17 partial tables a frequency reads (OscWt,
+// KNH_STAGE_FLAG_WAVETABLE).  The thresholds are 32 * 1.5^k, every one exact in f32, compared in f32 as the reference does:
+// the index is the number of them the frequency is not at or below (on a threshold: below it; negative: 0; NaN: 16, where
+// the reference's chain of else-ifs ends).  The device's copy: voice_stages.hpp wt_table_index.
+constexpr uint32_t kWavetableSize = 16384, kWavetableTables = 17;
+inline uint32_t wt_table_index(float f) {
+  static const float kThresholds[16] = {32.0f, 48.0f, 72.0f, 108.0f, 162.0f, 243.0f, 364.5f, 546.75f, 820.125f, 1230.1875f, 1845.28125f,
+                                        2767.921875f, 4151.8828125f, 6227.82421875f, 9341.736328125f, 14012.6044921875f};
+  uint32_t n = 0;
+  for (float t : kThresholds) n += !(f <= t);
+  return n;
 }
 
 // fastapprox::fast::{sin, cos} (crate fastapprox 0.3.1, Cargo.lock:931 -- a crates.io dependency that is not in the
@@ -223,6 +236,8 @@ struct StageInfo {
   // (KNH_STAGE_FLAG_READER_CH1: no node -- no slots, no parameters, no constructor arguments, no shadows)
   bool reader() const { return kind == KNH_STAGE_BUFFER_READER && !(flags & KNH_STAGE_FLAG_READER_CH1); }
   bool ch1() const { return kind == KNH_STAGE_BUFFER_READER && (flags & KNH_STAGE_FLAG_READER_CH1); }
+  // OscWt on a Wavetable of the stage's pool (KNH_STAGE_SIN_WT with KNH_STAGE_FLAG_WAVETABLE): two more slots, the table in use and the voice's entry
+  bool wavetable() const { return kind == KNH_STAGE_SIN_WT && (flags & KNH_STAGE_FLAG_WAVETABLE); }
 };
 const char kCh1NoParams[] = "a KNH_STAGE_FLAG_READER_CH1 stage is the second output of a BufferReader, not a node: it has no parameters (address the reader stage)";
 inline bool is_reader_ch1(const knh_stage_desc& d) { return d.kind == KNH_STAGE_BUFFER_READER && (d.flags & KNH_STAGE_FLAG_READER_CH1); }

@@ -283,7 +283,7 @@ struct Bank final : knh_bank {
     a.n_blocks = n_blocks;
     a.frame_begin = fb;
     a.frame_end = fe;
-    a.sine_table = d_sine;
+    a.sine_table = wt_lds ? reinterpret_cast<const float*>(d_wavetables) : d_sine;  // (wt_lds: an f32 bank whose wavetables are one table, at offset 0)
     a.f2pi = f2pi;
     a.sample_rate = sample_rate;
     a.seg_table = d_seg_table;
@@ -292,6 +292,7 @@ struct Bank final : knh_bank {
     a.delay_stride = delay_stride;
     a.ring_sink_row = ring_sink_row;
     a.buffer = d_buffer;
+    a.wavetables = d_wavetables;
     a.input = nullptr;
     a.in_channels = desc.in_channels;
     a.ev_start = nullptr;
@@ -319,7 +320,7 @@ struct Bank final : knh_bank {
     if (own_stream) (void)hipStreamSynchronize(own_stream);
     resolver.quiesce();
     if (flags_stream_set && flags_stream != own_stream) (void)hipStreamSynchronize(flags_stream);
-    void* dev_ptrs[] = {d_state, d_sine, d_seg_table, d_delay, d_buffer, d_partials, d_out, d_voices, d_done, d_flags, d_input, d_prog, d_sin_slots, d_fold_count};
+    void* dev_ptrs[] = {d_state, d_sine, d_seg_table, d_delay, d_buffer, d_wavetables, d_partials, d_out, d_voices, d_done, d_flags, d_input, d_prog, d_sin_slots, d_fold_count};
     for (void* p : dev_ptrs)
       if (p) (void)hipFree(p);
     void* host_ptrs[] = {h_ev_start2[0], h_ev_start2[1], h_events2[0], h_events2[1], h_out, h_input, h_done, h_rs_voices, h_rs_words, h_rs_seg};
@@ -430,6 +431,99 @@ struct Bank final : knh_bank {
     return KNH_OK;
   }
 
+  // ---- OscWt's Wavetables (KNH_STAGE_FLAG_WAVETABLE) -----------------------------------------------------------
+  // A pool per flagged stage; all of them in ONE device allocation, stage after stage, entry after entry, each entry 17
+  // tables of 16384 samples in a row or one (Wavetable::from_buffer: one table that serves as all seventeen).  `off` counts
+  // samples from the start of the allocation and is a multiple of 16384.  The host copies are staged in the entries until init.
+  // The device reads at `table word + a 14-bit index` (knh_dev::OscWtT): every table word the host writes is
+  // off + k * 16384 with k < n_tables of an entry of this list.
+  F* d_wavetables = nullptr;
+  bool wt_lds = false;  // the bank plays one f32 table and its kernel stages it to LDS in the sine table's place (init)
+  struct WtEntry { std::vector<F> samples; uint32_t n_tables = 1, off = 0; };
+  std::vector<std::vector<WtEntry>> wt_pool;   // [stage]
+  std::vector<std::vector<uint32_t>> wt_id;    // [stage][voice], empty: every voice on entry 0
+  const std::vector<WtEntry>& wt_entries(uint32_t stage) const {
+    static const std::vector<WtEntry> none;
+    return stage < wt_pool.size() ? wt_pool[stage] : none;
+  }
+  const WtEntry& wt_of(size_t stage, uint32_t v) const { return wt_pool[stage][stage < wt_id.size() && !wt_id[stage].empty() ? wt_id[stage][v] : 0u]; }
+  uint64_t wt_samples() const {
+    uint64_t total = 0;
+    for (const auto& entries : wt_pool)
+      for (const WtEntry& e : entries) total += static_cast<uint64_t>(e.n_tables) * kWavetableSize;
+    return total;
+  }
+  // the two words of a voice's OscWt that say where it reads: the partial table Wavetable::get picks for `freq`
+  // (wavetable.rs:606-609, freq.to_f32()), and the entry itself
+  static uint32_t wt_table_word(const WtEntry& e, F freq) {
+    return e.off + (e.n_tables == kWavetableTables ? wt_table_index(static_cast<float>(freq)) * kWavetableSize : 0u);
+  }
+  static uint32_t wt_entry_word(const WtEntry& e) { return e.off | (e.n_tables == kWavetableTables ? 1u : 0u); }
+  int add_wavetable(uint32_t stage, const void* samples, uint32_t n_tables, uint32_t* out_index) override {
+    if (initialised) return fail(KNH_ERR_INVALID_ARGUMENT, "knh_bank_add_wavetable comes before knh_bank_init");
+    if (stage >= stages.size() || !stages[stage].wavetable()) return fail(KNH_ERR_INVALID_ARGUMENT, "not a KNH_STAGE_FLAG_WAVETABLE stage");
+    if (!samples) return fail(KNH_ERR_INVALID_ARGUMENT, "null wavetable");
+    if (n_tables != 1 && n_tables != kWavetableTables) return fail(KNH_ERR_INVALID_ARGUMENT, "a Wavetable is 17 partial tables of 16384 samples, or 1 that serves as all of them");
+    const size_t n = static_cast<size_t>(n_tables) * kWavetableSize;
+    // a voice's table is one 32-bit slot word
+    if (wt_samples() + n > 0xFFFFFFFFull) return fail(KNH_ERR_INVALID_ARGUMENT, "the bank's wavetables would hold more than 2^32 - 1 samples");
+    WtEntry e;
+    e.samples.assign(static_cast<const F*>(samples), static_cast<const F*>(samples) + n);  // (first: nothing changes if it does not fit)
+    e.n_tables = n_tables;
+    if (wt_pool.size() < stages.size()) wt_pool.resize(stages.size());
+    wt_pool[stage].push_back(std::move(e));
+    if (out_index) *out_index = static_cast<uint32_t>(wt_pool[stage].size() - 1);
+    return KNH_OK;
+  }
+  void drop_last_wavetable(uint32_t stage) override {
+    if (!initialised && stage < wt_pool.size() && !wt_pool[stage].empty()) wt_pool[stage].pop_back();
+  }
+  uint32_t wavetable_count(uint32_t stage) const override {
+    return stage < stages.size() && stages[stage].wavetable() ? static_cast<uint32_t>(wt_entries(stage).size()) : 0u;
+  }
+  // knh_bank_assign_wavetables.  Before init: the entry each voice's OscWt is constructed on (and, with `args`, its freq).
+  // After init: the voice's node becomes a new OscWt on that entry -- every slot of the stage is patched at the first frame
+  // of the next launch, the way a parameter change is; the shadow, the constructor argument and the wrapper's smoothing follow.
+  int assign_wavetables(uint32_t stage, size_t count, const uint32_t* voices, const uint32_t* ids, const double* args) override {
+    if (stage >= stages.size() || !stages[stage].wavetable()) return fail(KNH_ERR_INVALID_ARGUMENT, "not a KNH_STAGE_FLAG_WAVETABLE stage");
+    if (count && (!voices || !ids)) return fail(KNH_ERR_INVALID_ARGUMENT, "null array");
+    if (initialised && !args) return fail(KNH_ERR_INVALID_ARGUMENT, "after knh_bank_init knh_bank_assign_wavetables needs the new oscillator's constructor argument");
+    const StageInfo& S = stages[stage];
+    const size_t n_entries = wt_entries(stage).size();
+    for (size_t k = 0; k < count; ++k) {
+      if (voices[k] >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
+      if (ids[k] >= n_entries) return fail(KNH_ERR_OUT_OF_RANGE, "wavetable index out of range");
+    }
+    if (count == 0) return KNH_OK;
+    if (wt_id.size() < stages.size()) wt_id.resize(stages.size());
+    if (wt_id[stage].empty()) wt_id[stage].assign(nv, 0u);
+    if (initialised) {
+      note_frame(frame_base);
+      pending.reserve(pending.size() + count * static_cast<size_t>(S.n_slots));
+      if (S.dcpb > 0) {  // changes still waiting in the old node's WrPreciseTiming queue went with it (as at a restart: forget_voices)
+        std::vector<uint8_t> named(nv, 0);
+        for (size_t k = 0; k < count; ++k) named[voices[k]] = 1;
+        const uint64_t ns = stages.size();
+        for (auto& recs : qfuture)
+          recs.erase(std::remove_if(recs.begin(), recs.end(), [&](const QRec& r) { return r.stage == stage && named[r.voice] && r.has_value(); }), recs.end());
+        queued.erase(std::remove_if(queued.begin(), queued.end(), [&](const std::pair<uint64_t, QueuedChange>& q) { return q.first % ns == stage && named[q.first / ns]; }), queued.end());
+      }
+    }
+    for (size_t k = 0; k < count; ++k) {
+      const uint32_t v = voices[k];
+      wt_id[stage][v] = ids[k];
+      if (args) ctor[stage][v] = args[k];
+      if (!initialised) continue;
+      if (!smooth[stage].empty()) std::fill_n(smooth[stage].begin() + static_cast<size_t>(v) * S.n_params, S.n_params, SmoothState{});
+      if (S.dcpb > 0 && !next_delay.empty())
+        for (int p = 0; p < S.n_params; ++p) next_delay[static_cast<size_t>(S.param_base + p) * nv + v] = 0;
+      (void)construct_stage(stage, v, args + k, [&](int rel, W word) {
+        pending.push_back(HostEvent{v, frame_base, knh_dev::EV_SET, static_cast<uint32_t>(S.slot_base + rel), static_cast<uint64_t>(word)});
+      });
+    }
+    return KNH_OK;
+  }
+
   // the bank node's input channels for the next launch
   F* d_input = nullptr;           // [in_blocks_cap][in_channels][block_size]
   F* h_input = nullptr;           // pinned staging of the same
@@ -505,7 +599,10 @@ struct Bank final : knh_bank {
     const StageInfo& S = stages[si];
     Shadow& sh = shadow[si];
     switch (S.kind) {
-      case KNH_STAGE_SIN_WT: sh.a.resize(nv); break;
+      case KNH_STAGE_SIN_WT:
+        sh.a.resize(nv);
+        if (S.wavetable() && wt_entries(static_cast<uint32_t>(si)).empty()) return fail(KNH_ERR_INVALID_ARGUMENT, "KNH_STAGE_FLAG_WAVETABLE stage without knh_bank_add_wavetable");
+        break;
       case KNH_STAGE_SVF: sh.a.resize(nv); sh.b.resize(nv); sh.c.resize(nv); sh.ty.resize(nv); break;
       case KNH_STAGE_MUL_ENV_ASR: case KNH_STAGE_MUL_ENV_AR: sh.a.resize(nv); sh.b.resize(nv); break;
       case KNH_STAGE_MUL_ENVELOPE: {
@@ -562,6 +659,11 @@ struct Bank final : knh_bank {
         put(0, 0);
         put(1, 0);
         put(2, sat_u32(static_cast<double>(freq) * f2pi));
+        if (S.wavetable()) {  // OscWt: init (osc.rs:82-86), then freq(a[0]) (:44-47) -- knaster_hip.h, the decision at the flag
+          const WtEntry& e = wt_of(si, v);
+          put(3, wt_table_word(e, freq));
+          put(4, wt_entry_word(e));
+        }
       } break;
       case KNH_STAGE_SIN_NUMERIC: {  // osc.rs:231-236,253-261
         F freq = static_cast<F>(a[0]);
@@ -756,6 +858,24 @@ struct Bank final : knh_bank {
     const bool f64 = sizeof(F) == 8, fma = desc.allow_fma != 0;
     knh::FormInputs in;
     in.signature = signature;
+    // Where OscWt's samples come from, decided here beside the staging of the sine table.  Staged to LDS: the voice has one
+    // flagged stage, its pool is a single one-table entry, the table is the 64 KiB of f32 the forms keep a place for (an f64
+    // table is 128 KiB: gathered) and no SinWt of the voice needs that place -- the whole bank then reads one table exactly as
+    // SinWt reads the sine table ('g' for 'M', 'h' for 'k').  Anything else, and KNH_WT_LDS=0 (A/B runs, tests): gathered from
+    // the allocation in device memory, which is always correct.
+    wt_lds = false;
+    {
+      size_t flagged = 0, at = 0;
+      for (size_t si = 0; si < stages.size(); ++si)
+        if (stages[si].wavetable()) { ++flagged; at = si; }
+      const char* const e = std::getenv("KNH_WT_LDS");
+      if (flagged == 1 && !f64 && !(e && e[0] == '0') && wt_entries(static_cast<uint32_t>(at)).size() == 1 && wt_entries(static_cast<uint32_t>(at))[0].n_tables == 1 &&
+          in.signature.find_first_of("WR") == std::string::npos) {
+        wt_lds = true;
+        std::replace(in.signature.begin(), in.signature.end(), 'M', 'g');
+        std::replace(in.signature.begin(), in.signature.end(), 'k', 'h');
+      }
+    }
     in.n_voices = nv;
     in.f64 = f64;
     in.block_size = bs;
@@ -857,6 +977,11 @@ struct Bank final : knh_bank {
     rings.clear();
     delay_len.clear();
     ring_of_stage.assign(stages.size(), -1);
+    {  // the wavetables' places in their one allocation (add_wavetable has kept the sum within 32 bits)
+      uint64_t off = 0;
+      for (auto& entries : wt_pool)
+        for (WtEntry& e : entries) { e.off = static_cast<uint32_t>(off); off += static_cast<uint64_t>(e.n_tables) * kWavetableSize; }
+    }
     for (size_t si = 0; si < stages.size(); ++si) {
       const StageInfo& S = stages[si];
       const double* ca = ctor[si].data();
@@ -886,6 +1011,14 @@ struct Bank final : knh_bank {
         KNH_HIP(hipMemcpy(d_buffer + e.off, e.samples.data(), e.samples.size() * sizeof(F), hipMemcpyHostToDevice));
         std::vector<F>().swap(e.samples);
       }
+    }
+    if (wt_samples() != 0) {
+      KNH_HIP(hipMalloc(&d_wavetables, static_cast<size_t>(wt_samples()) * sizeof(F)));
+      for (auto& entries : wt_pool)
+        for (WtEntry& e : entries) {
+          KNH_HIP(hipMemcpy(d_wavetables + e.off, e.samples.data(), e.samples.size() * sizeof(F), hipMemcpyHostToDevice));
+          std::vector<F>().swap(e.samples);
+        }
     }
     if (!rings.empty()) {
       // the sum over the delay stages of nv x the stage's stride
@@ -956,7 +1089,7 @@ struct Bank final : knh_bank {
       int n_dev = 0;
       for (size_t si = 0; si < stages.size(); ++si) {
         const StageInfo& S = stages[si];
-        const bool on = fastq(S) && dev_resolvable_kind(S.kind) && n_dev < 8 && !(de && de[0] == '0') && S.slot_base < 65536 && n_params_total < 65536;
+        const bool on = fastq(S) && dev_resolvable_kind(S.kind) && !S.wavetable() && n_dev < 8 && !(de && de[0] == '0') && S.slot_base < 65536 && n_params_total < 65536;
         ds[si] = knh_dev::DevStage{S.kind, S.dcpb, static_cast<unsigned short>(S.slot_base), static_cast<unsigned short>(S.param_base), S.flags, S.ar_param,
                                    static_cast<short>(on ? n_dev : -1), 0};
         if (on) { stage_dev[si] = 1; ++n_dev; }
@@ -1328,6 +1461,7 @@ struct Bank final : knh_bank {
     switch (S.kind) {
       case KNH_STAGE_SVF: return false;             // every setter recomputes from the three shadows
       case KNH_STAGE_BUFFER_READER: return false;   // start / duration / rate shadows
+      case KNH_STAGE_SIN_WT: return !(S.wavetable() && param == 0);  // OscWt's table word is the new freq's on the voice's entry at that block
       case KNH_STAGE_MUL_ENV_ASR: case KNH_STAGE_MUL_ENV_AR: return param >= 2;  // the times skip when unchanged (shadow); the triggers do not
       default: return true;
     }
@@ -1495,6 +1629,7 @@ struct Bank final : knh_bank {
           F freq = static_cast<F>(f);
           sh.a[v] = freq;
           set(2, sat_u32(static_cast<double>(freq) * f2pi));
+          if (S.wavetable()) set(3, wt_table_word(wt_of(stage, v), freq));  // OscWt::freq keeps self.freq: the table Wavetable::get picks moves with the increment
         } else if (param == 1) {  // osc.rs:133-135
           set(1, sat_u32(f * 65536.0));
         } else {

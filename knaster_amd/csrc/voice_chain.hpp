@@ -589,6 +589,7 @@ struct VoiceKernelArgs {
   u32 delay_stride;                 // the granule rings start on, in samples (Ctx::delay_stride)
   u32 ring_sink_row;                // the spare ring's first granule (Ctx::ring_sink_row)
   const void* buffer;               // BufferReader's pool of Buffers (single channel, F; a voice's offset and length are its slots), or null
+  const void* wavetables;           // OscWt's pools of Wavetables (every flagged stage's, one allocation of F; a voice's table and entry are its slots), or null
   const void* input;                // the bank node's input channels, [n_blocks][in_channels][block_size] of F, or null
   u32 in_channels;
   const u32* ev_start;              // [n_voices + 1] or null when the block has no events
@@ -1080,6 +1081,7 @@ __global__ void __launch_bounds__(WAVES * 64) voice_kernel(VoiceKernelArgs<F> a)
   ctx.delay_stride = a.delay_stride;
   ctx.ring_sink_row = a.ring_sink_row;
   ctx.buffer = a.buffer;
+  ctx.wavetables = a.wavetables;
   ctx.input_block = a.input;
   ctx.in_stride = a.block_size;
   ctx.sample_rate = a.sample_rate;

@@ -166,6 +166,7 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
   ctx.delay_stride = a.delay_stride;
   ctx.ring_sink_row = a.ring_sink_row;
   ctx.buffer = a.buffer;
+  ctx.wavetables = a.wavetables;
   ctx.input_block = a.input;
   ctx.in_stride = a.block_size;
   ctx.sample_rate = a.sample_rate;

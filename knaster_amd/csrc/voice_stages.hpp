@@ -108,6 +108,7 @@ struct Ctx {
   void* delay_ring;         // the delay stages' rings, one per (delay stage, voice), each contiguous: a ring starts at granule
   u32 delay_stride;         // `row` (the stage's slot 3) of the allocation, a granule being delay_stride samples of F (32: a 128-byte line or two)
   const void* buffer;       // BufferReader: the bank's pool of single-channel Buffers, samples of F (each voice's offset and length: its slots)
+  const void* wavetables;   // OscWt: the pools of Wavetables of the bank's flagged stages, one allocation, samples of F (each voice's table: its slots)
   const void* input_block;  // the bank node's input channels for the block being processed: [in_channels][in_stride] of F
   u32 in_stride;            // = block_size
   u32 sample_rate;          // ctx.sample_rate(), for setters that run on the device (audio-rate parameters)
@@ -196,6 +197,123 @@ struct SinWtT : StageDefaults {
 };
 typedef SinWtT<false> SinWt;
 typedef SinWtT<true> SinWtAr;
+
+// freq_to_table_index -- dsp/wavetable.rs:329-377: which of a Wavetable's 17 partial tables a frequency reads.  The
+// thresholds are 32 * 1.5^k, k = 0..15, every one exact in f32; the index is the number of them the f32 frequency is not
+// at or below (`f <= t` fails: a frequency on a threshold stays below it, a negative one gives 0, a NaN 16 -- the end of the
+// reference's chain of else-ifs).  Compares and adds only: exact, no libm.
+__device__ __forceinline__ u32 wt_table_index(float f) {
+  u32 n = 0;
+  n += !(f <= 32.0f);          n += !(f <= 48.0f);           n += !(f <= 72.0f);            n += !(f <= 108.0f);
+  n += !(f <= 162.0f);         n += !(f <= 243.0f);          n += !(f <= 364.5f);           n += !(f <= 546.75f);
+  n += !(f <= 820.125f);       n += !(f <= 1230.1875f);      n += !(f <= 1845.28125f);      n += !(f <= 2767.921875f);
+  n += !(f <= 4151.8828125f);  n += !(f <= 6227.82421875f);  n += !(f <= 9341.736328125f);  n += !(f <= 14012.6044921875f);
+  return n;
+}
+
+// OscWt -- knaster_core_dsp/src/ugens/osc.rs:28-87 on a Wavetable<F> (dsp/wavetable.rs:396-610): SinWt's phase arithmetic;
+// the sample is Wavetable::get(phase + phase_offset, freq) (:606-609): partial table freq_to_table_index(freq as f32),
+// entry (phase >> 16) & 16383, no interpolation.  The tables hold samples of F.  KNH_STAGE_SIN_WT with
+// KNH_STAGE_FLAG_WAVETABLE; AR_FREQ: pushed as .ar_params() with the running signal on "freq", as SinWtT<true>.
+// The Wavetables of every such stage of the bank live in one allocation (Ctx::wavetables), each a multiple of 16384 samples
+// from its start, 17 tables in a row or ONE that serves as all seventeen (Wavetable::from_buffer, :428-442).
+// slots: 0 phase, 1 phase_offset, 2 phase_increment,
+//        3 table: the first sample of the partial table in use, counted from the start of the allocation,
+//        4 entry: the first sample of the voice's Wavetable | 1 if it holds 17 tables (0: one).
+// The host writes slots 3 and 4 from entries it has checked (voice_bank.hpp) and moves increment and table together when
+// the frequency changes; under an audio-rate frequency the table is entry + index * 16384, index 0..16, on a 17-table entry.
+// Every read is at table + a 14-bit index: inside the voice's entry whatever the frequency, the phase or the input.
+template <bool AR_FREQ>
+struct OscWtT : StageDefaults {
+  static constexpr int kSlots = 5;
+  static constexpr u32 kMutableMask = AR_FREQ ? 0b01101u : 0b00001u;
+  static constexpr bool kUsesSine = false;
+  static constexpr bool kIsEnv = false;
+  static constexpr bool kNeedsBind = false;
+  static constexpr bool kHasSeg = false;
+  template <typename F> struct Regs { u32 phase, off, inc, tbl, entry; };
+  static constexpr u32 kParamMask = AR_FREQ ? 0b10010u : 0b11110u;  // phase_offset, the entry, and increment and table unless the signal drives them
+  template <typename R> static __device__ __forceinline__ void take_params(R& r, const R& n, bool c) {
+    r.off = c ? n.off : r.off;
+    r.entry = c ? n.entry : r.entry;
+    if (!AR_FREQ) { r.inc = c ? n.inc : r.inc; r.tbl = c ? n.tbl : r.tbl; }
+  }
+  template <typename F, typename W>
+  static __device__ __forceinline__ void load(Regs<F>& r, const W* s, long stride) {
+    r.phase = (u32)s[0]; r.off = (u32)s[stride]; r.inc = (u32)s[2 * stride]; r.tbl = (u32)s[3 * stride]; r.entry = (u32)s[4 * stride];
+  }
+  template <typename F, typename W>
+  static __device__ __forceinline__ void store(const Regs<F>& r, W* s, long stride) {
+    s[0] = (W)r.phase;
+    if (AR_FREQ) { s[2 * stride] = (W)r.inc; s[3 * stride] = (W)r.tbl; }
+  }
+  // OscWt::freq (osc.rs:44-47): the increment, and the table Wavetable::get will pick from self.freq
+  template <typename F>
+  static __device__ __forceinline__ void set_freq(Regs<F>& r, F v, const Ctx& c) {
+    r.inc = sat_u32((double)v * c.f2pi);
+    r.tbl = (r.entry & ~1u) + ((0u - (r.entry & 1u)) & (wt_table_index((float)v) << 14));
+  }
+  // OscWt::freq / ::phase_offset (osc.rs:50-52) applied to one sample of the driving signal
+  template <typename F, int P>
+  static __device__ __forceinline__ void ar_set(Regs<F>& r, F v, const Ctx& c) {
+    if (P == 0) set_freq<F>(r, v, c);
+    else r.off = sat_u32((double)v * 65536.0);
+  }
+  template <typename F>
+  static __device__ __forceinline__ const F* pool(const Ctx& c) { return reinterpret_cast<const F*>(c.wavetables); }
+  template <typename F, bool FMA>
+  static __device__ __forceinline__ F tick(Regs<F>& r, F x, const Ctx& c, u32, u32&) {
+    if (AR_FREQ) set_freq<F>(r, x, c);  // WrArParams::process (audio_rate.rs:42-57): param_apply(freq, x as f64) then process
+    const F s = pool<F>(c)[(size_t)r.tbl + (((r.phase + r.off) >> 16) & 16383u)];
+    r.phase += r.inc;
+    return s;
+  }
+  template <typename F, bool FMA, int T>
+  static __device__ __forceinline__ void tick_tile(Regs<F>& r, F (&x)[T], const Ctx& c, u32 frame0, u32& done_frame) {
+    // the tile's addresses first, then its reads: T independent gathers in flight, one wait
+    u32 q = r.phase + r.off;
+    u32 at[T];
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+      if constexpr (AR_FREQ) set_freq<F>(r, x[j], c);
+      at[j] = r.tbl + ((q >> 16) & 16383u);
+      q += r.inc;
+    }
+    const F* const p = pool<F>(c);
+#pragma unroll
+    for (int j = 0; j < T; ++j) x[j] = p[at[j]];
+    r.phase = q - r.off;
+  }
+  template <typename F>
+  static __device__ __forceinline__ void on_event(Regs<F>& r, u32 op, u32 rel, u64 bits, u32 /*frame*/) {
+    if ((op & 0x7Fu) != EV_SET) return;
+    switch (rel) {
+      case 0: r.phase = (u32)bits; break;
+      case 1: r.off = (u32)bits; break;
+      case 2: r.inc = (u32)bits; break;
+      case 3: r.tbl = (u32)bits; break;
+      default: r.entry = (u32)bits; break;
+    }
+  }
+};
+typedef OscWtT<false> OscWt;
+typedef OscWtT<true> OscWtAr;
+// OscWt whose bank plays ONE table: the voice has one flagged stage, that stage's pool is a single one-table entry of f32
+// samples, and no SinWt in the voice needs the sine table's place -- decided once, at init (voice_bank.hpp).  The kernel then
+// stages that table to LDS where it would stage the sine table (VoiceKernelArgs::sine_table names it) and this stage reads it
+// exactly as SinWt reads the sine table: SinWt's code, with OscWt's five slots.  The table and entry words are kept (the host
+// writes them as for the gather) and ignored: whatever the frequency, the one table is read.
+template <bool AR_FREQ>
+struct OscWtLdsT : SinWtT<AR_FREQ> {
+  static constexpr int kSlots = 5;
+  static constexpr u32 kParamMask = SinWtT<AR_FREQ>::kParamMask | 0b11000u;  // a patch of the two unused words changes nothing, at any frame
+  template <typename F>
+  static __device__ __forceinline__ void on_event(typename SinWtT<AR_FREQ>::template Regs<F>& r, u32 op, u32 rel, u64 bits, u32 frame) {
+    if (rel < 3u) SinWtT<AR_FREQ>::template on_event<F>(r, op, rel, bits, frame);
+  }
+};
+typedef OscWtLdsT<false> OscWtLds;
+typedef OscWtLdsT<true> OscWtLdsAr;
 
 // Phasor -- osc.rs:172-214: out = phase; phase += step; while phase >= 1 { phase -= 1 }.  Phase and step are f64 for
 // any F.  slots: 0,1 phase (low, high word)  2,3 step

@@ -25,6 +25,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <deque>
 #include <functional>
 #include <initializer_list>
@@ -105,6 +106,8 @@ struct UGenSpec {
   size_t buffer_frames = 0, buffer_word = 0;  // buffer_word: sizeof(F) of its samples
   uint32_t buffer_channels = 1;               // 2: interleaved frames (Buffer::from_vec_interleaved)
   double buffer_sample_rate = 0.0;
+  // OscWt: the Wavetable the node is constructed on -- `buffer` keeps it alive, buffer_samples are its 17 x 16384 samples
+  bool wavetable_ = false;
   // wrappers_core.rs:26-111
   UGenSpec wr_mul(double v) && { wrappers.emplace_back(KNH_STAGE_WR_MUL, v); return std::move(*this); }
   UGenSpec wr_add(double v) && { wrappers.emplace_back(KNH_STAGE_WR_ADD, v); return std::move(*this); }
@@ -217,6 +220,101 @@ inline UGenSpec BufferReader(std::shared_ptr<const Buffer<F>> buffer, double rat
   s.buffer = std::move(buffer);
   return s;
 }
+// Wavetable<F> -- dsp/wavetable.rs:396-610: 17 partial tables of 16384 samples, table i read at frequencies above
+// 32 * 1.5^(i - 1) up to 32 * 1.5^i (freq_to_table_index, :329-377), each holding only the harmonics that stay below 20 kHz
+// there.  The reference keeps partial_tables private, so a host cannot take the tables out of a Rust Wavetable: these are the
+// reference's builders restated, every sample computed in f64 in the reference's order and rounded by F::new.
+constexpr size_t kTableSize = 16384, kPartialTables = 17;
+// table_index_to_max_harmonic (:378-386): (20000.0 / (32. * 1.5f32.powi(i))) as usize, in f32
+constexpr size_t kMaxHarmonic[kPartialTables] = {625, 416, 277, 185, 123, 82, 54, 36, 24, 16, 10, 7, 4, 3, 2, 1, 0};
+template <typename F>
+struct Wavetable {
+  std::vector<F> tables = std::vector<F>(kPartialTables * kTableSize, F(0));  // Wavetable::new(): all zero (:412-414)
+  F* table(size_t i) { return tables.data() + i * kTableSize; }
+  const F* table(size_t i) const { return tables.data() + i * kTableSize; }
+  // Wavetable::from_buffer (:428-442): every partial table is the buffer (no anti-aliasing)
+  static Wavetable from_buffer(const std::vector<F>& buffer) {
+    if (buffer.size() != kTableSize) throw std::runtime_error("Invalid size buffer for a wavetable: wavetables must be of size 16384");
+    Wavetable w;
+    for (size_t i = 0; i < kPartialTables; ++i) std::copy(buffer.begin(), buffer.end(), w.table(i));
+    return w;
+  }
+  // Wavetable::sine (:460-466): NonAaWavetable::sine() in every table (:130-139)
+  static Wavetable sine() {
+    Wavetable w;
+    const double PI = 3.14159265358979323846;
+    for (size_t i = 0; i < kPartialTables; ++i)
+      for (size_t k = 0; k < kTableSize; ++k) w.table(i)[k] = static_cast<F>(std::sin((static_cast<double>(k) / static_cast<double>(kTableSize)) * PI * 2.0));
+    return w;
+  }
+  // add_sine (:522-528): into the tables whose harmonic limit `freq` (relative to the table) stays within; NonAaWavetable::add_sine
+  // (:219-226) steps an f64 phase
+  Wavetable& add_sine(double freq, double amplitude, double phase) {
+    const double PI = 3.14159265358979323846;
+    const double c = std::ceil(freq);
+    const size_t harmonic = c > 0.0 ? static_cast<size_t>(c) : 0u;  // `freq.ceil() as usize`
+    for (size_t i = 0; i < kPartialTables; ++i) {
+      if (harmonic > kMaxHarmonic[i]) continue;
+      const double step = (freq * PI * 2.0) / static_cast<double>(kTableSize);
+      double ph = phase;
+      F* t = table(i);
+      for (size_t k = 0; k < kTableSize; ++k) { t[k] += static_cast<F>(std::sin(ph) * amplitude); ph += step; }
+    }
+    return *this;
+  }
+  // add_saw (:545-552): harmonics start_harmonic ..= min(end_harmonic, the table's limit), if that is more than start_harmonic;
+  // NonAaWavetable::add_saw (:247-261): harmonic i (0-based) has amplitude 1 / ((i + 1) * PI)
+  Wavetable& add_saw(size_t start_harmonic, size_t end_harmonic, double amp) {
+    const double PI = 3.14159265358979323846;
+    const double len = static_cast<double>(kTableSize);
+    for (size_t i = 0; i < kPartialTables; ++i) {
+      const size_t end = std::min(end_harmonic, kMaxHarmonic[i]);
+      if (!(end > start_harmonic)) continue;
+      F* t = table(i);
+      for (size_t h = start_harmonic; h <= end; ++h) {
+        const double harmonic_amp = 1.0 / (static_cast<double>(h + 1) * PI);
+        for (size_t k = 0; k < kTableSize; ++k)
+          t[k] += static_cast<F>((std::sin(static_cast<double>(k) / len * PI * 2.0 * static_cast<double>(h + 1) + 0.0) * harmonic_amp) * amp);
+      }
+    }
+    return *this;
+  }
+  Wavetable& multiply(F mult) {  // :573-577
+    for (F& x : tables) x *= mult;
+    return *this;
+  }
+  // normalize (:579-592): by the loudest sample of table 0, the one richest in harmonics
+  Wavetable& normalize() {
+    F loudest = F(0);
+    for (size_t k = 0; k < kTableSize; ++k)
+      if (std::fabs(table(0)[k]) > loudest) loudest = std::fabs(table(0)[k]);
+    return multiply(F(1) / loudest);
+  }
+  // every partial table the same samples (from_buffer, sine): the bank stores one
+  bool single() const {
+    for (size_t i = 1; i < kPartialTables; ++i)
+      if (std::memcmp(table(0), table(i), kTableSize * sizeof(F)) != 0) return false;
+    return true;
+  }
+};
+// OscWt on a Wavetable -- osc.rs:28-87.  The reference has no OscWt::new at the surveyed commit: here the node is made from its
+// Wavetable and a frequency, applied as freq() right after init (knaster_hip.h, the decision at KNH_STAGE_FLAG_WAVETABLE).
+// Parameters "freq", "phase_offset", "reset_phase".  Voices of one chain shape share a bank whatever Wavetable each was made
+// on: the stage's pool holds every distinct one once (knh_bank_add_wavetable), each voice plays its own.  Oscillators that are
+// to share a Wavetable take the same shared_ptr; the by-value form makes a copy of its own, as the reference's owned field is.
+template <typename F>
+inline UGenSpec OscWt(std::shared_ptr<const Wavetable<F>> wavetable, double freq) {
+  if (!wavetable || wavetable->tables.size() != kPartialTables * kTableSize) throw std::runtime_error("OscWt needs a Wavetable of 17 x 16384 samples");
+  UGenSpec s(KNH_STAGE_SIN_WT, {freq});
+  s.wavetable_ = true;
+  s.buffer_samples = wavetable->tables.data();
+  s.buffer_word = sizeof(F);
+  s.buffer = std::move(wavetable);
+  return s;
+}
+template <typename F>
+inline UGenSpec OscWt(const Wavetable<F>& wavetable, double freq) { return OscWt<F>(std::make_shared<const Wavetable<F>>(wavetable), freq); }
+
 inline UGenSpec Constant(double value) { UGenSpec s(KNH_STAGE_MUL_CONST, {value}); s.is_constant = true; return s; }
 
 struct GraphError : std::runtime_error { using std::runtime_error::runtime_error; };
@@ -522,6 +620,7 @@ class Graph {
       if (!source) input = in_of(trace(n.in0, p, visited, done));
     }
     if (s.smooth_params_) flags |= KNH_STAGE_FLAG_SMOOTH_PARAMS;
+    if (s.wavetable_) flags |= KNH_STAGE_FLAG_WAVETABLE;  // OscWt: SIN_WT on a Wavetable of the stage's pool
     push_stage(p, s.kind, flags, s.precise_timing_, node, s.args, input, ar.second, ar.first);
     if (s.kind == KNH_STAGE_BUFFER_READER && s.outputs == 2) {
       // BufferReader<F, U2>: the node's second output is a stage of its own that names the reader stage
@@ -677,6 +776,28 @@ class Graph {
             ids.push_back(static_cast<uint32_t>(id));
           }
           check(b, knh_bank_assign_buffers(b.h, static_cast<uint32_t>(s), vs.size(), vs.data(), ids.data(), nullptr));
+        }
+        for (size_t s = 0; s < b.plan.stages.size(); ++s) {
+          // OscWt voices: every distinct Wavetable once in the stage's pool, in order of first appearance (one whose partial
+          // tables are all alike is stored as one table); each voice on its own
+          if (b.plan.stages[s].kind != KNH_STAGE_SIN_WT || !(b.plan.stages[s].flags & KNH_STAGE_FLAG_WAVETABLE)) continue;
+          std::vector<const void*> pooled;
+          std::vector<uint32_t> vs, ids;
+          for (size_t vi = 0; vi < members.size(); ++vi) {
+            const UGenSpec& spec = nodes_[static_cast<size_t>(voices[members[vi]].plan.stage_node[s])].spec;
+            if (!spec.buffer_samples || spec.buffer_word != sizeof(F)) throw GraphError("OscWt: its Wavetable must hold samples of the graph's type");
+            size_t id = static_cast<size_t>(std::find(pooled.begin(), pooled.end(), spec.buffer_samples) - pooled.begin());
+            if (id == pooled.size()) {
+              uint32_t index = 0;
+              const bool single = static_cast<const Wavetable<F>*>(spec.buffer.get())->single();
+              check(b, knh_bank_add_wavetable(b.h, static_cast<uint32_t>(s), spec.buffer_samples, single ? 1u : static_cast<uint32_t>(kPartialTables), &index));
+              pooled.push_back(spec.buffer_samples);
+              id = index;
+            }
+            vs.push_back(static_cast<uint32_t>(vi));
+            ids.push_back(static_cast<uint32_t>(id));
+          }
+          check(b, knh_bank_assign_wavetables(b.h, static_cast<uint32_t>(s), vs.size(), vs.data(), ids.data(), nullptr));
         }
         // UGen::init runs at push time in the reference (graph.rs:462-475); the bank's voices all init here
         check(b, knh_bank_init(b.h, sample_rate_, block_size_));
