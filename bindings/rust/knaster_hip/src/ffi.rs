@@ -135,6 +135,7 @@ pub const KNH_STAGE_FLAG_AR_FREQ: u16 = 1 << 0;
 pub const KNH_STAGE_FLAG_SMOOTH_PARAMS: u16 = 1 << 1;
 pub const KNH_STAGE_FLAG_READER_CH1: u16 = 1 << 2;
 pub const KNH_STAGE_FLAG_WAVETABLE: u16 = 1 << 3;
+pub const KNH_STAGE_FLAG_ENV_SOURCE: u16 = 1 << 4;
 
 // knh_mix_mode
 pub const KNH_MIX_TREE: u32 = 0;

@@ -335,7 +335,31 @@ enum {
    * per sample) and 2 (phase_offset), input / input2, knh_bank_connect_outputs, following KNH_STAGE_WR_* stages, Pan2 or
    * Galactic at the end, restart, host-sharded / multi-device / rank banks.  A voice may hold several such stages, each with
    * a pool of its own.  A voice with such a stage is fused at knh_bank_init (no pre-built kernel, never a lane per frame). */
-  KNH_STAGE_FLAG_WAVETABLE = 1u << 3
+  KNH_STAGE_FLAG_WAVETABLE = 1u << 3,
+  /* kind = KNH_STAGE_MUL_ENV_ASR, KNH_STAGE_MUL_ENV_AR or KNH_STAGE_MUL_ENVELOPE with this flag: the envelope ALONE --
+   * g.push(EnvAsr::new(a, r)) (envelopes.rs:19-163), g.push(EnvAr::new(a, r)) (:174-303), g.push(Envelope) (:359-527) -- a
+   * node with no inputs and one output, its signal a signal of the voice.  Without the flag the kind stands for
+   * `x * g.push(EnvAsr::new(..))`, two nodes; with it the stage is ONE node (knh_chain_ugen_count counts 1) whose output is the
+   * envelope's sample, with no multiply.  On any other kind: KNH_ERR_INVALID_ARGUMENT at knh_bank_create.
+   * It is a SOURCE: it reads no signal (input must be 0: KNH_ERR_INVALID_ARGUMENT), it starts a new signal of the voice and
+   * may be stage 0; a source after stage 0 makes the voice a graph, as for every other source.  Constructor arguments,
+   * parameters and their indices, value kinds, delayed_changes_per_block, KNH_STAGE_FLAG_SMOOTH_PARAMS and the supported
+   * ar_param values (attack_time, release_time / time_scale, driven by input2; input2 without ar_param is refused) are
+   * exactly those of the multiplying form of the same kind; so are knh_bank_restart_voices and the limit of one
+   * KNH_STAGE_MUL_ENVELOPE per voice, in either form.  KNH_STAGE_WR_* stages behind it wrap the envelope node itself
+   * (EnvAsr::new(..).wr_mul(3000.).wr_add(200.)): whoever reads "the output of stage k" gets the last wrapper's output, as
+   * for every node.  That output may be the `input` of any stage, an operand of KNH_STAGE_MATH_*, the running signal of a
+   * SIN_WT | AR_FREQ, the input2 of any supported ar_param (a link, graph_edit.rs:735-754: the filter, pitch and index
+   * envelopes of a subtractive or FM voice), either input of Galactic, either output of knh_bank_connect_outputs.
+   * Refused with KNH_ERR_INVALID_ARGUMENT: the flag together with KNH_STAGE_FLAG_AR_FREQ, _READER_CH1 or _WAVETABLE.
+   * mark_done works as in the reference: the source marks the voice's done frame exactly as the multiplying form does
+   * (the partial-block origin under WrPreciseTiming included), and takes its place among the envelopes in the task order.
+   * THE RULE for KNH_FLAG_ALL_DONE and the "running" counts: they describe SILENCE, so only a stage that can silence the
+   * voice takes part -- a multiplying envelope or a one-shot reader.  A stage with this flag is skipped: a voice whose filter
+   * envelope has run out while its amplitude envelope sounds is running; a voice whose only finishing stages are envelope
+   * sources never reports KNH_FLAG_ALL_DONE (its done frames and KNH_FLAG_ANY_DONE are still reported).
+   * A voice with such a stage is fused at knh_bank_init (no pre-built kernel, never a lane per frame). */
+  KNH_STAGE_FLAG_ENV_SOURCE = 1u << 4
 };
 
 typedef struct knh_stage_desc {

@@ -254,7 +254,7 @@ int32_t knh_chain_ugen_count(const knh_stage_desc* stages, uint32_t n_stages) {
     if (!stages) return 0;
     int n = 0;
     for (uint32_t i = 0; i < n_stages; ++i)
-      if (stages[i].kind < KNH_STAGE_KIND_COUNT && !is_reader_ch1(stages[i])) n += kKinds[stages[i].kind].n_nodes;  // (a reader's second output is the reader)
+      if (stages[i].kind < KNH_STAGE_KIND_COUNT && !is_reader_ch1(stages[i])) n += stage_nodes(stages[i].kind, stages[i].flags);  // (a reader's second output is the reader; an envelope source is one node)
     return n;
   });
 }

@@ -43,11 +43,17 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     const bool source = !ch1 && (st[i].kind == KNH_STAGE_SIN_WT || st[i].kind == KNH_STAGE_SIN_NUMERIC || st[i].kind == KNH_STAGE_PHASOR ||
                         st[i].kind == KNH_STAGE_WHITE_NOISE || st[i].kind == KNH_STAGE_PINK_NOISE || st[i].kind == KNH_STAGE_BROWN_NOISE ||
                         st[i].kind == KNH_STAGE_RANDOM_LIN ||
-                        st[i].kind == KNH_STAGE_POLYBLEP || st[i].kind == KNH_STAGE_BUFFER_READER || st[i].kind == KNH_STAGE_INPUT);
+                        st[i].kind == KNH_STAGE_POLYBLEP || st[i].kind == KNH_STAGE_BUFFER_READER || st[i].kind == KNH_STAGE_INPUT ||
+                        is_env_source(st[i].kind, st[i].flags));
+    const bool env_src = is_env_source(st[i].kind, st[i].flags);  // the envelope alone: 'b' 'j' 'l' for 'A' 'E' 'V'
     const bool ar = st[i].kind == KNH_STAGE_SIN_WT && (st[i].flags & KNH_STAGE_FLAG_AR_FREQ);
     const bool wt = st[i].kind == KNH_STAGE_SIN_WT && (st[i].flags & KNH_STAGE_FLAG_WAVETABLE);  // OscWt: 'M' for 'W', 'k' for 'R'
     const bool math2 = is_math2_kind(st[i].kind);
-    if (st[i].flags & ~(KNH_STAGE_FLAG_AR_FREQ | KNH_STAGE_FLAG_SMOOTH_PARAMS | KNH_STAGE_FLAG_READER_CH1 | KNH_STAGE_FLAG_WAVETABLE)) { *why = "unknown stage flag"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (st[i].flags & ~(KNH_STAGE_FLAG_AR_FREQ | KNH_STAGE_FLAG_SMOOTH_PARAMS | KNH_STAGE_FLAG_READER_CH1 | KNH_STAGE_FLAG_WAVETABLE | KNH_STAGE_FLAG_ENV_SOURCE)) { *why = "unknown stage flag"; return KNH_ERR_INVALID_ARGUMENT; }
+    if ((st[i].flags & KNH_STAGE_FLAG_ENV_SOURCE) && !is_env_kind(st[i].kind)) { *why = "ENV_SOURCE is only defined for MUL_ENV_ASR, MUL_ENV_AR and MUL_ENVELOPE"; return KNH_ERR_INVALID_ARGUMENT; }
+    if ((st[i].flags & KNH_STAGE_FLAG_ENV_SOURCE) && (st[i].flags & (KNH_STAGE_FLAG_AR_FREQ | KNH_STAGE_FLAG_READER_CH1 | KNH_STAGE_FLAG_WAVETABLE))) { *why = "ENV_SOURCE cannot be combined with AR_FREQ, READER_CH1 or WAVETABLE"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (env_src && st[i].input != 0) { *why = "an ENV_SOURCE stage is a source: it reads no signal (input = 0)"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (env_src && st[i].input2 != 0 && st[i].ar_param == 0) { *why = "input2 of an ENV_SOURCE stage is the driver of an audio-rate parameter: it needs ar_param"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((st[i].flags & KNH_STAGE_FLAG_WAVETABLE) && st[i].kind != KNH_STAGE_SIN_WT) { *why = "WAVETABLE is only defined for SIN_WT"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((st[i].flags & KNH_STAGE_FLAG_SMOOTH_PARAMS) && (st[i].flags & KNH_STAGE_FLAG_AR_FREQ)) { *why = "SMOOTH_PARAMS and AR_FREQ cannot be combined"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((st[i].flags & KNH_STAGE_FLAG_SMOOTH_PARAMS) && is_wrapper_kind(st[i].kind)) { *why = "SMOOTH_PARAMS applies to a node, not to a wrapper stage"; return KNH_ERR_INVALID_ARGUMENT; }
@@ -71,7 +77,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       *why = "a voice holds at most KNH_MAX_DELAY_STAGES delay stages";
       return KNH_ERR_UNSUPPORTED_CHAIN;
     }
-    if (st[i].kind == KNH_STAGE_MUL_ENVELOPE && sig->find('V') != std::string::npos) { *why = "at most one Envelope stage per chain"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (st[i].kind == KNH_STAGE_MUL_ENVELOPE && sig->find_first_of("Vl") != std::string::npos) { *why = "at most one Envelope stage per chain"; return KNH_ERR_INVALID_ARGUMENT; }
     if (st[i].kind == KNH_STAGE_PAN2 && i + 1 != n) { *why = "Pan2 ends the chain: it must be the last stage"; return KNH_ERR_INVALID_ARGUMENT; }
     if (st[i].kind == KNH_STAGE_PAN2 && st[i].delayed_changes_per_block > 0) { *why = "Pan2 cannot be wrapped in WrPreciseTiming here (its gains change at block boundaries)"; return KNH_ERR_INVALID_ARGUMENT; }
     if (st[i].kind == KNH_STAGE_GALACTIC) {  // the reverb ends a chain of its own kind (galactic_bank.hpp)
@@ -97,7 +103,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       if (kKinds[st[i].kind].sig == 'I' || st[st[i].input2 - 1].kind == KNH_STAGE_INPUT) { *why = "an audio-rate parameter edge starts at a node, not at a bank input (put the input through `* 1.0`)"; return KNH_ERR_INVALID_ARGUMENT; }
     }
     // ('T': a reader with two outputs; '2': its second output, which is no device stage and leaves the signature below)
-    sig->push_back(wt ? (ar ? 'k' : 'M') : ar ? 'R' : ch1 ? '2' : (st[i].kind == KNH_STAGE_BUFFER_READER && companion[i] >= 0) ? 'T' : kKinds[st[i].kind].sig);
+    sig->push_back(env_src ? env_source_sig(st[i].kind) : wt ? (ar ? 'k' : 'M') : ar ? 'R' : ch1 ? '2' : (st[i].kind == KNH_STAGE_BUFFER_READER && companion[i] >= 0) ? 'T' : kKinds[st[i].kind].sig);
     have_x = true;
   }
   // A voice that is a graph (a stage that names its operands, a MathUGen of two signals, a second source): every stage is
@@ -111,7 +117,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     uint32_t sources = 0;
     for (uint32_t i = 0; i < n; ++i) {
       const bool ar = st[i].kind == KNH_STAGE_SIN_WT && (st[i].flags & KNH_STAGE_FLAG_AR_FREQ);
-      sources += std::strchr("WNPUKOGBFI", kKinds[st[i].kind].sig) != nullptr && !ar && !is_reader_ch1(st[i]);
+      sources += (std::strchr("WNPUKOGBFI", kKinds[st[i].kind].sig) != nullptr || is_env_source(st[i].kind, st[i].flags)) && !ar && !is_reader_ch1(st[i]);
       dag = dag || is_math2_kind(st[i].kind) || (st[i].input != 0 && st[i].input != i) || st[i].ar_param != 0 || is_reader_ch1(st[i]);
     }
     dag = dag || sources > 1;
@@ -133,7 +139,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       return k;
     };
     for (uint32_t i = 0; i < n; ++i) {
-      const bool reads = i > 0 && !(std::strchr("WMNPUKOGBFIT2", (*sig)[i]) != nullptr);  // 'R' reads, the plain sources do not (nor does a reader's second output: it IS the reader)
+      const bool reads = i > 0 && !(std::strchr("WMNPUKOGBFIT2bjl", (*sig)[i]) != nullptr);  // 'R' reads, the plain sources do not (nor does a reader's second output: it IS the reader)
       if (is_math2_kind(st[i].kind)) { a[i] = node_output(st[i].input - 1); b[i] = node_output(st[i].input2 - 1); }
       else if (reads) a[i] = st[i].input ? node_output(st[i].input - 1) : static_cast<int>(i) - 1;
       if (st[i].ar_param != 0) b[i] = node_output(st[i].input2 - 1);  // the signal that drives the parameter
@@ -267,7 +273,7 @@ bool parse_frame_program(const std::string& signature, const std::vector<StageIn
 uint64_t envelope_task_ranks(const std::string& signature, const std::vector<StageInfo>& stages, const uint32_t* outs = nullptr) {
   if (!signature_is_dag(signature)) return 0;
   const int n = static_cast<int>(stages.size());
-  auto is_src = [&](int i) { return std::strchr("WNPUKOGBFI", kKinds[stages[i].kind].sig) != nullptr && !(stages[i].flags & KNH_STAGE_FLAG_AR_FREQ); };
+  auto is_src = [&](int i) { return (std::strchr("WNPUKOGBFI", kKinds[stages[i].kind].sig) != nullptr || stages[i].env_source()) && !(stages[i].flags & KNH_STAGE_FLAG_AR_FREQ); };
   auto node_output = [&](int k) { while (k + 1 < n && is_wrapper_kind(stages[k + 1].kind)) ++k; return k; };
   std::vector<int> a(n, -1), b(n, -1);
   for (int i = 0; i < n; ++i) {
@@ -336,9 +342,10 @@ uint64_t envelope_task_ranks(const std::string& signature, const std::vector<Sta
 }
 
 // The chain has a stage that can end a voice: without one ALL_DONE is never reported (a chain without an envelope never finishes).
+// ALL_DONE describes silence: an envelope that is a source (KNH_STAGE_FLAG_ENV_SOURCE) silences nothing and does not count.
 bool chain_can_finish(const std::vector<StageInfo>& stages) {
   for (const StageInfo& st : stages)
-    if (st.kind == KNH_STAGE_MUL_ENV_ASR || st.kind == KNH_STAGE_MUL_ENV_AR || st.kind == KNH_STAGE_MUL_ENVELOPE || st.kind == KNH_STAGE_BUFFER_READER) return true;
+    if ((is_env_kind(st.kind) && !st.env_source()) || st.kind == KNH_STAGE_BUFFER_READER) return true;
   return false;
 }
 // A block's done / running voice counts -> the flags of knh_bank_process_block.

@@ -6,6 +6,8 @@
 //     (neither has a pre-built kernel: a voice with one is fused at init)
 //   g, h: M, k of a bank whose one f32 table is staged to LDS in the sine table's place (decided at init, voice_bank.hpp)
 //   S SvfFilter   L OnePoleLpf   H OnePoleHpf   A x*EnvAsr   E x*EnvAr   V x*Envelope (segments)   D SampleDelay   P Phasor   X SafetyLimiter   B PolyBlep   Y AllpassDelay   Z AllpassFeedbackDelay   F BufferReader   U WhiteNoise   K PinkNoise   O BrownNoise   G RandomLin
+//   b EnvAsr   j EnvAr   l Envelope (segments): the envelope ALONE, a source of the voice (KNH_STAGE_FLAG_ENV_SOURCE on the kinds of
+//     A, E, V; no pre-built kernel: a voice with one is fused at init)
 //   Q Galactic (last stage only: the stereo reverb; never part of a fused kernel -- galactic_bank.hpp runs the chain before it
 //     through one of the kernels below and the reverb in kernels_galactic.hip)
 //   J Pan2 (last stage only: two output channels)   I an input channel of the bank node (a source shared by all voices)

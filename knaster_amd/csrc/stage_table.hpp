@@ -61,6 +61,12 @@ const KindInfo kKinds[KNH_STAGE_KIND_COUNT] = {
     /* MATH1_FRACT */ {0, 0, 0, 1, 'w', {nullptr}},
     /* MATH1_EXP   */ {0, 0, 0, 1, 'e', {nullptr}},
 };
+inline bool is_env_kind(uint16_t kind) { return kind == KNH_STAGE_MUL_ENV_ASR || kind == KNH_STAGE_MUL_ENV_AR || kind == KNH_STAGE_MUL_ENVELOPE; }
+// The envelope alone, a source (KNH_STAGE_FLAG_ENV_SOURCE on an envelope kind): one node, not the two of `x * env`; its
+// signature characters are 'b' (EnvAsr), 'j' (EnvAr), 'l' (Envelope) for 'A', 'E', 'V'.
+inline bool is_env_source(uint16_t kind, uint16_t flags) { return is_env_kind(kind) && (flags & KNH_STAGE_FLAG_ENV_SOURCE); }
+inline char env_source_sig(uint16_t kind) { return kind == KNH_STAGE_MUL_ENV_ASR ? 'b' : kind == KNH_STAGE_MUL_ENV_AR ? 'j' : 'l'; }
+inline int stage_nodes(uint16_t kind, uint16_t flags) { return is_env_source(kind, flags) ? 1 : kKinds[kind].n_nodes; }
 inline bool is_math2_kind(uint16_t kind) { return kind >= KNH_STAGE_MATH_ADD && kind <= KNH_STAGE_MATH_POW; }
 inline bool is_math1_kind(uint16_t kind) { return kind >= KNH_STAGE_MATH1_CEIL && kind <= KNH_STAGE_MATH1_EXP; }
 // A voice that is a graph rather than a chain: explicit operands, a MathUGen of two signals, or a second source.
@@ -86,7 +92,7 @@ bool interp_can_run(const knh_stage_desc* st, uint32_t n) {
 inline int stage_cost(char c) {
   switch (c) {
     case 'W': return 7;  case 'R': return 10; case 'M': return 9; case 'k': return 30; case 'g': return 7; case 'h': return 10; case 'N': return 25; case 'S': return 10; case 'L': return 3;
-    case 'H': return 4;  case 'A': return 5;  case 'E': return 5;  case 'V': return 14; case 'D': return 12;
+    case 'H': return 4;  case 'A': return 5;  case 'E': return 5;  case 'V': return 14; case 'b': return 4; case 'j': return 4; case 'l': return 13; case 'D': return 12;
     case 'd': case 'q': return 8;  case 'p': return 40; case 'i': return 10; case 'P': return 6; case 'U': return 14; case 'O': return 19; case 'K': return 50; case 'G': return 10; case 'X': return 4; case 'B': return 45; case 'Y': return 14; case 'Z': return 18; case 'F': case 'C': return 16;  // ('C': the mono reader on a two-channel pool, the same work)
     case 'r': return 12; case 'e': return 20;  // Math1: the correctly rounded sqrt sequence, the device library's exp (ceil floor trunc fract: 1-2)
     default: return 1;
@@ -238,6 +244,8 @@ struct StageInfo {
   bool ch1() const { return kind == KNH_STAGE_BUFFER_READER && (flags & KNH_STAGE_FLAG_READER_CH1); }
   // OscWt on a Wavetable of the stage's pool (KNH_STAGE_SIN_WT with KNH_STAGE_FLAG_WAVETABLE): two more slots, the table in use and the voice's entry
   bool wavetable() const { return kind == KNH_STAGE_SIN_WT && (flags & KNH_STAGE_FLAG_WAVETABLE); }
+  // the envelope alone, a source of the voice (KNH_STAGE_FLAG_ENV_SOURCE): same slots, parameters and constructor arguments as `x * env`
+  bool env_source() const { return is_env_source(kind, flags); }
 };
 const char kCh1NoParams[] = "a KNH_STAGE_FLAG_READER_CH1 stage is the second output of a BufferReader, not a node: it has no parameters (address the reader stage)";
 inline bool is_reader_ch1(const knh_stage_desc& d) { return d.kind == KNH_STAGE_BUFFER_READER && (d.flags & KNH_STAGE_FLAG_READER_CH1); }

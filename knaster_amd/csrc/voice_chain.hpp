@@ -147,7 +147,7 @@ struct Chain<F, FMA, BASE, S0, Rest...> {
     else rest.on_event(op, slot, bits, frame);
   }
   __device__ __forceinline__ bool last_env_stopped(bool dflt) const {
-    if constexpr (S0::kIsEnv) return rest.last_env_stopped(S0::template is_stopped<F>(r));
+    if constexpr (S0::kIsEnv && !S0::kEnvSource) return rest.last_env_stopped(S0::template is_stopped<F>(r));  // (an envelope source silences nothing)
     else return rest.last_env_stopped(dflt);
   }
   __device__ __forceinline__ void begin_block(u32 frame_begin, const Ctx& c) {
@@ -380,7 +380,7 @@ struct DagChain<F, FMA, BASE, R, LAST, N0, Rest...> {
     else rest.on_event(op, slot, bits, frame);
   }
   __device__ __forceinline__ bool last_env_stopped(bool dflt) const {
-    if constexpr (S0::kIsEnv) return rest.last_env_stopped(S0::template is_stopped<F>(r));
+    if constexpr (S0::kIsEnv && !S0::kEnvSource) return rest.last_env_stopped(S0::template is_stopped<F>(r));  // (an envelope source silences nothing)
     else return rest.last_env_stopped(dflt);
   }
   __device__ __forceinline__ void begin_block(u32 frame_begin, const Ctx& c) {

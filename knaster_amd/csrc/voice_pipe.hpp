@@ -28,6 +28,7 @@ template <typename... S> struct GroupInfo<Group<S...>> {
   static constexpr bool uses_sine = (false || ... || S::kUsesSine);
   static constexpr bool uses_ring = (false || ... || S::kUsesRing);  // a delay: the group's wavefront moves ring tiles as lines (RingLines)
   static constexpr bool has_env = (false || ... || S::kIsEnv);
+  static constexpr bool has_silencer = (false || ... || (S::kIsEnv && !S::kEnvSource));  // an envelope or reader that can end the voice's sound (not an envelope source)
   static constexpr bool pan = (false || ... || IsPan<S>::value);  // the group ends the chain with a Pan2
   static constexpr int fan_for(int) { return 1; }
 };
@@ -36,6 +37,7 @@ template <int K, typename... S> struct GroupInfo<Fan<K, S...>> {
   static constexpr bool uses_sine = (false || ... || S::kUsesSine);
   static constexpr bool uses_ring = false;
   static constexpr bool has_env = false;
+  static constexpr bool has_silencer = false;
   static constexpr bool pan = false;
   // wavefronts for tiles of T samples: K, or as many as leave every one a window of eight samples (f64 tiles are shorter)
   static constexpr int fan_for(int T) { return K * 8 <= T ? K : (T >= 8 ? T / 8 : 1); }
@@ -132,7 +134,7 @@ __device__ __forceinline__ void pipe_fold_tile(const F* tile, const VoiceKernelA
                                                int blk, u32 n0, u32 len, u32 v0, u32 nv, u32 res_tile = 0u, u32 res_epoch = 0u);
 
 // One stage group = one wavefront.  I: group index, NG: number of chain groups (mixer excluded),
-// LAST_ENV: index of the group holding the chain's last envelope stage (-1: none).
+// LAST_ENV: index of the group holding the chain's last envelope stage that can silence the voice (-1: none).
 // MODE PIPE_FOLD: the last group also folds its tile over the voices (what pipe_run_mixer does in a wavefront of its own
 // otherwise): it stores the tile in a buffer no other wavefront touches and reads it back column-wise.
 template <typename F, bool FMA, int T, int MODE, int NG, int I, int BASE, int LAST_ENV, typename G>
@@ -594,8 +596,9 @@ __device__ __forceinline__ void pipe_fold_tile(const F* tile, const VoiceKernelA
 
 // The mixer wavefront: folds the tile the last chain group finished in the previous step.  In a resident launch it also takes
 // the workgroup's row to the fold server as granules and, with a call's last tile, reports the call's done marks
-// and flags.  CHAINW = wavefronts that run stage groups; HAS_ENV: some group holds an envelope.
-template <typename F, bool FMA, int T, int MODE, int NG, bool PAN, int CHAINW, bool HAS_ENV>
+// and flags.  CHAINW = wavefronts that run stage groups; HAS_ENV: bit 0 some group holds an envelope (done marks), bit 1 one of them
+// can silence the voice (a running flag; an envelope source cannot).
+template <typename F, bool FMA, int T, int MODE, int NG, bool PAN, int CHAINW, int HAS_ENV>
 __device__ __forceinline__ void pipe_run_mixer(const PipeShared<F>& sh, const VoiceKernelArgs<F>& a, int lane, u32 wave_global,
                                                u32 v0, u32 nv, int wave_all) {
   u32 fbeg = a.frame_begin, fend = a.frame_end;
@@ -649,7 +652,7 @@ __device__ __forceinline__ void pipe_run_mixer(const PipeShared<F>& sh, const Vo
           const bool live = (u32)lane < nv;
           if (live) a.done_frames[v0 + lane] = d;
           n_done = (u32)__builtin_popcountll(__builtin_amdgcn_ballot_w64(live && d != 0xFFFFFFFFu));
-          n_run = (u32)__builtin_popcountll(__builtin_amdgcn_ballot_w64(live && sh.res_marks[15 * 64 + lane] != 0u));
+          if (HAS_ENV & 2) n_run = (u32)__builtin_popcountll(__builtin_amdgcn_ballot_w64(live && sh.res_marks[15 * 64 + lane] != 0u));
         }
         if (lane == 0) res_put(a.res.wg_flags + wave_global, n_done | (n_run << 8), res_tag(call.epoch, 255u));
       }
@@ -688,7 +691,7 @@ template <int I, typename... Gs> struct LastEnv;
 template <int I> struct LastEnv<I> { static constexpr int value = -1; };
 template <int I, typename G, typename... Rest> struct LastEnv<I, G, Rest...> {
   static constexpr int later = LastEnv<I + 1, Rest...>::value;
-  static constexpr int value = later >= 0 ? later : (GroupInfo<G>::has_env ? I : -1);
+  static constexpr int value = later >= 0 ? later : (GroupInfo<G>::has_silencer ? I : -1);
 };
 
 // One workgroup = GPW x 64 voices; per 64-voice group one wavefront per stage group (K for a Fan group) + the mixer, or
@@ -812,7 +815,7 @@ __global__ void __launch_bounds__((GPW * PipeWaves<T, MODE, Gs...>::value * 64))
     const int n_steps = (int)((n_frames + T - 1) / T) * (int)a.n_blocks + NG - (MODE == PIPE_FOLD ? 1 : 0);
     for (int s = 0; s < n_steps; ++s) pipe_barrier();
   } else if (wave == CHAINW) {
-    constexpr bool kAnyEnvM = (false || ... || GroupInfo<Gs>::has_env);
+    constexpr int kAnyEnvM = ((false || ... || GroupInfo<Gs>::has_env) ? 1 : 0) | (LastEnv<0, Gs...>::value >= 0 ? 2 : 0);  // 1: done marks, 2: a running flag
     pipe_run_mixer<F, FMA, T, MODE, NG, kPan, CHAINW, kAnyEnvM>(sh, a, lane, wave_global, v0, nv, wave_all);
   } else {
     done_frame = pipe_dispatch<F, FMA, T, MODE, NG, 0, 0, 0, LastEnv<0, Gs...>::value, Gs...>(wave, sh, a, lane, wave_global, v0, nv, wave_all);

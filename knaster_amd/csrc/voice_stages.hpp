@@ -80,6 +80,9 @@ struct StageDefaults {
   // pipeline evaluates prepare_run once per quiet run of tiles (voice_pipe.hpp: consecutive tiles with no event applied
   // between them) and hands the result to tick_tile_prepared for each tile of the run.  Only Svf has one.
   static constexpr bool kHasRunPrep = false;
+  // An envelope that is a SOURCE of the voice (KNH_STAGE_FLAG_ENV_SOURCE): it marks done like any envelope (kIsEnv), but it
+  // silences nothing, so "the voice's last envelope has stopped" (ALL_DONE, the running counts) passes it by.
+  static constexpr bool kEnvSource = false;
 };
 // A stage whose parameter P is driven at audio rate by another signal of the voice (graph-shaped voices: DagChain reads the
 // driver through the stage's second operand and calls S::ar_set<F, P> in front of every sample).  What the setter of each
@@ -1686,57 +1689,16 @@ struct MulEnvT : StageDefaults {
   static __device__ __forceinline__ F tick(Regs<F>& r, F x, const Ctx&, u32 frame, u32& done_frame) {
     return x * env_next<F>(r, frame, done_frame);
   }
-  // T envelope samples at once.  State transitions are rare (at most three per note), so the tile is
-  // first evaluated branch-free under the assumption that no lane changes state inside it; every
-  // sample's transition test is still evaluated, and if any lane would have changed state the tile is
-  // redone with the exact per-sample state machine from the untouched registers.  Same values either way.
-  template <typename F, int T>
-  static __device__ __forceinline__ void env_tile(Regs<F>& r, F (&e)[T], u32 frame0, u32& done_frame) {
-    const u32 st = r.state;
-    const bool isA = st == 1u, isR = st == 3u;
-    const bool anyA = __builtin_amdgcn_ballot_w64(isA) != 0, anyR = __builtin_amdgcn_ballot_w64(isR) != 0;
-    const F konst = st == 2u ? (F)1 : (F)0;
-    if (!anyA && !anyR) {  // every lane Sustaining or Stopped
-#pragma unroll
-      for (int j = 0; j < T; ++j) e[j] = konst;
-      return;
-    }
-    const F step = isA ? r.ar : (isR ? -r.rr : (F)0);  // t - rr == t + (-rr) exactly
-    F t = r.t;
-    bool hit_hi = false, hit_lo = false;
-    if (!anyR) {
-#pragma unroll
-      for (int j = 0; j < T; ++j) {
-        e[j] = isA ? t : konst;
-        t = t + step;
-        hit_hi |= t >= (F)1;
-      }
-    } else {
-      const F scale = r.scale;
-#pragma unroll
-      for (int j = 0; j < T; ++j) {
-        const F cube = (t * (t * t)) * scale;
-        e[j] = isA ? t : (isR ? cube : konst);
-        t = t + step;
-        hit_hi |= t >= (F)1;
-        hit_lo |= t <= (F)0;
-      }
-    }
-    const bool hit = (isA && hit_hi) || (isR && hit_lo);
-    if (__builtin_amdgcn_ballot_w64(hit) == 0) {
-      r.t = t;
-      return;
-    }
-#pragma unroll
-    for (int j = 0; j < T; ++j) e[j] = env_next<F>(r, frame0 + j, done_frame);
-  }
   // Tiles with Releasing lanes (none Attacking) in which a lane may run out: x[j] *= max((t*(t*t))*scale, 0), t += step,
   // straight-line for every lane.  The clamp is what Releasing -> Stopped means for this sequence: t falls
   // monotonically, a sample whose t is <= 0 lies after the stop (envelopes.rs:72-78) and its cube times a non-negative
   // scale is <= 0.  t_block[k] = t of the first sample after the k-th block of eight (for mark_done's frame).
   // (Two hand-scheduled packed versions of this loop were measured slower than what the compiler makes of it:
   // 4 060 against 3 500 cycles per 64-sample tile for the envelope wave, tools/env_stamps.py.)
-  template <typename F, int T>
+  // What a tile does with an envelope sample e: the multiplier's x * e (MUL), or e itself -- the envelope as a source of the
+  // voice (EnvSrcT below), which shares every path of this tile code.
+  template <bool MUL, typename F> static __device__ __forceinline__ F put(F x, F e) { return MUL ? x * e : e; }
+  template <typename F, int T, bool MUL>
   static __device__ __forceinline__ void release_tile_clamped(F (&x)[T], F& t_io, F step, F scale, F (&t_block)[T / 8]) {
     static_assert(T % 8 == 0, "blocks of eight samples");
     F t = t_io;
@@ -1745,7 +1707,7 @@ struct MulEnvT : StageDefaults {
       const F tj = t;
       t = t + step;
       const F e = (tj * (tj * tj)) * scale;
-      x[j] = x[j] * (e > (F)0 ? e : (F)0);
+      x[j] = put<MUL>(x[j], (e > (F)0 ? e : (F)0));
       if (j % 8 == 7) t_block[j / 8] = t;
     }
     t_io = t;
@@ -1757,15 +1719,16 @@ struct MulEnvT : StageDefaults {
   // a constant step, so the sequence is monotone and a threshold is crossed inside the tile iff it is crossed at
   // its first or its last sample.  If any lane would change state (or Attacking and Releasing lanes share the
   // tile) the exact per-sample state machine runs instead, from the untouched registers.  Same values either way.
-  template <typename F, bool FMA, int T>
-  static __device__ __forceinline__ void tick_tile(Regs<F>& r, F (&x)[T], const Ctx&, u32 frame0, u32& done_frame) {
+  // (MUL: x[j] *= envelope, this stage; !MUL: x[j] = envelope, the envelope as a source -- EnvSrcT)
+  template <typename F, int T, bool MUL>
+  static __device__ __forceinline__ void env_tile(Regs<F>& r, F (&x)[T], u32 frame0, u32& done_frame) {
     const u32 st = r.state;
     const bool isA = st == 1u, isR = st == 3u;
     const bool anyA = __builtin_amdgcn_ballot_w64(isA) != 0, anyR = __builtin_amdgcn_ballot_w64(isR) != 0;
     const F konst = st == 2u ? (F)1 : (F)0;
     if (!anyA && !anyR) {  // every lane Sustaining or Stopped
 #pragma unroll
-      for (int j = 0; j < T; ++j) x[j] = x[j] * konst;
+      for (int j = 0; j < T; ++j) x[j] = put<MUL>(x[j], konst);
       return;
     }
     if (!(anyA && anyR)) {
@@ -1785,7 +1748,7 @@ struct MulEnvT : StageDefaults {
         if (anyR && __builtin_amdgcn_ballot_w64(odd) == 0 && __builtin_amdgcn_ballot_w64(near) != 0) {
           const F t0 = t;
           F tb[T / 8];  // t of the first sample after each block of eight
-          release_tile_clamped<F, T>(x, t, step, scale, tb);
+          release_tile_clamped<F, T, MUL>(x, t, step, scale, tb);
           const F t1 = t0 + step;
           const bool hit = isR && (t1 <= (F)0 || t <= (F)0);
           if (__builtin_amdgcn_ballot_w64(hit) != 0) {
@@ -1825,10 +1788,10 @@ struct MulEnvT : StageDefaults {
         if (__builtin_amdgcn_ballot_w64(maybe) == 0) {
           if (anyR) {
 #pragma unroll
-            for (int j = 0; j < T; ++j) { const F tj = t; t = t + step; x[j] = x[j] * ((tj * (tj * tj)) * scale); }
+            for (int j = 0; j < T; ++j) { const F tj = t; t = t + step; x[j] = put<MUL>(x[j], ((tj * (tj * tj)) * scale)); }
           } else {
 #pragma unroll
-            for (int j = 0; j < T; ++j) { const F tj = t; t = t + step; x[j] = x[j] * tj; }
+            for (int j = 0; j < T; ++j) { const F tj = t; t = t + step; x[j] = put<MUL>(x[j], tj); }
           }
           if (moving) r.t = t;
           return;
@@ -1842,10 +1805,10 @@ struct MulEnvT : StageDefaults {
       if (__builtin_amdgcn_ballot_w64(hit) == 0) {
         if (anyR) {
 #pragma unroll
-          for (int j = 0; j < T; ++j) x[j] = x[j] * ((tt[j] * (tt[j] * tt[j])) * scale);
+          for (int j = 0; j < T; ++j) x[j] = put<MUL>(x[j], ((tt[j] * (tt[j] * tt[j])) * scale));
         } else {
 #pragma unroll
-          for (int j = 0; j < T; ++j) x[j] = x[j] * tt[j];
+          for (int j = 0; j < T; ++j) x[j] = put<MUL>(x[j], tt[j]);
         }
         if (moving) r.t = t;
         return;
@@ -1861,7 +1824,7 @@ struct MulEnvT : StageDefaults {
           const bool pos = !(tt[j] <= (F)0);
           const F e = pos ? (tt[j] * (tt[j] * tt[j])) * scale : (F)0;
           alive += pos ? 1u : 0u;
-          x[j] = x[j] * e;
+          x[j] = put<MUL>(x[j], e);
         }
         if (isR && hit) { r.state = 0u; r.t = (F)0; done_frame = frame0 + alive - 1u - r.seg; }
         else if (moving) r.t = t;
@@ -1871,12 +1834,12 @@ struct MulEnvT : StageDefaults {
         // an EnvAsr attack arrives (envelopes.rs:58-64): from the first t >= 1 on the envelope is 1 (Sustaining)
         // and t stays at that first value.  Sample 0 outputs its t whatever it is (a restart can come in above 1).
         F first = t;  // the sequence rises, so the first t >= 1 is the smallest one; the tile's last step is a candidate too
-        x[0] = x[0] * tt[0];
+        x[0] = put<MUL>(x[0], tt[0]);
 #pragma unroll
         for (int j = T - 1; j >= 1; --j) {
           const bool ge = tt[j] >= (F)1;
           first = ge ? tt[j] : first;
-          x[j] = x[j] * (ge ? (F)1 : tt[j]);
+          x[j] = put<MUL>(x[j], (ge ? (F)1 : tt[j]));
         }
         if (isA && hit) { r.state = 2u; r.t = first; }
         else if (moving) r.t = t;
@@ -1884,7 +1847,11 @@ struct MulEnvT : StageDefaults {
       }
     }
 #pragma unroll
-    for (int j = 0; j < T; ++j) x[j] = x[j] * env_next<F>(r, frame0 + j, done_frame);
+    for (int j = 0; j < T; ++j) x[j] = put<MUL>(x[j], env_next<F>(r, frame0 + j, done_frame));
+  }
+  template <typename F, bool FMA, int T>
+  static __device__ __forceinline__ void tick_tile(Regs<F>& r, F (&x)[T], const Ctx&, u32 frame0, u32& done_frame) {
+    env_tile<F, T, true>(r, x, frame0, done_frame);
   }
   template <typename F>
   static __device__ __forceinline__ void on_event(Regs<F>& r, u32 op, u32 rel, u64 bits, u32 frame) {
@@ -1903,6 +1870,29 @@ struct MulEnvT : StageDefaults {
 };
 typedef MulEnvT<false> MulAsr;
 typedef MulEnvT<true> MulAr;
+
+// EnvAsr / EnvAr ALONE -- g.push(EnvAsr::new(a, r)), envelopes.rs:19-163 / :174-303: a node with no inputs whose output is
+// the envelope's sample (KNH_STAGE_FLAG_ENV_SOURCE).  Registers, slots, load / store, events, setters and the done mark are
+// those of the multiplying form; the input sample is not read.
+template <bool AR>
+struct EnvSrcT : MulEnvT<AR> {
+  typedef MulEnvT<AR> Base;
+  static constexpr bool kEnvSource = true;
+  template <typename F, bool FMA>
+  static __device__ __forceinline__ F tick(typename Base::template Regs<F>& r, F, const Ctx&, u32 frame, u32& done_frame) {
+    return Base::template env_next<F>(r, frame, done_frame);
+  }
+  // x[j] = envelope, T samples at once: the multiplier's tile code with the sample written instead of multiplied in
+  // (MulEnvT::env_tile, MUL = false) -- the constant tile, the straight-line tiles that keep nothing but the running t, the
+  // tile-wise paths for a release that runs out and an attack that arrives, and the exact per-sample state machine from the
+  // untouched registers whenever lanes of the wavefront would change state in a way those do not cover.  Same values on every path.
+  template <typename F, bool FMA, int T>
+  static __device__ __forceinline__ void tick_tile(typename Base::template Regs<F>& r, F (&x)[T], const Ctx&, u32 frame0, u32& done_frame) {
+    Base::template env_tile<F, T, false>(r, x, frame0, done_frame);
+  }
+};
+typedef EnvSrcT<false> EnvAsrSrc;
+typedef EnvSrcT<true> EnvArSrc;
 
 // x * Envelope (segment envelope) -- envelopes.rs:359-527 with MathUGen Mul.  Every quantity is f64 whatever F is.
 // slots (one word each; doubles take two, low word first):
@@ -1962,8 +1952,9 @@ struct MulSegEnv : StageDefaults {
   static __device__ __forceinline__ void ar_set(Regs<F>& r, F v, const Ctx& c) {
     r.dt = (double)v * (1.0 / (double)c.sample_rate);
   }
-  template <typename F, bool FMA>
-  static __device__ __forceinline__ F tick(Regs<F>& r, F x, const Ctx& c, u32, u32& done_frame) {
+  // One sample of the Envelope itself (Envelope::process, envelopes.rs:407-463).
+  template <typename F>
+  static __device__ __forceinline__ F env_next(Regs<F>& r, const Ctx& c, u32& done_frame) {
     bind<F>(r, c);
     F out;
     if (!r.running) {
@@ -1992,7 +1983,11 @@ struct MulSegEnv : StageDefaults {
         }
       }
     }
-    return x * out;
+    return out;
+  }
+  template <typename F, bool FMA>
+  static __device__ __forceinline__ F tick(Regs<F>& r, F x, const Ctx& c, u32, u32& done_frame) {
+    return x * env_next<F>(r, c, done_frame);
   }
   template <typename F, bool FMA, int T>
   static __device__ __forceinline__ void tick_tile(Regs<F>& r, F (&x)[T], const Ctx& c, u32 frame0, u32& done_frame) {
@@ -2022,6 +2017,21 @@ struct MulSegEnv : StageDefaults {
       case 7: r.dt = hi(r.dt, w); break;
       default: break;
     }
+  }
+};
+
+// Envelope (segments) ALONE -- g.push(Envelope), envelopes.rs:359-527: the source form of MulSegEnv
+// (KNH_STAGE_FLAG_ENV_SOURCE).  Sample by sample, like its multiplier.
+struct SegEnvSrc : MulSegEnv {
+  static constexpr bool kEnvSource = true;
+  template <typename F, bool FMA>
+  static __device__ __forceinline__ F tick(Regs<F>& r, F, const Ctx& c, u32, u32& done_frame) {
+    return env_next<F>(r, c, done_frame);
+  }
+  template <typename F, bool FMA, int T>
+  static __device__ __forceinline__ void tick_tile(Regs<F>& r, F (&x)[T], const Ctx& c, u32, u32& done_frame) {
+#pragma unroll
+    for (int j = 0; j < T; ++j) x[j] = env_next<F>(r, c, done_frame);
   }
 };
 

@@ -552,13 +552,15 @@ class Graph {
       }
       const NodeRec& a = nodes_[static_cast<size_t>(n.in0)];
       const NodeRec& b = nodes_[static_cast<size_t>(n.in1)];
-      // signal * envelope (either operand order; multiplication commutes exactly)
+      // signal * envelope (either operand order; multiplication commutes exactly): one MUL_ENV_* stage, where the product is
+      // the envelope's only reader and the envelope has no wrappers.  An envelope with wrappers, or one that something else
+      // reads too (a filter's cutoff through link(), a second product), is a signal of the voice: an ENV_SOURCE stage
+      // (below), and this product a MathUGen of two signals.
       int env = -1;
-      if (n.math2_kind == KNH_STAGE_MATH_MUL)
-        env = (b.type == NodeRec::UGEN && b.spec.is_env) ? n.in1 : (a.type == NodeRec::UGEN && a.spec.is_env) ? n.in0 : -1;
+      auto folds = [&](const NodeRec& x, int id) { return x.type == NodeRec::UGEN && x.spec.is_env && x.spec.wrappers.empty() && env_readers_[id] <= 1; };
+      if (n.math2_kind == KNH_STAGE_MATH_MUL) env = folds(b, n.in1) ? n.in1 : folds(a, n.in0) ? n.in0 : -1;
       if (env >= 0) {
         const NodeRec& e = nodes_[static_cast<size_t>(env)];
-        if (!e.spec.wrappers.empty()) throw GraphError("wrappers on an envelope inside a product are not fused");
         const auto ar = ar_edge(e);
         const uint16_t src = operand(env == n.in1);
         push_stage(p, e.spec.kind, e.spec.smooth_params_ ? KNH_STAGE_FLAG_SMOOTH_PARAMS : 0, e.spec.precise_timing_, env, e.spec.args, in_of(src), ar.second, ar.first);
@@ -588,7 +590,8 @@ class Graph {
       return finish();
     }
     const UGenSpec& s = n.spec;
-    if (s.is_env || s.is_constant) throw GraphError("an envelope/constant must be an operand of * + - /");
+    if (s.is_constant) throw GraphError("a constant must be an operand of * + - /");
+    if (s.is_env && n.in0 >= 0) throw GraphError("an envelope has no inputs: it is an operand of `*` or a signal of its own, not a processor of one");
     if (s.kind == KNH_STAGE_GALACTIC) {
       // the reverb ends the voice (only the graph outputs read it: it is the first node met) and reads two signals of it:
       // one signal on both inputs is the mono descriptor, two are named by `input` / `input2` (knh_stage_desc)
@@ -608,8 +611,10 @@ class Graph {
     }
     const bool source = s.kind == KNH_STAGE_SIN_WT || s.kind == KNH_STAGE_SIN_NUMERIC || s.kind == KNH_STAGE_PHASOR || s.kind == KNH_STAGE_POLYBLEP ||
                         s.kind == KNH_STAGE_BUFFER_READER || s.kind == KNH_STAGE_WHITE_NOISE || s.kind == KNH_STAGE_PINK_NOISE ||
-                        s.kind == KNH_STAGE_BROWN_NOISE || s.kind == KNH_STAGE_RANDOM_LIN;
-    uint16_t flags = 0, input = 0;
+                        s.kind == KNH_STAGE_BROWN_NOISE || s.kind == KNH_STAGE_RANDOM_LIN || s.is_env;
+    // an envelope read as a signal -- g.push(EnvAsr::new(..)) into a filter, a `+`, a link(), the graph output: the envelope
+    // alone, a source (KNH_STAGE_FLAG_ENV_SOURCE), its wrappers behind it
+    uint16_t flags = s.is_env ? KNH_STAGE_FLAG_ENV_SOURCE : 0, input = 0;
     std::pair<uint16_t, uint16_t> ar{0, 0};
     if (source && n.link_source >= 0 && s.kind == KNH_STAGE_SIN_WT && s.ar_params_ && n.link_param == 0) {
       // SinWt(..).ar_params().link("freq", ..): the spelling with pre-built kernels (BASELINE config C5)
@@ -660,6 +665,16 @@ class Graph {
         partial_output_.clear();
         throw GraphError("to_graph_out_channels(): a graph output of the voice has no signal");
       }
+    // who reads the envelopes that are not in a bank yet: `signal * env` is one stage only where the product is the envelope's
+    // one reader (trace)
+    env_readers_.clear();
+    auto reads = [&](int src) {
+      if (src >= 0 && nodes_[static_cast<size_t>(src)].type == NodeRec::UGEN && nodes_[static_cast<size_t>(src)].spec.is_env) ++env_readers_[src];
+    };
+    for (const NodeRec& x : nodes_)
+      if (x.bank < 0) { reads(x.in0); reads(x.in1); reads(x.link_source); }
+    for (auto& conn : new_outputs_)
+      for (auto& c : conn) reads(c.first);
     struct Voice { ChainPlan plan; std::vector<int> nodes; };
     std::vector<Voice> voices;
     for (auto& conn : new_outputs_) {
@@ -813,6 +828,7 @@ class Graph {
   uint32_t outputs_, sample_rate_;
   size_t block_size_;
   std::vector<NodeRec> nodes_;
+  std::map<int, int> env_readers_;  // commit_changes: envelope node -> how many edges (inputs, links, graph outputs) start at it
   std::vector<std::vector<std::pair<int, int>>> new_outputs_;  // per to_graph_out(): (node, output channel) per graph output
   std::vector<std::pair<int, int>> partial_output_;            // to_graph_out_channels(): the voice being connected, (-1, 0): no signal yet
   std::vector<Bank> banks_;
