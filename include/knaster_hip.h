@@ -514,7 +514,8 @@ int32_t knh_bank_add_buffer_interleaved(knh_bank* bank, uint32_t stage, const vo
  * BufferReader::new(pool[id], rate, looping).start_at(start_s) is pushed and initialised (buffer.rs:43-72, 110-118): rate
  * scale, start, duration (the whole new Buffer) and end from the new Buffer's sample rate, read pointer at the start, not
  * finished; earlier duration_s / end_s / start_s calls are forgotten, later ones convert with the new rate; the voice's
- * entry of knh_bank_read_done_frames is not-done until the new reader finishes.
+ * entry of knh_bank_read_done_frames is not-done until the new reader finishes.  ctor becomes the voice's constructor
+ * arguments, as knh_bank_set_voice_ctor_args' would: a later knh_bank_restart_voices constructs this reader again.
  * Refused, changing nothing: a stage that is not a BufferReader, a voice or buffer index out of range
  * (KNH_ERR_OUT_OF_RANGE), ctor == NULL after init, and -- after init -- a chain in which another stage can also mark a
  * voice done (EnvAsr, EnvAr, Envelope: KNH_ERR_UNSUPPORTED_CHAIN, the single done frame per voice could not be attributed)

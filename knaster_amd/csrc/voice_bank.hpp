@@ -424,6 +424,9 @@ struct Bank final : knh_bank {
     for (size_t k = 0; k < count; ++k) {
       const uint32_t v = voices[k];
       buf_id[v] = ids[k];
+      // the new reader's constructor arguments are the voice's from here on, as knh_bank_assign_wavetables' are: a later
+      // knh_bank_restart_voices constructs the reader the voice has, not the first one's rate on the new Buffer
+      std::copy(args + 3 * k, args + 3 * k + 3, ctor[stage].begin() + static_cast<size_t>(v) * 3);
       reader_construct(S, v, args + 3 * k, [&](int rel, uint32_t word) {
         pending.push_back(HostEvent{v, frame_base, knh_dev::EV_SET, static_cast<uint32_t>(S.slot_base + rel), word});
       });

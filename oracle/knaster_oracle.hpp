@@ -1589,6 +1589,41 @@ struct MathUGen : UGen<F> {
 };
 
 // ---------------------------------------------------------------------------
+// Math1UGen -- knaster_core_dsp/src/ugens/math.rs:167-305: one input, one
+// output, no parameters; Operation1::apply per sample.  Ceil (173-183), Sqrt
+// (185-195), Floor (197-207), Trunc (209-219), Fract (221-231: Rust's
+// `fract` is `x - x.trunc()`).  Exp (233-243) is not restated: `exp` is not
+// the same bits in every libm, and nothing here compares against it.
+// ---------------------------------------------------------------------------
+enum class Math1Op { Ceil, Sqrt, Floor, Trunc, Fract };
+template <typename F>
+inline F math1_apply(Math1Op op, F a) {
+  switch (op) {
+    case Math1Op::Ceil: return std::ceil(a);
+    case Math1Op::Sqrt: return std::sqrt(a);
+    case Math1Op::Floor: return std::floor(a);
+    case Math1Op::Trunc: return std::trunc(a);
+    case Math1Op::Fract: return a - std::trunc(a);
+  }
+  return a;
+}
+template <typename F>
+struct Math1UGen : UGen<F> {
+  Math1Op op;
+  explicit Math1UGen(Math1Op op_) : op(op_) {}
+  size_t inputs() const override { return 1; }
+  size_t outputs() const override { return 1; }
+  size_t parameters() const override { return 0; }
+  void process(AudioCtx&, UGenFlags&, const F* in, F* out) override { out[0] = math1_apply(op, in[0]); }
+  void process_block(AudioCtx&, UGenFlags&, const BlockView<F>& input, BlockView<F>& output) override {
+    const F* a = input.channel(0);
+    F* o = output.channel(0);
+    for (size_t i = 0; i < output.frames; ++i) o[i] = math1_apply(op, a[i]);
+  }
+  void param_apply(AudioCtx&, size_t, ParameterValue) override {}
+};
+
+// ---------------------------------------------------------------------------
 // Test UGens -- knaster_core_dsp/src/test_utils.rs:8-86,
 // knaster_graph/src/tests/utils.rs:4-67
 // ---------------------------------------------------------------------------

@@ -168,6 +168,14 @@ struct VoiceChainBuilder {
         case KNH_STAGE_POW_CONST:
           core = std::make_unique<Constant<F>>(fnew<F>(a[0]));
           break;
+        // Math1UGen<F, Op> (math.rs:167-305): no constructor arguments, no parameters
+        case KNH_STAGE_MATH1_CEIL: core = std::make_unique<Math1UGen<F>>(Math1Op::Ceil); break;
+        case KNH_STAGE_MATH1_SQRT: core = std::make_unique<Math1UGen<F>>(Math1Op::Sqrt); break;
+        case KNH_STAGE_MATH1_FLOOR: core = std::make_unique<Math1UGen<F>>(Math1Op::Floor); break;
+        case KNH_STAGE_MATH1_TRUNC: core = std::make_unique<Math1UGen<F>>(Math1Op::Trunc); break;
+        case KNH_STAGE_MATH1_FRACT: core = std::make_unique<Math1UGen<F>>(Math1Op::Fract); break;
+        case KNH_STAGE_MATH1_EXP:
+          throw std::runtime_error("MATH1_EXP is not in the oracle: exp is not bit-exact across math libraries (compare it with a tolerance against numpy)");
         default: throw std::runtime_error("unknown stage kind");
       }
       const bool two_node = (st.kind >= KNH_STAGE_MUL_ENV_ASR && st.kind <= KNH_STAGE_DIV_CONST) || st.kind == KNH_STAGE_MUL_ENVELOPE ||

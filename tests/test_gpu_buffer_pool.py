@@ -196,6 +196,42 @@ def test_reassignment_is_a_fresh_reader(knh, oracle, sample_type):
     m.close()
 
 
+@pytest.mark.parametrize("sample_type", BOTH)
+def test_a_restart_constructs_the_reader_the_voice_has(knh, oracle, sample_type):
+    """knh_bank_restart_voices behind a reassignment: the constructor arguments given with knh_bank_assign_buffers are the
+    voice's from then on, so every other voice restarted in front of block 5 -- reassigned at block 3 or not -- is a fresh
+    reader on the entry it has with the rate, looping and start it has, the oracle bank Expected starts at that block.
+    (Found by the graph-voice fuzz, tests/test_gpu_graph_voices.py: the restart built the FIRST reader's rate, looping and
+    start on the new Buffer.)"""
+    buffers = sp.make_buffers(RE_SPEC, seed=5)
+    ids0 = (np.arange(RE_N) % 4).astype(np.uint32)
+    x = sp.Expected(oracle, RE_N, RE_BS, sample_type, buffers, ids0, re_ctor0(), re_traffic)
+    g = sp.pooled_bank(knh, RE_N, RE_BS, sample_type, buffers, ids0, re_ctor0(), mix_mode=L.MIX_LEFT_FOLD)
+    voices3, ids3, rows3 = re_swaps()[3]
+    held = re_ctor0().copy()
+    again = np.arange(0, RE_N, 2, dtype=np.uint32)
+    assert np.isin(again, voices3).any() and (~np.isin(again, voices3)).any()
+    for k in range(8):
+        if k == 3:
+            x.reassign(k, voices3, ids3, rows3)
+            g.assign_buffers(0, voices3, ids3, rows3)
+            held[voices3] = rows3
+        if k == 5:
+            assert (held[again] != re_ctor0()[again]).any()
+            x.reassign(k, again, x.ids[again].astype(np.uint32), held[again])
+            g.restart_voices(again)
+        re_traffic(k, g)
+        voices, done = x.step(k)
+        out, g_voices, _ = g.process_block_voices()
+        assert_bit_equal(g_voices, voices, f"block {k} per-voice")
+        assert_bit_equal(out[0], sp.left_fold(voices), f"block {k} left-fold mix")
+        np.testing.assert_array_equal(g.read_done_frames(), done)
+        if k == 5:
+            assert (np.abs(voices[again]).max(axis=1) > 0).any()
+    x.close()
+    g.close()
+
+
 # ---- every kernel form -------------------------------------------------------------------------------------------------
 POOL_FORMS = dict(FORMS)
 POOL_FORMS["jitwide4"] = {"KNH_JIT_PIPE": "0", "KNH_JIT_WAVES": "4"}  # whole-chain wavefronts, four to a workgroup

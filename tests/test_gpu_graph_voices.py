@@ -4,6 +4,7 @@ into the output slot in front of a stage's tile code, linked stages run sample b
 the done frame, eight-sample visits past sixteen stages.  Seeded random voices and six directed ones against the oracle,
 bit for bit; a comb against numpy; one launch against block by block; the bank cut into voice ranges; ALL_DONE."""
 import functools
+import re
 
 import numpy as np
 import pytest
@@ -216,3 +217,133 @@ def test_all_done_follows_the_envelope_listed_last(knh, held_last_in_list):
         assert not any(f & L.FLAG_ALL_DONE for f in flags)
     else:
         assert all(f & L.FLAG_ALL_DONE for f in flags[2:])
+
+
+# ---- the second generator path: voices that combine the newer stage kinds, flags and calls ----------------------------------
+def expected_form(w):
+    """A graph takes the one-wavefront fused form, a plain chain the fused pipeline (kernel_form.hpp plan_forms)."""
+    return L.DEBUG_FORM_PIPELINE_FUSED if w.info.chain else L.DEBUG_FORM_WHOLE_CHAIN_FUSED
+
+
+def check_wavetable_place(w, sig):
+    """'g' / 'h' in the initialised bank's signature: its one f32 Wavetable is staged to LDS in the sine table's place -- one
+    flagged stage, a one-table entry, f32, no 'W' / 'R' in the voice; 'M' / 'k': gathered from device memory."""
+    if not w.wavetables:
+        assert not set("gMhk") & set(sig.split("#")[0].replace("@", " ")), sig
+        return
+    chars = [gv.stage_char(s) for s in w.stages]
+    staged = w.wavetables[1] == ["one"] and w.sample_type == L.F32 and not set("WR") & set(chars) and sum(c in "Mk" for c in chars) == 1
+    assert staged == (w.info.wt_variant == "lds")
+    body = [m.group(1) for m in re.finditer(r"(.)(?:%\d+)?@", sig)] if "@" in sig else list(sig)
+    assert (("g" in body) or ("h" in body)) == staged, sig
+    assert (("M" in body) or ("k" in body)) == (not staged), sig
+
+
+@pytest.mark.parametrize("seed", range(gv.N_SEEDS))
+def test_random_head_voice_matches_the_oracle(knh, seed):
+    """Nine blocks in KNH_MIX_LEFT_FOLD against the lowered oracle (gv.lower_for_oracle), bit for bit: every voice's signal
+    (both planes with connected outputs), the left-fold mix, the done frames, ANY_DONE.  Readers are given other Buffers in
+    front of blocks 3 and 7; in front of block 6 every third voice is restarted and continues against a freshly built oracle
+    bank, the others against the first one."""
+    w = gv.random_voice_head(seed)
+    ref = w.reference
+    g = gv.head_gpu_bank(knh, w, L.MIX_LEFT_FOLD)
+    sig = g.debug_signature()
+    what = f"head seed {seed} {sig}"
+    check_wavetable_place(w, sig)
+    form = int(g.debug_words()[2])
+    print(f"head seed {seed}: form {form} n {w.n_voices} bs {w.block_size} {'f64' if w.sample_type == L.F64 else 'f32'} {sorted(w.info.features)}")
+    assert form == expected_form(w), what  # (a silent change of form would empty the test)
+    for b in range(gv.HEAD_BLOCKS):
+        gv.head_edits(w, b, g)
+        g_out, g_voices, g_flags = g.process_block_voices()
+        assert_bit_equal(g_voices, ref.voices[b], f"{what} block {b} per-voice")
+        assert_bit_equal(g_out, ref.mix[b], f"{what} block {b} left-fold mix")
+        np.testing.assert_array_equal(g.read_done_frames(), ref.done[b], err_msg=f"{what} block {b} done frames")
+        assert g_flags & L.FLAG_ANY_DONE == int(ref.flags[b]) & L.FLAG_ANY_DONE, f"{what} block {b} ANY_DONE"
+    g.close()
+
+
+WAYS = ("split", "one_launch", "host_threads", "devices", "rank", "resident")
+WAY_BLOCKS = 6  # (the restart, in front of block 6, is the first test's)
+
+
+class _AtBlock:
+    """parameter calls for block `offset` of the coming launch (knh_bank_param_apply_many_at)"""
+
+    def __init__(self, bank, offset):
+        self.bank, self.offset = bank, offset
+
+    def param_apply_many(self, voices, stages, params, kinds, fvalues=None, ivalues=None, delays=None):
+        self.bank.param_apply_many(voices, stages, params, kinds, fvalues, ivalues, delays, block_offset=self.offset)
+
+
+@pytest.mark.parametrize("seed", range(gv.N_SEEDS))
+def test_head_voice_runs_the_same_every_way(knh, monkeypatch, seed):
+    """The seed's voice in KNH_MIX_TREE, run one other way (seed % 6) beside a plain bank, six blocks with the reassignment in
+    front of block 3: each block as 40 + rest frames (17 + rest at block size 48); the blocks in one process_blocks per
+    stretch between graph edits; on two host threads; as two voice ranges on one device; as one rank's share; resident.
+    Per-voice rows bit for bit, signs of zero included, where the way hands them out; the mix bit for bit for the split, the
+    single launch and the resident call, and within 1e-5 * max(1, peak) -- what tests/test_gpu_multi.py holds re-associated
+    tree mixes to -- for the three forms that cut the bank into voice ranges."""
+    w = gv.random_voice_head(seed)
+    way = WAYS[seed % len(WAYS)]
+    bs = w.block_size
+    monkeypatch.setenv("KNH_RESIDENT", "0")
+    plain = gv.head_gpu_bank(knh, w, L.MIX_TREE)
+    monkeypatch.setenv("KNH_RESIDENT", "1" if way == "resident" else "0")
+    kw = {"host_threads": dict(host_threads=2), "devices": dict(devices=[0, 0]), "rank": dict(rank=0, world=1)}.get(way, {})
+    other = gv.head_gpu_bank(knh, w, L.MIX_TREE, **kw)
+    what = f"head seed {seed} {way}"
+    want_mix, want_voices, want_done = [], [], []
+    for b in range(WAY_BLOCKS):
+        gv.head_edits(w, b, plain, restart=False)
+        out, voices, _ = plain.process_block_voices()
+        want_mix.append(out)
+        want_voices.append(voices)
+        want_done.append(plain.read_done_frames())
+    assert max(float(np.abs(m).max()) for m in want_mix) > 1e-4
+    if way == "one_launch":
+        cuts = sorted({0, WAY_BLOCKS} | {b for b in w.reassign if b < WAY_BLOCKS})
+        for lo, hi in zip(cuts, cuts[1:]):
+            if lo in w.reassign:
+                voices, ids, rows = w.reassign[lo]
+                other.assign_buffers(w.pool[0], voices, ids, ctor=rows)
+            for b in range(lo, hi):
+                w.events(b, _AtBlock(other, b - lo))
+            many, _ = other.process_blocks(hi - lo)
+            for b in range(lo, hi):
+                assert_bit_equal(many[b - lo], want_mix[b], f"{what} block {b} mix", strict_zero=True)
+    else:
+        for b in range(WAY_BLOCKS):
+            gv.head_edits(w, b, other, restart=False)
+            if way == "split":
+                first = gv.head_split_point(bs)
+                out = np.zeros_like(want_mix[b])
+                other.process_block(first, 0, out=out)
+                other.process_block(bs - first, first, out=out)
+                assert_bit_equal(out, want_mix[b], f"{what} block {b} mix", strict_zero=True)
+            elif way == "resident":
+                out, _ = other.process_block()
+                assert_bit_equal(out, want_mix[b], f"{what} block {b} mix", strict_zero=True)
+            else:
+                if way == "rank":  # (a rank bank gives the mix only)
+                    out, _ = other.process_block()
+                else:
+                    out, voices, _ = other.process_block_voices()
+                    assert_bit_equal(voices, want_voices[b], f"{what} block {b} per-voice", strict_zero=True)
+                bound = 1e-5 * max(1.0, float(np.abs(want_mix[b]).max()))
+                assert np.max(np.abs(out.astype(np.float64) - want_mix[b].astype(np.float64))) <= bound, f"{what} block {b} mix"
+            if way != "split":  # (a call that ends inside a block reports frames of its own part)
+                np.testing.assert_array_equal(other.read_done_frames(), want_done[b], err_msg=f"{what} block {b} done frames")
+    # the way meant is the way run
+    if way in ("host_threads", "devices"):
+        assert other.ranks() == 2
+    elif way == "rank":  # one rank of a world of one: what tells it from a plain bank is that it hands out no per-voice rows
+        assert other.ranks() == 1 and plain.ranks() == 1
+        with pytest.raises(L.KnasterHipError, match="per-voice output is not available from a sharded bank"):
+            other.process_block_voices()
+    elif way == "resident":
+        assert other.resident_stats()[0] >= 1 and plain.resident_stats()[0] == 0
+    plain.close()
+    other.close()
