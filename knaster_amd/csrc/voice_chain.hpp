@@ -29,6 +29,7 @@ struct Chain<F, FMA, BASE> {
   static constexpr bool kStereo = false;
   static constexpr u64 kParamBits = 0ull, kNopOkBits = 0ull;
   static constexpr bool kBinds = false;
+  static constexpr bool kBlockWork = false;
   static constexpr bool kUsesRing = false;
   static constexpr int kRingStages = 0;
   template <int T> __device__ __forceinline__ void tick_tile_sw(const Chain&, u32, u64, F (&)[T], const Ctx&, u32) {}
@@ -48,6 +49,7 @@ struct Chain<F, FMA, BASE> {
   __device__ __forceinline__ u32 collect_done(u32 acc) const { return acc; }
   __device__ __forceinline__ void reset_marks() {}
   __device__ __forceinline__ void begin_block(u32, const Ctx&) {}
+  __device__ __forceinline__ bool block_begun(u32) const { return true; }
 };
 template <typename F, bool FMA, int BASE, typename S0, typename... Rest>
 struct Chain<F, FMA, BASE, S0, Rest...> {
@@ -63,6 +65,9 @@ struct Chain<F, FMA, BASE, S0, Rest...> {
   static constexpr u64 kParamBits = (BASE + S0::kSlots <= 64 ? (u64)S0::kParamMask << (BASE < 64 ? BASE : 0) : 0ull) | RestT::kParamBits;
   static constexpr u64 kNopOkBits = ((S0::kParamMask != 0u || !S0::kHasSeg) && BASE < 64 ? (u64)1 << (BASE < 64 ? BASE : 0) : 0ull) | RestT::kNopOkBits;
   static constexpr bool kBinds = S0::kNeedsBind || RestT::kBinds;  // a stage with memory behind it (delay ring, segment table, buffer)
+  // some stage has work where a block of the launch ends and the next begins (StageDefaults::kHasBlockWork): the chain's quiet
+  // runs end with their block.  A stage that begin_block binds has such work whatever it says.
+  static constexpr bool kBlockWork = S0::kHasBlockWork || S0::kNeedsBind || RestT::kBlockWork;
   static constexpr bool kUsesRing = S0::kUsesRing || RestT::kUsesRing;
   static constexpr int kRingStages = (S0::kUsesRing ? 1 : 0) + RestT::kRingStages;  // delay stages of the voice
   typename S0::template Regs<F> r;
@@ -154,6 +159,14 @@ struct Chain<F, FMA, BASE, S0, Rest...> {
     if constexpr (S0::kNeedsBind) S0::template bind<F>(r, c);
     if constexpr (S0::kIsEnv && S0::kHasSeg) r.seg = frame_begin;
     rest.begin_block(frame_begin, c);
+  }
+  // "begin_block(frame_begin, ..) would change nothing in this voice": what a chain without block work (kBlockWork) still has
+  // to be asked before a quiet run carries on into the next block -- an envelope's seg is the launch's first frame again, not
+  // the frame of a queued change inside the current block.
+  __device__ __forceinline__ bool block_begun(u32 frame_begin) const {
+    bool ok = rest.block_begun(frame_begin);
+    if constexpr (S0::kIsEnv && S0::kHasSeg) ok = ok && r.seg == frame_begin;
+    return ok;
   }
 };
 

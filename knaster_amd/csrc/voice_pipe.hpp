@@ -271,11 +271,14 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
   // behind group 0: it waits I steps while the pipeline fills, takes its n_tiles tiles, one per step, and waits out the rest
   // while the pipeline drains.
   // EVERY WAVEFRONT OF THE WORKGROUP ARRIVES AT EXACTLY n_steps STEP BARRIERS PER CALL.  Here that is: I in the loop in front,
-  // one per tile -- a tile of a quiet run meets its barrier inside the run, except the run's last tile when the run ends with
-  // the supply of whole tiles, whose barrier (like that of every tile of the general paths) is the one at the end of the tile
-  // loop, `step_open` saying which -- and n_steps - I - n_tiles in the loop behind.  A Fan group's wavefronts each make the
+  // one per tile -- a tile of a quiet run meets its barrier inside the run, except the run's last tile, whose barrier (like
+  // that of every tile of the general paths) is the one at the end of the tile loop: a run is left in front of its last
+  // tile's barrier (a group whose runs end with their block, which keeps the older loop, also leaves behind it when an event
+  // ends the run: `step_open` says which) -- and n_steps - I - n_tiles in the loop behind.  A Fan group's wavefronts each make the
   // same steps (their tiles are windows of the same tiles); a folding group (PIPE_FOLD) folds inside its step; the mixer
   // (pipe_run_mixer) and the dead group of the two-group form (voice_pipe_kernel) count the same n_steps.
+  // A quiet run that carries on from the last tile of one block into tile 0 of the next (below) changes none of this: it
+  // makes the same tiles in the same order, one barrier each, and only skips the block-end bookkeeping between them.
   const u32 n_frames = fend - fbeg;
   const int tpb = (int)((n_frames + T - 1) / T);           // tiles per block
   const int n_tiles = tpb * (int)a.n_blocks;
@@ -285,6 +288,12 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
   const int full = n_frames >= fo + (u32)TW ? (int)((n_frames - fo - (u32)TW) / (u32)T) + 1 : 0;
   // the buffers of this group's next tile, carried from tile to tile (EdgeMap::next_*) instead of worked out from g
   int in_t = Map::in_tile(I, 0), out_t = Map::out_tile(I, 0);
+  // Whether this call's quiet runs may carry on over the end of a block (the QUIET RUN below): the group's stages have nothing
+  // to do there, the launch is an ordinary one (a resident call is one block), and every tile of a block is whole
+  // (full == tpb follows).  wrap_gap: the absolute frames between a block's last frame and the next block's first one.
+  constexpr bool CROSS = !ChainT::kBlockWork;
+  const bool cross_ok = CROSS && !resident && n_frames != 0u && n_frames % (u32)T == 0u;
+  const u32 wrap_gap = a.block_size - n_frames;
 #ifdef KNH_DAG_STAMPS  // diagnostic build only: cycles this wavefront is busy per tile (tools/pipe_stamps.py)
   u64 busy = 0, busy_in = 0, busy_out = 0, busy_tick = 0, busy_fold = 0;
 #endif
@@ -302,85 +311,122 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
       const u32 n = n_tile + fo;                                                            // the window's first frame
       apply_events_upto(base + n);  // (a Fan wavefront: also the changes inside the part of the tile before its window)
       const bool ev_inside = next_frame < base + n + TW;
-      bool step_open = true;  // this step's barrier is still to come
+      bool step_open = true;  // this step's barrier is still to come (false only behind a run of a group that ends its runs with the block)
       if (__builtin_expect(ti < full && !__builtin_amdgcn_ballot_w64(ev_inside), 1)) {  // (the cold paths out of line: one instruction cache for all roles)
-        // A QUIET RUN: consecutive tiles of this block that are whole and have no event of any lane inside them.  No event is
-        // applied between them, so what the stages choose per tile from their parameters is chosen once (Chain::prepare_run),
-        // and a tile is nothing but: its LDS reads, the stages, its LDS stores, the step barrier, the advance.  This is the only
-        // place the fast tile body exists, a run of one tile included.
+        // A QUIET RUN: consecutive tiles that are whole and have no event of any lane inside them.  No event is applied between
+        // them, so what the stages choose per tile from their parameters is chosen once (Chain::prepare_run), and a tile is
+        // nothing but: its LDS reads, the stages, its LDS stores, the step barrier, the advance.  This is the only place the
+        // fast tile body exists, a run of one tile included.
+        // The run ends where a lane's next event is due before the end of the next tile -- `due`, in absolute frames -- or with
+        // the block's whole tiles.  A group without block work (cross_ok; and no voice whose begin_block would still change
+        // something: block_begun) carries on from a block's last tile into tile 0 of the next block of the launch instead:
+        // the frame goes back to the launch's first, blk and base move on, and nothing else happens.  Today's block end applies
+        // what is due up to the block's last frame + 1 (the end itself included) and the next tile's head what is due up to its
+        // first frame; both lie before the end of that tile, so the one test `next_frame < due` covers them and the tile, and
+        // a run with anything due there ends at the block's end as it always did.
         const typename ChainT::RunPrep prep = chain.prepare_run();
+        int cross_left = 0;  // the block ends this run may still carry on over: those of the launch that lie ahead, or none
+        if constexpr (CROSS) {
+          if (cross_ok && !__builtin_amdgcn_ballot_w64(!chain.block_begun(fbeg))) cross_left = (int)a.n_blocks - 1 - blk;
+        }
         u32 nq = n;
-        for (;;) {
+        u32 due = base + n + (u32)TW;  // the end of this wavefront's window of the tile at hand; from the advance on, of the next tile
+        for (;;) {  // the blocks of the run
+          for (;;) {  // the tiles of the run inside one block
 #ifdef KNH_DAG_STAMPS
-          const u64 q0 = __builtin_amdgcn_s_memtime();
+            const u64 q0 = __builtin_amdgcn_s_memtime();
 #endif
-          F x[TW];
-          if (I > 0) {
-            const Vec* in = reinterpret_cast<const Vec*>(sh.edge + (long)in_t * EdgeLayout<F, T>::tile + (long)lane * EdgeLayout<F, T>::stride + fo);
+            F x[TW];
+            if (I > 0) {
+              const Vec* in = reinterpret_cast<const Vec*>(sh.edge + (long)in_t * EdgeLayout<F, T>::tile + (long)lane * EdgeLayout<F, T>::stride + fo);
+#pragma unroll
+              for (int j = 0; j < TW / VW; ++j) {
+                const Vec v = in[j];
+#pragma unroll
+                for (int k = 0; k < VW; ++k) x[j * VW + k] = v[k];
+              }
+            } else {
+#pragma unroll
+              for (int j = 0; j < TW; ++j) x[j] = (F)0;
+            }
+#if defined(KNH_DAG_STAMPS) || defined(KNH_TILE_FENCES)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#endif
+#ifdef KNH_DAG_STAMPS
+            const u64 q1 = __builtin_amdgcn_s_memtime();
+            busy_in += q1 - q0;
+#endif
+            chain.template tick_tile_run<TW>(x, ctx, nq, prep);
+#ifdef KNH_DAG_STAMPS
+            asm volatile("" ::: "memory");
+            const u64 q2 = __builtin_amdgcn_s_memtime();
+            busy_tick += q2 - q1;
+#endif
+            F* const out_tile = sh.edge + (long)out_t * EdgeLayout<F, T>::tile;
+            F* const out_row = out_tile + (long)lane * EdgeLayout<F, T>::stride + fo;
+            Vec* out = reinterpret_cast<Vec*>(out_row);  // 16-byte LDS stores
 #pragma unroll
             for (int j = 0; j < TW / VW; ++j) {
-              const Vec v = in[j];
+              Vec v;
 #pragma unroll
-              for (int k = 0; k < VW; ++k) x[j * VW + k] = v[k];
+              for (int k = 0; k < VW; ++k) v[k] = x[j * VW + k];
+              out[j] = v;
             }
-          } else {
-#pragma unroll
-            for (int j = 0; j < TW; ++j) x[j] = (F)0;
-          }
+            if constexpr (GroupInfo<G>::pan) {  // (as below)
+              F gl = (F)0, gr = (F)0;
+              chain.pan_gains(gl, gr);
+              out_row[T] = gl;
+              out_row[T + 1] = gr;
+            }
+#ifdef KNH_DAG_STAMPS
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            const u64 qf = __builtin_amdgcn_s_memtime();
+#endif
+            if constexpr (FOLDS) pipe_fold_tile<F, FMA, T, GroupInfo<G>::pan>(out_tile, a, lane, wave_global, n_waves_total, blk, nq, (u32)T, v0, nv);  // (fo == 0)
+#ifdef KNH_DAG_STAMPS
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            const u64 qe = __builtin_amdgcn_s_memtime();
+            busy_fold += qe - qf;
+#endif
+            in_t = Map::next_in(I, in_t);
+            out_t = Map::next_out(I, out_t);
+            nq += (u32)T;
+            due += (u32)T;
+            ++ti;
 #if defined(KNH_DAG_STAMPS) || defined(KNH_TILE_FENCES)
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
 #ifdef KNH_DAG_STAMPS
-          const u64 q1 = __builtin_amdgcn_s_memtime();
-          busy_in += q1 - q0;
+            const u64 q3 = __builtin_amdgcn_s_memtime();
+            busy_out += q3 - qe;
+            busy += q3 - q0;
 #endif
-          chain.template tick_tile_run<TW>(x, ctx, nq, prep);
-#ifdef KNH_DAG_STAMPS
-          asm volatile("" ::: "memory");
-          const u64 q2 = __builtin_amdgcn_s_memtime();
-          busy_tick += q2 - q1;
-#endif
-          F* const out_tile = sh.edge + (long)out_t * EdgeLayout<F, T>::tile;
-          F* const out_row = out_tile + (long)lane * EdgeLayout<F, T>::stride + fo;
-          Vec* out = reinterpret_cast<Vec*>(out_row);  // 16-byte LDS stores
-#pragma unroll
-          for (int j = 0; j < TW / VW; ++j) {
-            Vec v;
-#pragma unroll
-            for (int k = 0; k < VW; ++k) v[k] = x[j * VW + k];
-            out[j] = v;
+            if constexpr (CROSS) {
+              // The run ends here, in front of this tile's barrier (the tile loop's end meets it), or goes on behind it.  (The test
+              // reads registers only, so it may stand on either side of the barrier; in front of it, every way out of the run
+              // leaves the same thing to do, and the loop carries no flag for it.)
+              if (ti >= full) break;  // no whole tile left in the block
+              if (__builtin_amdgcn_ballot_w64(next_frame < due)) break;
+              pipe_barrier();
+            } else {
+              // A group whose runs end with their block keeps the loop it had, test behind the barrier and all: C2's ten
+              // wavefronts to four SIMDs measured 0.6 % slower kernel-only with the test in front, every run of three below every run of
+              // the parent (profiles/r13_runs_across_blocks_ab.json, event_test_in_front_of_the_barrier_in_every_group).
+              if (ti >= full) break;  // no whole tile left in the block: the step's barrier is the tile loop's
+              pipe_barrier();
+              if (__builtin_amdgcn_ballot_w64(next_frame < base + nq + TW)) { step_open = false; break; }
+            }
           }
-          if constexpr (GroupInfo<G>::pan) {  // (as below)
-            F gl = (F)0, gr = (F)0;
-            chain.pan_gains(gl, gr);
-            out_row[T] = gl;
-            out_row[T + 1] = gr;
-          }
-#ifdef KNH_DAG_STAMPS
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          const u64 qf = __builtin_amdgcn_s_memtime();
-#endif
-          if constexpr (FOLDS) pipe_fold_tile<F, FMA, T, GroupInfo<G>::pan>(out_tile, a, lane, wave_global, n_waves_total, blk, nq, (u32)T, v0, nv);  // (fo == 0)
-#ifdef KNH_DAG_STAMPS
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          const u64 qe = __builtin_amdgcn_s_memtime();
-          busy_fold += qe - qf;
-#endif
-          in_t = Map::next_in(I, in_t);
-          out_t = Map::next_out(I, out_t);
-          nq += (u32)T;
-          ++ti;
-#if defined(KNH_DAG_STAMPS) || defined(KNH_TILE_FENCES)
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-#ifdef KNH_DAG_STAMPS
-          const u64 q3 = __builtin_amdgcn_s_memtime();
-          busy_out += q3 - qe;
-          busy += q3 - q0;
-#endif
-          if (ti >= full) break;  // no whole tile left in the block: the step's barrier is the tile loop's
+          // (out here, so that the loop over a block's tiles stays what it was: the advance, one test, the barrier)
+          if (!CROSS || ti < full || cross_left == 0) break;  // an event inside the block, or no block to carry on into
+          --cross_left;
+          due += wrap_gap;  // the next tile is tile 0 of the next block
+          if (__builtin_amdgcn_ballot_w64(next_frame < due)) break;  // something is due at the block's end or up to the end of that tile: the block ends as ever
+          nq = fbeg + fo;
+          ti = 0;
+          ++blk;
+          base += a.block_size;
           pipe_barrier();
-          if (__builtin_amdgcn_ballot_w64(next_frame < base + nq + TW)) { step_open = false; break; }
         }
       } else {
         const u32 m_tile = fend - n_tile < (u32)T ? fend - n_tile : (u32)T;

@@ -80,6 +80,14 @@ struct StageDefaults {
   // pipeline evaluates prepare_run once per quiet run of tiles (voice_pipe.hpp: consecutive tiles with no event applied
   // between them) and hands the result to tick_tile_prepared for each tile of the run.  Only Svf has one.
   static constexpr bool kHasRunPrep = false;
+  // Whether the stage has work to do where one block of a launch ends and the next begins: a pointer to bind
+  // (Chain::begin_block), registers that follow the block, anything in its tile code that reads the block's input or ring.
+  // A quiet run of a group none of whose stages has any carries on over the block's end into the next block of the launch
+  // (voice_pipe.hpp); any other group's runs end with the block.  "It has" unless the stage says otherwise: a stage says
+  // `false` only after its begin_block and the pipeline's block-end path have been read and found to do nothing for it.
+  // An envelope's `seg` counts as nothing: begin_block sets it to the launch's first frame, which it already is unless a
+  // queued change has moved it inside this block -- and then the run stays in its block (Chain::block_begun).
+  static constexpr bool kHasBlockWork = true;
   // An envelope that is a SOURCE of the voice (KNH_STAGE_FLAG_ENV_SOURCE): it marks done like any envelope (kIsEnv), but it
   // silences nothing, so "the voice's last envelope has stopped" (ALL_DONE, the running counts) passes it by.
   static constexpr bool kEnvSource = false;
@@ -134,6 +142,10 @@ struct SinWtT : StageDefaults {
   static constexpr bool kIsEnv = false;
   static constexpr bool kNeedsBind = false;
   static constexpr bool kHasSeg = false;
+  // nothing to bind, no frame read: the phase runs on.  Read for both forms of the template -- SinWtAr's tile code takes its
+  // increment from the running signal, sample by sample, and reads no more of the block than SinWt's -- and for OscWtLdsT
+  // below, which inherits this: SinWt's code on five slots.
+  static constexpr bool kHasBlockWork = false;
   template <typename F> struct Regs { u32 phase, off, inc; };
   static constexpr u32 kParamMask = AR_FREQ ? 0b010u : 0b110u;  // phase_offset, and the increment unless the signal drives it
   template <typename R> static __device__ __forceinline__ void take_params(R& r, const R& n, bool c) {
@@ -308,7 +320,7 @@ typedef OscWtT<true> OscWtAr;
 // writes them as for the gather) and ignored: whatever the frequency, the one table is read.
 template <bool AR_FREQ>
 struct OscWtLdsT : SinWtT<AR_FREQ> {
-  static constexpr int kSlots = 5;
+  static constexpr int kSlots = 5;  // (kHasBlockWork: SinWtT's `false`, inherited on purpose -- the table it reads is staged once per launch)
   static constexpr u32 kParamMask = SinWtT<AR_FREQ>::kParamMask | 0b11000u;  // a patch of the two unused words changes nothing, at any frame
   template <typename F>
   static __device__ __forceinline__ void on_event(typename SinWtT<AR_FREQ>::template Regs<F>& r, u32 op, u32 rel, u64 bits, u32 frame) {
@@ -1218,6 +1230,7 @@ struct Svf : StageDefaults {
   static constexpr bool kIsEnv = false;
   static constexpr bool kNeedsBind = false;
   static constexpr bool kHasSeg = false;
+  static constexpr bool kHasBlockWork = false;  // state and coefficients only; the step chosen per run holds over a block's end (prepare_run)
   // nl ("not low"): zero iff the output mix is the low-pass one (m0 = 0, m1 = 0, m2 = 1 to the bit), kept beside the three so
   // that the per-tile choice of the step (low_pass() below) looks at one register, not at three that are otherwise idle in
   // that step.  m0 is NOT next to m1, m2 on purpose: as neighbours the three were accessed as overlapping two-float vectors
@@ -1466,7 +1479,8 @@ struct Svf : StageDefaults {
   // The choice of the step holds for a whole quiet run of tiles (voice_pipe.hpp), not only for one tile: nl changes with an
   // event only, and no step -- the low-pass one or the general one -- ever leaves ic2 = -0 behind (above), so `low` stays
   // true from tile to tile; a run that starts with ic2 = -0 (right after a load or a SET) evaluates false and takes the
-  // general step, which is right for any state, until the run ends.
+  // general step, which is right for any state, until the run ends.  Nothing in this speaks of the block: its end neither
+  // writes nl nor touches the state, so the choice also holds for a run that carries on into the launch's next block.
   static constexpr bool kHasRunPrep = true;
   template <typename F> static __device__ __forceinline__ bool prepare_run(const Regs<F>& r) { return low_pass(r); }
   template <typename F, bool FMA, int T>
@@ -1507,6 +1521,7 @@ struct SvfP : Svf {
   static constexpr int kSlots = 12;
   static constexpr u32 kParamMask = 0u;  // (graph-shaped voices only: no mid-tile parameter switching there)
   static constexpr bool kHasRunPrep = false;  // (its tick_tile is the per-sample loop below, not Svf's choice of step)
+  static constexpr bool kHasBlockWork = true;  // (graph-shaped voices only: no pipeline group holds one, so nothing was read for it)
   template <typename F> struct Regs : Svf::Regs<F> { F cutoff, q, gain; u32 ty; };
   template <typename F, typename W>
   static __device__ __forceinline__ void load(Regs<F>& r, const W* s, long st) {
@@ -1631,6 +1646,12 @@ struct MulEnvT : StageDefaults {
   static constexpr bool kIsEnv = true;
   static constexpr bool kNeedsBind = false;
   static constexpr bool kHasSeg = true;  // r.seg: start of the (partial) block, for mark_done
+  // begin_block writes seg = the launch's first frame: the same value block after block, unless an EV_SPLIT change has moved
+  // seg inside the current block.  A run carries on over a block's end only while seg is that value (Chain::block_begun);
+  // the tile code reads the frame for the done mark alone, and the run hands it the frame in the new block.  Read for
+  // EnvAsr and EnvAr (MulAsr, MulAr: the AR form differs where an attack arrives, not in what it reads) and for the
+  // envelope sources below (EnvSrcT: the same registers, begin_block and tile code with the sample written, not multiplied in).
+  static constexpr bool kHasBlockWork = false;
   template <typename F> struct Regs { u32 state; F t, ar, rr, scale; u32 seg; };
   // the two rates; `seg` (where the node's partial block began, set by any change that came out of a WrPreciseTiming
   // queue) moves with them
@@ -1878,6 +1899,8 @@ template <bool AR>
 struct EnvSrcT : MulEnvT<AR> {
   typedef MulEnvT<AR> Base;
   static constexpr bool kEnvSource = true;
+  // (kHasBlockWork: MulEnvT's `false`, inherited on purpose -- seg is its only per-block register, and Chain::block_begun asks
+  // about it for every kIsEnv && kHasSeg stage, this one included)
   template <typename F, bool FMA>
   static __device__ __forceinline__ F tick(typename Base::template Regs<F>& r, F, const Ctx&, u32 frame, u32& done_frame) {
     return Base::template env_next<F>(r, frame, done_frame);
@@ -2522,6 +2545,7 @@ struct ValT : StageDefaults {
   static constexpr bool kIsEnv = false;
   static constexpr bool kNeedsBind = false;
   static constexpr bool kHasSeg = false;
+  static constexpr bool kHasBlockWork = false;  // one value, applied sample by sample
   template <typename F> struct Regs { F v; };
   static constexpr u32 kParamMask = 0b1u;
   template <typename R> static __device__ __forceinline__ void take_params(R& r, const R& n, bool c) { r.v = c ? n.v : r.v; }
@@ -2626,6 +2650,7 @@ struct Pan2 : StageDefaults {
   static constexpr bool kIsEnv = false;
   static constexpr bool kNeedsBind = false;
   static constexpr bool kHasSeg = false;
+  static constexpr bool kHasBlockWork = false;  // two gains that only an event changes; every tile of a run writes them into its row
   template <typename F> struct Regs { F l, r; };
   template <typename F, typename W>
   static __device__ __forceinline__ void load(Regs<F>& r, const W* s, long st) { r.l = word_to_f<F>(s[0]); r.r = word_to_f<F>(s[st]); }
