@@ -38,6 +38,7 @@ struct Chain<F, FMA, BASE> {
   template <typename W> __device__ __forceinline__ void store(W*, long) const {}
   __device__ __forceinline__ F tick(F x, const Ctx&, u32) { return x; }
   template <int T> __device__ __forceinline__ void tick_tile(F (&)[T], const Ctx&, u32) {}
+  static constexpr bool kRunFixed = false;
   struct RunPrep {};
   __device__ __forceinline__ RunPrep prepare_run() const { return RunPrep(); }
   template <int T> __device__ __forceinline__ void tick_tile_run(F (&)[T], const Ctx&, u32, const RunPrep&) {}
@@ -117,6 +118,14 @@ struct Chain<F, FMA, BASE, S0, Rest...> {
     rest.template tick_tile_stamped<T>(x, c, frame0, acc + 1, t_prev);
   }
 #endif
+  // A chain that is ONE stage whose tile step can keep its registers in place over a quiet run (StageDefaults::kRunFixed: a
+  // filter alone in its stage group): the run brings them there once, runs its tiles on them -- the stage's choice of step
+  // (RunPrep::mine) is the run's, at compile time -- and takes them out once.
+  static constexpr bool kRunFixed = sizeof...(Rest) == 0 && S0::template kRunFixed<F, FMA>;
+  typedef S0 Stage0;
+  template <typename Q> __device__ __forceinline__ void enter_run(Q& q) const { S0::run_enter(r, q); }
+  template <int T, bool LOW, typename Q> __device__ __forceinline__ void tick_tile_fixed(Q& q, F (&x)[T]) { S0::template tick_tile_fixed<T, LOW>(r, q, x); }
+  template <typename Q> __device__ __forceinline__ void leave_run(Q& q) { S0::run_leave(r, q); }
   // A tile in which voices change parameters at frames of their own: `cn` holds each voice's registers with its changes
   // applied, `sw` the tile-relative frame at which the voice takes them over (T: never), `touched` the slots its changes
   // address.  A stage none of whose slots is touched in the whole wave runs its ordinary tile code.

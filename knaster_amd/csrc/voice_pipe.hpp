@@ -90,16 +90,37 @@ template <int MODE, int NG> struct EdgeMap {
   }
   static __device__ __forceinline__ int in_tile(int I, int g) { return I > 0 ? out_tile(I - 1, g) : 0; }
   static __device__ __forceinline__ int mixer_tile(int g) { return out_tile(NG - 1, g); }
-  // ... and, given the buffer of its tile g, that of its tile g + 1: the loops carry the buffer from tile to tile with these (a
-  // flipped bit -- I * 2 is even -- or a count that wraps at three) instead of dividing g
-  static __device__ __forceinline__ int next_out(int I, int t) {
-    if (MODE == PIPE_FOLD && I == NG - 1) return t;
-    if (MODE == PIPE_INPLACE && I >= NG - 2) return t == (NG - 2) * 2 + 2 ? (NG - 2) * 2 : t + 1;
-    return t ^ 1;
+  // ... and, given where its tile g lies, where its tile g + 1 does.  The loops carry not the buffer's index but a PLACE in it
+  // from tile to tile -- the LDS byte address of a lane's row (the stage groups), the tile's element offset (the mixer) -- so
+  // that a tile costs no division of g, no multiply by the buffer size and no add of the row.  `p0` is that place in buffer 0
+  // and `tb` a buffer's size, in the unit of the place.
+  // A double buffer flips between two places (an xor with the two xor-ed, a value that stays put: one instruction),
+  // the in-place edge's three rotate (a step on, or back to the first from the last), a private buffer stays where it is.
+  static __device__ __forceinline__ u32 out_place(int I, int g, u32 p0, u32 tb) { return p0 + (u32)out_tile(I, g) * tb; }
+  static __device__ __forceinline__ u32 in_place(int I, int g, u32 p0, u32 tb) { return p0 + (u32)in_tile(I, g) * tb; }
+  static __device__ __forceinline__ u32 next_out_place(int I, u32 p, u32 p0, u32 tb) {
+    if (MODE == PIPE_FOLD && I == NG - 1) return p;
+    if (MODE == PIPE_INPLACE && I >= NG - 2) return p == p0 + (u32)((NG - 2) * 2 + 2) * tb ? p0 + (u32)((NG - 2) * 2) * tb : p + tb;
+    return p ^ ((p0 + (u32)(2 * I) * tb) ^ (p0 + (u32)(2 * I + 1) * tb));
   }
-  static __device__ __forceinline__ int next_in(int I, int t) { return I > 0 ? next_out(I - 1, t) : 0; }
-  static __device__ __forceinline__ int next_mixer(int t) { return next_out(NG - 1, t); }
+  static __device__ __forceinline__ u32 next_in_place(int I, u32 p, u32 p0, u32 tb) { return I > 0 ? next_out_place(I - 1, p, p0, tb) : p; }
+  static __device__ __forceinline__ u32 next_mixer_place(u32 p, u32 p0, u32 tb) { return next_out_place(NG - 1, p, p0, tb); }
 };
+// The minimum of a value over the 64 lanes of a wavefront, all of them active, as a uniform value: four shifts within the rows
+// of sixteen lanes (a lane that has no neighbour that far down keeps the identity), the rows' last lanes handed on to the next
+// row and to the upper half (row_bcast:15, row_bcast:31), and lane 63 read.  Six v_min_u32 with a DPP operand and a readlane.
+__device__ __forceinline__ u32 wave_min_u32(u32 v) {
+  const int id = (int)0xFFFFFFFFu;
+#define KNH_MIN_STEP(ctrl, rows) { const u32 o = (u32)__builtin_amdgcn_update_dpp(id, (int)v, ctrl, rows, 0xf, false); v = o < v ? o : v; }
+  KNH_MIN_STEP(0x111, 0xf)  // row_shr:1
+  KNH_MIN_STEP(0x112, 0xf)  // row_shr:2
+  KNH_MIN_STEP(0x114, 0xf)  // row_shr:4
+  KNH_MIN_STEP(0x118, 0xf)  // row_shr:8 -- lane 15 of every row holds the row's minimum
+  KNH_MIN_STEP(0x142, 0xa)  // row_bcast:15 into rows 1 and 3
+  KNH_MIN_STEP(0x143, 0xc)  // row_bcast:31 into rows 2 and 3
+#undef KNH_MIN_STEP
+  return (u32)__builtin_amdgcn_readlane((int)v, 63);
+}
 // The pipeline's step barrier.  Its wavefronts run different code (one role each) and reach the barrier from different call
 // sites; what is relied on is the HARDWARE barrier of gfx950 -- s_barrier counts the wavefronts of the workgroup that have
 // arrived, wherever in the program each one is -- not HIP's __syncthreads(), whose contract speaks of one call site reached
@@ -273,8 +294,12 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
   // EVERY WAVEFRONT OF THE WORKGROUP ARRIVES AT EXACTLY n_steps STEP BARRIERS PER CALL.  Here that is: I in the loop in front,
   // one per tile -- a tile of a quiet run meets its barrier inside the run, except the run's last tile, whose barrier (like
   // that of every tile of the general paths) is the one at the end of the tile loop: a run is left in front of its last
-  // tile's barrier (a group whose runs end with their block, which keeps the older loop, also leaves behind it when an event
-  // ends the run: `step_open` says which) -- and n_steps - I - n_tiles in the loop behind.  A Fan group's wavefronts each make the
+  // tile's barrier, where its one test `due > lim` stands (a group whose runs end with their block, which keeps the older
+  // loop, leaves there when the block's whole tiles are done, `ti >= full`, and behind the barrier when an event ends the
+  // run, `min_next < due`: `step_open` says which) -- and n_steps - I - n_tiles in the loop behind.  A group that takes a
+  // tile's barrier at the head of the next tile (LEAD, below) makes the same count in other places: I - 1 in the loop in
+  // front, one at the head of every tile (the first tile's is the I-th of the loop in front, the others' are their
+  // predecessors'), none behind a tile, and the last tile's as the first of the loop behind.  A Fan group's wavefronts each make the
   // same steps (their tiles are windows of the same tiles); a folding group (PIPE_FOLD) folds inside its step; the mixer
   // (pipe_run_mixer) and the dead group of the two-group form (voice_pipe_kernel) count the same n_steps.
   // A quiet run that carries on from the last tile of one block into tile 0 of the next (below) changes none of this: it
@@ -286,18 +311,35 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
   const u32 n_waves_total = (a.n_voices + 63u) / 64u;
   // the first `full` tiles of a block are those this wavefront's window lies wholly inside (m == TW below)
   const int full = n_frames >= fo + (u32)TW ? (int)((n_frames - fo - (u32)TW) / (u32)T) + 1 : 0;
-  // the buffers of this group's next tile, carried from tile to tile (EdgeMap::next_*) instead of worked out from g
-  int in_t = Map::in_tile(I, 0), out_t = Map::out_tile(I, 0);
+  // Where this lane's row (its window of it) lies in the buffers of this group's next tile: LDS byte addresses, carried from tile
+  // to tile (EdgeMap::next_*_place) instead of worked out from g or from a buffer index.  The run's tiles use them as they are;
+  // the general paths make their pointers from them (row_at).
+  typedef __attribute__((address_space(3))) char* lds_bytes_t;
+  constexpr u32 TB = (u32)(EdgeLayout<F, T>::tile * (int)sizeof(F));  // a buffer, in bytes
+  const u32 edge_a = (u32)(unsigned long)(lds_bytes_t)sh.edge;
+  const u32 row_b = (u32)(lane * EdgeLayout<F, T>::stride) * (u32)sizeof(F) + fo * (u32)sizeof(F);
+  // They hold the places of the group's LAST tile, and every tile begins by stepping them on: a tile then leaves nothing to do
+  // behind its stores, whichever way the loops go on from there.  (In front of tile 0 that is tile -1's place, which is tile
+  // 5's: the buffers come round with a period of two or of three.)
+  u32 in_a = Map::in_place(I, 5, edge_a + row_b, TB), out_a = Map::out_place(I, 5, edge_a + row_b, TB);
+  auto row_at = [&](u32 addr) -> F* { return reinterpret_cast<F*>(reinterpret_cast<char*>(sh.edge) + (addr - edge_a)); };
   // Whether this call's quiet runs may carry on over the end of a block (the QUIET RUN below): the group's stages have nothing
   // to do there, the launch is an ordinary one (a resident call is one block), and every tile of a block is whole
   // (full == tpb follows).  wrap_gap: the absolute frames between a block's last frame and the next block's first one.
   constexpr bool CROSS = !ChainT::kBlockWork;
+  // LEAD: this group meets a tile's step barrier at the HEAD of the next tile, not behind the tile (the last tile's with the
+  // barriers behind the tile loop).  The same barriers at the same places between the tiles; what changes is where the run's
+  // tile loop is entered and left: barrier, tile, test -- a loop whose one way out is its back edge's test, in front of the
+  // barrier as before.  (Left between the test and the barrier, as the other groups' loop is, the compiler's code carries a
+  // flag round the loop for the way out: five instructions per tile.)  Group 0 has no barrier in front of its first tile to
+  // take for it and keeps the loop with the barrier behind the tile; so does a group whose runs end with their block.
+  constexpr bool LEAD = CROSS && I > 0;
   const bool cross_ok = CROSS && !resident && n_frames != 0u && n_frames % (u32)T == 0u;
   const u32 wrap_gap = a.block_size - n_frames;
 #ifdef KNH_DAG_STAMPS  // diagnostic build only: cycles this wavefront is busy per tile (tools/pipe_stamps.py)
   u64 busy = 0, busy_in = 0, busy_out = 0, busy_tick = 0, busy_fold = 0;
 #endif
-  for (int s = 0; s < I; ++s) pipe_barrier();
+  for (int s = LEAD ? 1 : 0; s < I; ++s) pipe_barrier();
   for (int blk = 0, ti = 0; blk < (tpb > 0 ? (int)a.n_blocks : 0); ++blk) {
     ctx.input_block = reinterpret_cast<const F*>(a.input) + (long)blk * a.in_channels * a.block_size;
     chain.begin_block(fbeg, ctx);
@@ -322,23 +364,43 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
         // something: block_begun) carries on from a block's last tile into tile 0 of the next block of the launch instead:
         // the frame goes back to the launch's first, blk and base move on, and nothing else happens.  Today's block end applies
         // what is due up to the block's last frame + 1 (the end itself included) and the next tile's head what is due up to its
-        // first frame; both lie before the end of that tile, so the one test `next_frame < due` covers them and the tile, and
-        // a run with anything due there ends at the block's end as it always did.
+        // first frame; both lie before the end of that tile, so the one test `next_frame < due` (of every lane; below: of the
+        // lanes' minimum) covers them and the tile, and a run with anything due there ends at the block's end as it always did.
         const typename ChainT::RunPrep prep = chain.prepare_run();
         int cross_left = 0;  // the block ends this run may still carry on over: those of the launch that lie ahead, or none
         if constexpr (CROSS) {
           if (cross_ok && !__builtin_amdgcn_ballot_w64(!chain.block_begun(fbeg))) cross_left = (int)a.n_blocks - 1 - blk;
         }
+        // No event is applied inside a run, so every lane's next_frame stands still and "does any lane have an event before the
+        // end of the next tile" is `min over the lanes (next_frame) < due`: a scalar compare against a value found once per
+        // run -- and only by a run that goes on to a second tile (a run of one tile pays nothing for it): until then min_next
+        // is 0, which no pending event's frame is (the tile's head has applied what was due up to the tile's first frame, so
+        // every lane's next event, a dead lane's and the 0xFFFFFFFF of a lane without one included, is due at frame 1 or later),
+        // and the test that 0 fails leads to where the lanes are looked at (the ballot a run always had) and the minimum taken.
+        // A group that carries on over block ends folds "no whole tile left in the block" into the same compare: `lim` is the
+        // smaller of min_next and last_due, the end of the block's last whole tile (0 likewise until it is worked out).
+        typedef __attribute__((address_space(3))) const Vec* lds_in_t;
+        typedef __attribute__((address_space(3))) Vec* lds_out_t;
+        typedef __attribute__((address_space(3))) F* lds_row_t;
         u32 nq = n;
-        u32 due = base + n + (u32)TW;  // the end of this wavefront's window of the tile at hand; from the advance on, of the next tile
+        // (uniform values, in scalar registers, all of them)
+        u32 due = (u32)__builtin_amdgcn_readfirstlane((int)(base + n + (u32)TW));  // the end of this wavefront's window of the tile at hand; from the advance on, of the next tile
+        u32 last_due = due + (u32)(full - 1 - ti) * (u32)T;
+        u32 min_next = 0u, lim = 0u;
+        // (the run's loops, given the stages' tile code: a filter alone in its group has two forms of it, each with the loops to
+        // itself -- below)
+        auto run_tiles = [&](auto&& tick_tile) __attribute__((always_inline)) {
         for (;;) {  // the blocks of the run
           for (;;) {  // the tiles of the run inside one block
+            if constexpr (LEAD) pipe_barrier();  // the barrier of the tile before this one
 #ifdef KNH_DAG_STAMPS
             const u64 q0 = __builtin_amdgcn_s_memtime();
 #endif
             F x[TW];
+            in_a = Map::next_in_place(I, in_a, edge_a + row_b, TB);
+            out_a = Map::next_out_place(I, out_a, edge_a + row_b, TB);
             if (I > 0) {
-              const Vec* in = reinterpret_cast<const Vec*>(sh.edge + (long)in_t * EdgeLayout<F, T>::tile + (long)lane * EdgeLayout<F, T>::stride + fo);
+              const lds_in_t in = (lds_in_t)(unsigned long)in_a;  // (an LDS pointer is 32 bits wide on the device; the host pass sees 64)
 #pragma unroll
               for (int j = 0; j < TW / VW; ++j) {
                 const Vec v = in[j];
@@ -356,15 +418,13 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
             const u64 q1 = __builtin_amdgcn_s_memtime();
             busy_in += q1 - q0;
 #endif
-            chain.template tick_tile_run<TW>(x, ctx, nq, prep);
+            tick_tile(x, nq);
 #ifdef KNH_DAG_STAMPS
             asm volatile("" ::: "memory");
             const u64 q2 = __builtin_amdgcn_s_memtime();
             busy_tick += q2 - q1;
 #endif
-            F* const out_tile = sh.edge + (long)out_t * EdgeLayout<F, T>::tile;
-            F* const out_row = out_tile + (long)lane * EdgeLayout<F, T>::stride + fo;
-            Vec* out = reinterpret_cast<Vec*>(out_row);  // 16-byte LDS stores
+            const lds_out_t out = (lds_out_t)(unsigned long)out_a;  // 16-byte LDS stores
 #pragma unroll
             for (int j = 0; j < TW / VW; ++j) {
               Vec v;
@@ -375,6 +435,7 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
             if constexpr (GroupInfo<G>::pan) {  // (as below)
               F gl = (F)0, gr = (F)0;
               chain.pan_gains(gl, gr);
+              const lds_row_t out_row = (lds_row_t)(unsigned long)out_a;
               out_row[T] = gl;
               out_row[T + 1] = gr;
             }
@@ -382,17 +443,15 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             const u64 qf = __builtin_amdgcn_s_memtime();
 #endif
-            if constexpr (FOLDS) pipe_fold_tile<F, FMA, T, GroupInfo<G>::pan>(out_tile, a, lane, wave_global, n_waves_total, blk, nq, (u32)T, v0, nv);  // (fo == 0)
+            if constexpr (FOLDS) pipe_fold_tile<F, FMA, T, GroupInfo<G>::pan>(row_at(out_a - row_b), a, lane, wave_global, n_waves_total, blk, nq, (u32)T, v0, nv);  // (fo == 0)
 #ifdef KNH_DAG_STAMPS
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             const u64 qe = __builtin_amdgcn_s_memtime();
             busy_fold += qe - qf;
 #endif
-            in_t = Map::next_in(I, in_t);
-            out_t = Map::next_out(I, out_t);
             nq += (u32)T;
             due += (u32)T;
-            ++ti;
+            if constexpr (!CROSS) ++ti;  // (a group that carries on reads ti off `due` where it leaves the block's tiles)
 #if defined(KNH_DAG_STAMPS) || defined(KNH_TILE_FENCES)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
@@ -405,36 +464,83 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
               // The run ends here, in front of this tile's barrier (the tile loop's end meets it), or goes on behind it.  (The test
               // reads registers only, so it may stand on either side of the barrier; in front of it, every way out of the run
               // leaves the same thing to do, and the loop carries no flag for it.)
-              if (ti >= full) break;  // no whole tile left in the block
-              if (__builtin_amdgcn_ballot_w64(next_frame < due)) break;
-              pipe_barrier();
+              // (ONE way out of this loop, and nothing else between the stores and the barrier: what the ways out differ in is
+              // sorted out behind it, once per run and once per block end)
+              if (due > lim) break;  // an event of some lane before the end of the next tile, no whole tile left in the block -- or the run's first tile
+              if constexpr (!LEAD) pipe_barrier();
             } else {
               // A group whose runs end with their block keeps the loop it had, test behind the barrier and all: C2's ten
               // wavefronts to four SIMDs measured 0.6 % slower kernel-only with the test in front, every run of three below every run of
               // the parent (profiles/r13_runs_across_blocks_ab.json, event_test_in_front_of_the_barrier_in_every_group).
+              // Only the test itself is the scalar one.
               if (ti >= full) break;  // no whole tile left in the block: the step's barrier is the tile loop's
               pipe_barrier();
-              if (__builtin_amdgcn_ballot_w64(next_frame < base + nq + TW)) { step_open = false; break; }
+              if (min_next < due) {
+                if (min_next != 0u || __builtin_amdgcn_ballot_w64(next_frame < due)) { step_open = false; break; }
+                min_next = wave_min_u32(next_frame);
+              }
             }
           }
           // (out here, so that the loop over a block's tiles stays what it was: the advance, one test, the barrier)
-          if (!CROSS || ti < full || cross_left == 0) break;  // an event inside the block, or no block to carry on into
-          --cross_left;
-          due += wrap_gap;  // the next tile is tile 0 of the next block
-          if (__builtin_amdgcn_ballot_w64(next_frame < due)) break;  // something is due at the block's end or up to the end of that tile: the block ends as ever
-          nq = fbeg + fo;
-          ti = 0;
-          ++blk;
-          base += a.block_size;
-          pipe_barrier();
+          if (!CROSS) return;
+          if (due > last_due) {  // through with the block's whole tiles
+            ti = full;
+            if (cross_left == 0) return;  // no block to carry on into
+            --cross_left;
+            due += wrap_gap;  // the next tile is tile 0 of the next block
+            // something due at the block's end or up to the end of that tile: the block ends as ever
+            if (min_next == 0u) {  // (the run's first tile was the block's last)
+              if (__builtin_amdgcn_ballot_w64(next_frame < due)) return;
+              min_next = wave_min_u32(next_frame);
+            }
+            if (min_next < due) return;
+            last_due += a.block_size;
+            lim = min_next < last_due ? min_next : last_due;
+            nq = fbeg + fo;
+            ++blk;
+            base += a.block_size;
+          } else {  // a whole tile ahead in the block: an event inside it, or this was the run's first tile
+            // (the run's first tile: a run of one tile ends here, the minimum never taken)
+            if (lim != 0u || __builtin_amdgcn_ballot_w64(next_frame < due)) {
+              ti = full - 1 - (int)((last_due - due) / (u32)T);  // the block's tiles this group is through with
+              return;
+            }
+            // (Putting the minimum off to the run's third tile, for banks whose runs are two tiles long -- C5 -- was measured: C5
+            // level within its spread either way, the headline 0.7 % slower: profiles/r14_run_bound_ab.json, minimum_at_the_third_tile.)
+            min_next = wave_min_u32(next_frame);
+            lim = min_next < last_due ? min_next : last_due;
+          }
+          if constexpr (!LEAD) pipe_barrier();
+        }
+        };
+        if constexpr (ChainT::kRunFixed) {
+          // the filter's state and coefficients in the registers of its step from here to the run's end (Svf::run_enter)
+          typename ChainT::Stage0::RunRegs fixed;
+          chain.enter_run(fixed);
+          if (prep.mine) run_tiles([&](F (&x)[TW], u32) __attribute__((always_inline)) { chain.template tick_tile_fixed<TW, true>(fixed, x); });
+          else run_tiles([&](F (&x)[TW], u32) __attribute__((always_inline)) { chain.template tick_tile_fixed<TW, false>(fixed, x); });
+          chain.leave_run(fixed);
+        } else {
+          run_tiles([&](F (&x)[TW], u32 frame0) __attribute__((always_inline)) { chain.template tick_tile_run<TW>(x, ctx, frame0, prep); });
         }
       } else {
+        if constexpr (LEAD) {  // the barrier of the tile before this one
+#ifdef KNH_DAG_STAMPS
+          const u64 b0 = __builtin_amdgcn_s_memtime();
+          pipe_barrier();
+          busy -= __builtin_amdgcn_s_memtime() - b0;
+#else
+          pipe_barrier();
+#endif
+        }
         const u32 m_tile = fend - n_tile < (u32)T ? fend - n_tile : (u32)T;
         const u32 m = m_tile > fo ? (m_tile - fo < (u32)TW ? m_tile - fo : (u32)TW) : 0u;     // frames of the window inside the block
         // every group, the last one included, hands its tile on as 64 rows of T samples
-        F* const out_tile = sh.edge + (long)out_t * EdgeLayout<F, T>::tile;
-        F* const out_row = out_tile + (long)lane * EdgeLayout<F, T>::stride + fo;
-        const F* const in_row = sh.edge + (long)in_t * EdgeLayout<F, T>::tile + (long)lane * EdgeLayout<F, T>::stride + fo;
+        in_a = Map::next_in_place(I, in_a, edge_a + row_b, TB);
+        out_a = Map::next_out_place(I, out_a, edge_a + row_b, TB);
+        F* const out_tile = row_at(out_a - row_b);
+        F* const out_row = row_at(out_a);
+        const F* const in_row = row_at(in_a);
 #ifdef KNH_AB_NO_SW
         if (false && [&]() -> bool {
 #else
@@ -551,8 +657,6 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
         const u64 tf0 = __builtin_amdgcn_s_memtime();
 #endif
         if constexpr (FOLDS) pipe_fold_tile<F, FMA, T, GroupInfo<G>::pan>(out_tile, a, lane, wave_global, n_waves_total, blk, n_tile, m_tile, v0, nv);
-        in_t = Map::next_in(I, in_t);
-        out_t = Map::next_out(I, out_t);
         ++ti;
 #ifdef KNH_DAG_STAMPS
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -571,13 +675,16 @@ __device__ __forceinline__ u32 pipe_run_group(const PipeShared<F>& sh, const Voi
 #if defined(KNH_DAG_STAMPS) || defined(KNH_TILE_FENCES)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
-        pipe_barrier();
+        if constexpr (!LEAD) pipe_barrier();
         break;
       }
-      if (step_open) pipe_barrier();
+      if constexpr (!LEAD) {
+        if (step_open) pipe_barrier();
+      }
     }
   }
-  for (int s = I + n_tiles; s < n_steps; ++s) pipe_barrier();
+  for (int s = I + n_tiles - (LEAD && n_tiles > 0 ? 1 : 0); s < n_steps; ++s) pipe_barrier();  // (LEAD: the last tile's barrier is the first of these)
+  if (LEAD && n_tiles == 0) pipe_barrier();  // (no tile has taken the barrier the loop in front left out)
 #ifdef KNH_DAG_STAMPS
   if (wave_global == 0u && lane == 0) {
     const u64 d = (u64)(n_tiles > 0 ? n_tiles : 1);
@@ -677,7 +784,8 @@ __device__ __forceinline__ void pipe_run_mixer(const PipeShared<F>& sh, const Vo
   // The mixer is NG steps behind group 0: NG steps of waiting while the pipeline fills, then the launch's tiles block by block,
   // one per step -- fold, advance, barrier: n_tiles + NG = n_steps barriers, the stage groups' count (pipe_run_group).
   for (int s = 0; s < NG; ++s) step_barrier();
-  int mix_t = EdgeMap<MODE, NG>::mixer_tile(0);  // the buffer of the next tile, carried from tile to tile
+  constexpr u32 TE = (u32)EdgeLayout<F, T>::tile;  // a buffer, in elements
+  u32 mix_o = EdgeMap<MODE, NG>::out_place(NG - 1, 0, 0u, TE);  // where the next tile starts (elements from sh.edge), carried from tile to tile
   int g = 0;                                      // the tile the last chain group finished in the previous step
   for (int blk = 0; blk < (tpb > 0 ? (int)a.n_blocks : 0); ++blk) {
     for (u32 rel = 0; rel < n_frames; rel += (u32)T) {
@@ -685,7 +793,7 @@ __device__ __forceinline__ void pipe_run_mixer(const PipeShared<F>& sh, const Vo
       const u64 t0 = __builtin_amdgcn_s_memtime();
 #endif
       const u32 len = n_frames - rel < (u32)T ? n_frames - rel : (u32)T;
-      const F* tile = sh.edge + (long)mix_t * EdgeLayout<F, T>::tile;
+      const F* tile = sh.edge + mix_o;
       pipe_fold_tile<F, FMA, T, PAN>(tile, a, lane, wave_global, n_waves_total, blk, fbeg + rel, len, v0, nv, (u32)g, call.epoch);
       if (resident && g == n_tiles - 1) {
         // the call's last tile: every stage group is through with the call (its marks are in LDS since its last step's
@@ -702,7 +810,7 @@ __device__ __forceinline__ void pipe_run_mixer(const PipeShared<F>& sh, const Vo
         }
         if (lane == 0) res_put(a.res.wg_flags + wave_global, n_done | (n_run << 8), res_tag(call.epoch, 255u));
       }
-      mix_t = EdgeMap<MODE, NG>::next_mixer(mix_t);
+      mix_o = EdgeMap<MODE, NG>::next_mixer_place(mix_o, 0u, TE);
       ++g;
 #ifdef KNH_DAG_STAMPS
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");

@@ -80,6 +80,10 @@ struct StageDefaults {
   // pipeline evaluates prepare_run once per quiet run of tiles (voice_pipe.hpp: consecutive tiles with no event applied
   // between them) and hands the result to tick_tile_prepared for each tile of the run.  Only Svf has one.
   static constexpr bool kHasRunPrep = false;
+  // A stage whose tile step works in fixed registers and can leave its state and coefficients IN them from the first tile of a
+  // quiet run to the last (run_enter / tick_tile_fixed / run_leave: only Svf, in exact f32).  The pipeline does that for a
+  // group that is this one stage and nothing else (Chain::kRunFixed, voice_pipe.hpp).
+  template <typename F, bool FMA> static constexpr bool kRunFixed = false;
   // Whether the stage has work to do where one block of a launch ends and the next begins: a pointer to bind
   // (Chain::begin_block), registers that follow the block, anything in its tile code that reads the block's input or ring.
   // A quiet run of a group none of whose stages has any carries on over the block's end into the next block of the launch
@@ -1313,6 +1317,7 @@ struct Svf : StageDefaults {
     //   v114 v3  v[116:117] (a1, a2)  v[118:119] (a2, a3)  v[120:121] (m1, m2)  v122 m0
     float ic1 = r.ic1, ic2 = r.ic2;
     const float a1 = r.a1, a2 = r.a2, a2b = r.a2, a3 = r.a3, m0 = r.m0, m1 = r.m1, m2 = r.m2;
+    // (the step's text stays defined behind this function: tick_tile_fixed below uses it too and undefines it)
 #define KNH_SVF_STEP(K)                                                                                            \
       "v_sub_f32 v114, %[x" #K "], v101\n\t"                              /* v3 = x - ic2                     */   \
       "v_pk_mul_f32 v[102:103], v[116:117], v[100:101] op_sel_hi:[1,0]\n\t"   /* (a1*ic1, a2*ic1)             */   \
@@ -1337,7 +1342,6 @@ struct Svf : StageDefaults {
                    : "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v112", "v114", "v115");
       x[j] = y0; x[j + 1] = y1; x[j + 2] = y2; x[j + 3] = y3; x[j + 4] = y4; x[j + 5] = y5; x[j + 6] = y6; x[j + 7] = y7;
     }
-#undef KNH_SVF_STEP
     // The state leaves the fixed registers inside an asm statement, into registers of the compiler's choice.  Left to the
     // compiler (r.ic1 = ic1; r.ic2 = ic2), the copy out of v101 went missing where a loop carries the state from tile to tile
     // (the pipeline's quiet runs, a filter group with a stage in front of the filter: ic2 then never advanced from tile to
@@ -1377,6 +1381,7 @@ struct Svf : StageDefaults {
     // in one function -- inside hiprtc, and therefore inside the host process.)
     float ic1 = r.ic1, ic2 = r.ic2;
     const float a1 = r.a1, a2 = r.a2, a2b = r.a2, a3 = r.a3;
+    // (the step's text stays defined behind this function: tick_tile_fixed below uses it too and undefines it)
 #define KNH_SVF_LOW(K)                                                                                             \
       "v_sub_f32 v114, %[x" #K "], v101\n\t"                              /* v3 = x - ic2                     */   \
       "v_pk_mul_f32 v[102:103], v[116:117], v[100:101] op_sel_hi:[1,0]\n\t"   /* (a1*ic1, a2*ic1)             */   \
@@ -1398,7 +1403,6 @@ struct Svf : StageDefaults {
                    : "v102", "v103", "v104", "v105", "v106", "v107", "v114", "v115");
       x[j] = y0; x[j + 1] = y1; x[j + 2] = y2; x[j + 3] = y3; x[j + 4] = y4; x[j + 5] = y5; x[j + 6] = y6; x[j + 7] = y7;
     }
-#undef KNH_SVF_LOW
     // The state leaves the fixed registers inside an asm statement, into registers of the compiler's choice.  Left to the
     // compiler (r.ic1 = ic1; r.ic2 = ic2), the copy out of v101 went missing where a loop carries the state from tile to tile
     // (the pipeline's quiet runs, a filter group with a stage in front of the filter: ic2 then never advanced from tile to
@@ -1406,6 +1410,55 @@ struct Svf : StageDefaults {
     // tests/test_gpu_pipe_quiet_runs.py::test_a_filter_behind_a_gain_in_its_group, chains cut into Group<MulVal, Svf>.
     float o1, o2;
     asm volatile("v_mov_b32 %0, v100\n\tv_mov_b32 %1, v101" : "=&v"(o1), "=&v"(o2) : "{v100}"(ic1), "{v101}"(ic2));
+    r.ic1 = o1; r.ic2 = o2;
+  }
+  // The same two steps for a filter that is alone in its stage group, over a whole quiet run of the pipeline (voice_pipe.hpp):
+  // ic1, ic2 stay in v100, v101 and a1, a2, a2, a3 in v116 .. v119 from the run's first tile to its last.  run_enter brings
+  // them there and run_leave takes the state out, once per run, where tick_tile_low / tick_tile_packed do both once per tile
+  // (eight moves and a hazard s_nop of the filter wavefront's serial path).  They are values of the run, tied to their
+  // registers in every statement that touches them -- run_enter's moves, the steps, run_leave's moves -- and used by nothing
+  // else; the compiler has no reason to keep them anywhere else between two tiles, and where it does it copies: the bits are
+  // the same either way.  a2 is two values, one per register, made by moves the compiler does not look into (as one value it
+  // would be kept in one register and copied to the other for every tile).  The state leaves through an asm statement with
+  // ordinary outputs, as in the per-tile steps and for their reason.  Every operand is a single 32-bit register below v128.
+  template <typename F, bool FMA> static constexpr bool kRunFixed = sizeof(F) == 4 && !FMA;
+  struct RunRegs { float ic1, ic2, a1, a2, a2b, a3; };
+  static __device__ __forceinline__ void run_enter(const Regs<float>& r, RunRegs& q) {
+    asm volatile("v_mov_b32 %0, %6\n\tv_mov_b32 %1, %7\n\tv_mov_b32 %2, %8\n\tv_mov_b32 %3, %9\n\tv_mov_b32 %4, %9\n\tv_mov_b32 %5, %10"
+                 : "=&{v100}"(q.ic1), "=&{v101}"(q.ic2), "=&{v116}"(q.a1), "=&{v117}"(q.a2), "=&{v118}"(q.a2b), "=&{v119}"(q.a3)
+                 : "v"(r.ic1), "v"(r.ic2), "v"(r.a1), "v"(r.a2), "v"(r.a3));
+  }
+  template <int T, bool LOW>
+  static __device__ __forceinline__ void tick_tile_fixed(const Regs<float>& r, RunRegs& q, float (&x)[T]) {
+    static_assert(T % 8 == 0, "the filter tile is unrolled in blocks of eight samples");
+    const float m0 = r.m0, m1 = r.m1, m2 = r.m2;
+#pragma unroll
+    for (int j = 0; j < T; j += 8) {
+      float y0, y1, y2, y3, y4, y5, y6, y7;
+      if constexpr (LOW) {
+        asm volatile(KNH_SVF_LOW(0) KNH_SVF_LOW(1) KNH_SVF_LOW(2) KNH_SVF_LOW(3) KNH_SVF_LOW(4) KNH_SVF_LOW(5) KNH_SVF_LOW(6) KNH_SVF_LOW(7)
+                     : [y0] "=&v"(y0), [y1] "=&v"(y1), [y2] "=&v"(y2), [y3] "=&v"(y3), [y4] "=&v"(y4), [y5] "=&v"(y5),
+                       [y6] "=&v"(y6), [y7] "=&v"(y7), "+{v100}"(q.ic1), "+{v101}"(q.ic2)
+                     : [x0] "v"(x[j]), [x1] "v"(x[j + 1]), [x2] "v"(x[j + 2]), [x3] "v"(x[j + 3]), [x4] "v"(x[j + 4]),
+                       [x5] "v"(x[j + 5]), [x6] "v"(x[j + 6]), [x7] "v"(x[j + 7]), "{v116}"(q.a1), "{v117}"(q.a2), "{v118}"(q.a2b), "{v119}"(q.a3)
+                     : "v102", "v103", "v104", "v105", "v106", "v107", "v114", "v115");
+      } else {
+        asm volatile(KNH_SVF_STEP(0) KNH_SVF_STEP(1) KNH_SVF_STEP(2) KNH_SVF_STEP(3) KNH_SVF_STEP(4) KNH_SVF_STEP(5) KNH_SVF_STEP(6) KNH_SVF_STEP(7)
+                     : [y0] "=&v"(y0), [y1] "=&v"(y1), [y2] "=&v"(y2), [y3] "=&v"(y3), [y4] "=&v"(y4), [y5] "=&v"(y5),
+                       [y6] "=&v"(y6), [y7] "=&v"(y7), "+{v100}"(q.ic1), "+{v101}"(q.ic2)
+                     : [x0] "v"(x[j]), [x1] "v"(x[j + 1]), [x2] "v"(x[j + 2]), [x3] "v"(x[j + 3]), [x4] "v"(x[j + 4]),
+                       [x5] "v"(x[j + 5]), [x6] "v"(x[j + 6]), [x7] "v"(x[j + 7]), "{v116}"(q.a1), "{v117}"(q.a2), "{v118}"(q.a2b), "{v119}"(q.a3),
+                       "{v120}"(m1), "{v121}"(m2), "{v122}"(m0)
+                     : "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v112", "v114", "v115");
+      }
+      x[j] = y0; x[j + 1] = y1; x[j + 2] = y2; x[j + 3] = y3; x[j + 4] = y4; x[j + 5] = y5; x[j + 6] = y6; x[j + 7] = y7;
+    }
+  }
+#undef KNH_SVF_STEP
+#undef KNH_SVF_LOW
+  static __device__ __forceinline__ void run_leave(Regs<float>& r, RunRegs& q) {
+    float o1, o2;
+    asm volatile("v_mov_b32 %0, v100\n\tv_mov_b32 %1, v101" : "=&v"(o1), "=&v"(o2) : "{v100}"(q.ic1), "{v101}"(q.ic2));
     r.ic1 = o1; r.ic2 = o2;
   }
   // the same in f64: eleven instructions for the general step's fifteen, every operand at least two instructions old
@@ -1518,6 +1571,7 @@ static __device__ __forceinline__ double dev_pow(double a, double b) { return __
 // voice with such a filter is compared with the reference within a tolerance, not bit for bit.
 // slots: 0..7 as Svf, 8 cutoff, 9 q, 10 gain_db, 11 type
 struct SvfP : Svf {
+  template <typename F, bool FMA> static constexpr bool kRunFixed = false;  // (graph voices only: never alone in a pipeline's stage group)
   static constexpr int kSlots = 12;
   static constexpr u32 kParamMask = 0u;  // (graph-shaped voices only: no mid-tile parameter switching there)
   static constexpr bool kHasRunPrep = false;  // (its tick_tile is the per-sample loop below, not Svf's choice of step)
