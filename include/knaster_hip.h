@@ -722,7 +722,15 @@ int32_t knh_bank_process_block_voices(knh_bank* bank, size_t frames_to_process,
  * AudioProcessor::run_without_inputs() called n_blocks times (knaster_graph/src/processor.rs:142-179)
  * with every SchedulingEvent of those blocks known up front; changes for block k > 0 of the launch are
  * queued with knh_bank_param_apply_many_at.
- *   out / out_device: [n_blocks][out_channels][block_size] of F. */
+ *   out / out_device: [n_blocks][out_channels][block_size] of F.
+ * knh_bank_process_blocks_device[_add] enqueue and return; whatever the caller enqueues on `hip_stream` behind the call sees
+ * the mixed blocks.  A tree-mix launch of a pipelined kernel, up to 256 voice groups, runs its voice kernel and its fold on two streams of the
+ * bank's, the fold beside the next launch's voice kernel, and `hip_stream` waits for the fold.  Such a call WAITS ON THE HOST
+ * for the fold of the launch before the last one: it returns at once while the caller is no more than two launches ahead
+ * of the device, and blocks until then otherwise (a caller that enqueues many launches ahead, or drives several banks from
+ * one thread, is held to two launches in flight per bank).  KNH_FOLD_OVERLAP=0 (read when the bank is created) keeps every
+ * launch on `hip_stream` alone, and the call purely asynchronous; the results are the same bit for bit.  KNH_FOLD_WAVE=1
+ * (tests of that fold alone) gives single-stream tree folds of up to 256 rows the form without LDS the overlapped launches use. */
 int32_t knh_bank_process_blocks(knh_bank* bank, uint32_t n_blocks, uint64_t frame_clock, void* out,
                                 uint32_t* out_flags);
 int32_t knh_bank_process_blocks_device(knh_bank* bank, uint32_t n_blocks, uint64_t frame_clock,
@@ -763,7 +771,9 @@ int32_t knh_bank_read_done_frames(knh_bank* bank, uint32_t* done_frames);
  * kernel form the bank's launches take (KNH_DEBUG_FORM_*; a bank cut into voice ranges reports its first range's).
  * Word 3 is filled in by the host too: in the two lane-per-frame forms the voices per workgroup that a launch over a whole
  * block takes (a call over part of a block may take another number in the interpreted form), 0 in every other form;
- * again the first range's for a bank cut into voice ranges. */
+ * again the first range's for a bank cut into voice ranges.  In a library built without -DKNH_DAG_STAMPS (whose kernels write
+ * words 4..11) words 9 and 10 are the host's as well: how many of the bank's launches so far ran their tree fold on the
+ * bank's fold stream, beside the launch after them, and how many took the tree fold's form without LDS (the first range's). */
 enum {
   KNH_DEBUG_FORM_WHOLE_CHAIN = 0,       /* pre-built kernel, a wavefront runs a voice group's whole chain */
   KNH_DEBUG_FORM_PIPELINE = 1,          /* pre-built wave pipeline */

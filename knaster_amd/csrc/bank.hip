@@ -382,6 +382,7 @@ void knh_bank_destroy(knh_bank* bank) {
     if (bank && bank->pipe_stream) {  // launches begun and never fetched still hold the bank's buffers
       (void)hipSetDevice(bank->device);
       (void)hipStreamSynchronize(bank->pipe_stream);
+      host_pipe_streams().remove(bank->pipe_stream);
     }
     delete bank;
   } catch (...) {
@@ -640,7 +641,10 @@ int32_t knh_bank_process_blocks_begin(knh_bank* bank, uint32_t n_blocks, uint64_
     auto hip = [&](hipError_t e, const char* what) { return e == hipSuccess ? KNH_OK : bank->fail(KNH_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
     int rc = hip(hipSetDevice(bank->device), "hipSetDevice");
     if (rc != KNH_OK) return rc;
-    if (!bank->pipe_stream && (rc = hip(hipStreamCreateWithFlags(&bank->pipe_stream, hipStreamNonBlocking), "hipStreamCreate")) != KNH_OK) return rc;
+    if (!bank->pipe_stream) {
+      if ((rc = hip(hipStreamCreateWithFlags(&bank->pipe_stream, hipStreamNonBlocking), "hipStreamCreate")) != KNH_OK) return rc;
+      host_pipe_streams().add(bank->pipe_stream);
+    }
     knh_bank::PipeSlot& p = bank->pipe[(bank->pipe_head + bank->pipe_count) % 2];
     const size_t bytes = static_cast<size_t>(n_blocks) * bank->desc.out_channels * bank->block_size * (bank->desc.sample_type == KNH_F64 ? 8 : 4);
     if (bytes > p.cap) {

@@ -18,6 +18,7 @@
 //   c x.ceil()   r x.sqrt()   f x.floor()   t x.trunc()   w x.fract()   e x.exp()   (Math1UGen: one operand, no state)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 
 #include "voice_chain.hpp"
 
@@ -92,6 +93,23 @@ hipError_t launch_restart_voices(const knh_dev::RestartArgs& a, unsigned count, 
 template <typename F>
 using VoiceLaunchFn = hipError_t (*)(const knh_dev::VoiceKernelArgs<F>& args, unsigned n_wavefronts, hipStream_t stream);
 
+// Events the calling thread's next launch of a pre-built voice kernel carries in its own dispatch (hipExtLaunchKernelGGL):
+// `start` and `stop` take the kernel's begin and end with no marker packet of their own in the stream -- between two voice
+// kernels that follow each other in one hardware queue every such packet is some 6 us in which the chip does nothing
+// (profiles/r15_fold_overlap.json).  Set right before the launch (voice_bank.hpp); the launch takes them and clears them.
+struct LaunchEvents { hipEvent_t start = nullptr, stop = nullptr; };
+LaunchEvents& launch_events();  // (kernels_fold.hip)
+template <typename K, typename A>
+inline void launch_voice_kernel(K kernel, dim3 grid, dim3 block, hipStream_t stream, const A& args) {
+  LaunchEvents& ev = launch_events();
+  if (ev.start || ev.stop) {
+    hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, ev.start, ev.stop, 0, args);
+    ev = LaunchEvents{};
+  } else {
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, args);
+  }
+}
+
 struct KernelEntry {
   const char* signature;
   int n_slots;
@@ -146,6 +164,11 @@ hipError_t launch_fold_f32(bool tree, const float* rows, unsigned n_rows, unsign
 hipError_t launch_fold_f64(bool tree, const double* rows, unsigned n_rows, unsigned row_len, unsigned frame_begin,
                            unsigned frame_end, double* out, unsigned channels, unsigned out_stride, unsigned n_blocks, bool accumulate,
                            unsigned* zero_flags, hipStream_t s, const knh_dev::HostDone* host = nullptr);
+// the tree fold of 1..256 rows without LDS (fold_tree_wave_kernel): same bits; something to fold, no host hand-over
+hipError_t launch_fold_wave_f32(const float* rows, unsigned n_rows, unsigned row_len, unsigned frame_begin, unsigned frame_end, float* out,
+                                unsigned channels, unsigned out_stride, unsigned n_blocks, bool accumulate, unsigned* zero_flags, hipStream_t s);
+hipError_t launch_fold_wave_f64(const double* rows, unsigned n_rows, unsigned row_len, unsigned frame_begin, unsigned frame_end, double* out,
+                                unsigned channels, unsigned out_stride, unsigned n_blocks, bool accumulate, unsigned* zero_flags, hipStream_t s);
 
 // Host-sharded banks (host_shards.hpp): out[i] (+)= shards[0][i] + shards[1][i] + ... in shard order, for the frames
 // [frame_begin, frame_end) of every block of `block_size` frames; n = elements per shard, shard k starts at k * shard_stride.

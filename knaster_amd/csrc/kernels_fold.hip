@@ -7,6 +7,11 @@
 namespace knh {
 using namespace knh_dev;
 
+LaunchEvents& launch_events() {
+  static thread_local LaunchEvents ev;
+  return ev;
+}
+
 template <typename F>
 static hipError_t launch_fold(bool tree, const F* rows, unsigned n_rows, unsigned row_len, unsigned frame_begin, unsigned frame_end,
                               F* out, unsigned channels, unsigned out_stride, unsigned n_blocks, bool accumulate, unsigned* zero_flags,
@@ -39,6 +44,25 @@ hipError_t launch_fold_f64(bool tree, const double* rows, unsigned n_rows, unsig
                              host ? *host : HostDone{nullptr, nullptr, nullptr, 0u}, s);
 }
 
+// The tree fold of up to 256 rows in the form that needs no LDS (fold_tree_wave_kernel): what a bank launches beside the next
+// launch's voice kernel.  No host hand-over; a launch with nothing to fold is not sent here.
+template <typename F>
+static hipError_t launch_fold_wave(const F* rows, unsigned n_rows, unsigned row_len, unsigned frame_begin, unsigned frame_end, F* out,
+                                   unsigned channels, unsigned out_stride, unsigned n_blocks, bool accumulate, unsigned* zero_flags, hipStream_t s) {
+  if (frame_end <= frame_begin || n_rows == 0 || n_rows > 256 || n_blocks == 0) return hipErrorInvalidValue;
+  const unsigned grid = (frame_end - frame_begin + 63u) / 64u;
+  hipLaunchKernelGGL((fold_tree_wave_kernel<F>), dim3(grid, n_blocks), dim3(64), 0, s, rows, n_rows, row_len, frame_begin, frame_end, out,
+                     channels, out_stride, accumulate ? 1u : 0u, zero_flags);
+  return hipGetLastError();
+}
+hipError_t launch_fold_wave_f32(const float* rows, unsigned n_rows, unsigned row_len, unsigned frame_begin, unsigned frame_end, float* out,
+                                unsigned channels, unsigned out_stride, unsigned n_blocks, bool accumulate, unsigned* zero_flags, hipStream_t s) {
+  return launch_fold_wave<float>(rows, n_rows, row_len, frame_begin, frame_end, out, channels, out_stride, n_blocks, accumulate, zero_flags, s);
+}
+hipError_t launch_fold_wave_f64(const double* rows, unsigned n_rows, unsigned row_len, unsigned frame_begin, unsigned frame_end, double* out,
+                                unsigned channels, unsigned out_stride, unsigned n_blocks, bool accumulate, unsigned* zero_flags, hipStream_t s) {
+  return launch_fold_wave<double>(rows, n_rows, row_len, frame_begin, frame_end, out, channels, out_stride, n_blocks, accumulate, zero_flags, s);
+}
 
 // the fold server of a resident launch (voice_chain.hpp, res_fold_server): four wavefronts per 32 partial rows + four for the root
 hipError_t launch_res_server_f32(const knh_dev::ResServerArgs<float>& a, hipStream_t s) {

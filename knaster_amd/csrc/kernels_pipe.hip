@@ -14,7 +14,7 @@ template <typename F, bool FMA, int FORM, typename... Gs>
 static hipError_t launch_pipe(const VoiceKernelArgs<F>& args, unsigned n_wavefronts, hipStream_t stream) {
   if (n_wavefronts == 0) return hipSuccess;
   constexpr int T = FORM != PIPE_MIXER ? PipeTile<F>::big : PipeTile<F>::value;
-  hipLaunchKernelGGL((voice_pipe_kernel<F, FMA, T, FORM, 1, Gs...>), dim3(n_wavefronts), dim3(PipeWaves<T, FORM, Gs...>::value * 64), 0, stream, args);
+  launch_voice_kernel(voice_pipe_kernel<F, FMA, T, FORM, 1, Gs...>, dim3(n_wavefronts), dim3(PipeWaves<T, FORM, Gs...>::value * 64), stream, args);
   return hipGetLastError();
 }
 // Two 64-voice groups per workgroup, short tiles (32 samples, f64: 16), the last stage group in place and a mixer wavefront
@@ -23,8 +23,8 @@ template <typename F, bool FMA, typename... Gs>
 static hipError_t launch_pipe_pair(const VoiceKernelArgs<F>& args, unsigned n_wavefronts, hipStream_t stream) {
   if (n_wavefronts == 0) return hipSuccess;
   constexpr int T = PipeTile<F>::value;
-  hipLaunchKernelGGL((voice_pipe_kernel<F, FMA, T, PIPE_INPLACE, 2, Gs...>), dim3((n_wavefronts + 1u) / 2u),
-                     dim3(2 * PipeWaves<T, PIPE_INPLACE, Gs...>::value * 64), 0, stream, args);
+  launch_voice_kernel(voice_pipe_kernel<F, FMA, T, PIPE_INPLACE, 2, Gs...>, dim3((n_wavefronts + 1u) / 2u),
+                      dim3(2 * PipeWaves<T, PIPE_INPLACE, Gs...>::value * 64), stream, args);
   return hipGetLastError();
 }
 // 64-sample tiles (32 for f64) WITH a mixer wavefront: for pipelines with a Fan group (the fold costs the same per
@@ -33,7 +33,7 @@ template <typename F, bool FMA, typename... Gs>
 static hipError_t launch_pipe_wide_tile(const VoiceKernelArgs<F>& args, unsigned n_wavefronts, hipStream_t stream) {
   if (n_wavefronts == 0) return hipSuccess;
   constexpr int T = PipeTile<F>::big;
-  hipLaunchKernelGGL((voice_pipe_kernel<F, FMA, T, PIPE_MIXER, 1, Gs...>), dim3(n_wavefronts), dim3(PipeWaves<T, PIPE_MIXER, Gs...>::value * 64), 0, stream, args);
+  launch_voice_kernel(voice_pipe_kernel<F, FMA, T, PIPE_MIXER, 1, Gs...>, dim3(n_wavefronts), dim3(PipeWaves<T, PIPE_MIXER, Gs...>::value * 64), stream, args);
   return hipGetLastError();
 }
 #define KNH_PIPE_FAN(sig, n, ...)                                                                                       \

@@ -11,7 +11,7 @@ using namespace knh_dev;
 template <typename F, bool FMA, typename... S>
 static hipError_t launch_voice(const VoiceKernelArgs<F>& args, unsigned n_wavefronts, hipStream_t stream) {
   if (n_wavefronts == 0) return hipSuccess;
-  hipLaunchKernelGGL((voice_kernel<F, FMA, 1, S...>), dim3(n_wavefronts), dim3(64), 0, stream, args);
+  launch_voice_kernel(voice_kernel<F, FMA, 1, S...>, dim3(n_wavefronts), dim3(64), stream, args);
   return hipGetLastError();
 }
 

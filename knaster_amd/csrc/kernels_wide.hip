@@ -11,7 +11,7 @@ using namespace knh_dev;
 template <typename F, bool FMA, int WAVES, typename... S>
 static hipError_t launch_wide(const VoiceKernelArgs<F>& args, unsigned n_wavefronts, hipStream_t stream) {
   if (n_wavefronts == 0) return hipSuccess;
-  hipLaunchKernelGGL((voice_kernel<F, FMA, WAVES, S...>), dim3((n_wavefronts + WAVES - 1) / WAVES), dim3(WAVES * 64), 0, stream, args);
+  launch_voice_kernel(voice_kernel<F, FMA, WAVES, S...>, dim3((n_wavefronts + WAVES - 1) / WAVES), dim3(WAVES * 64), stream, args);
   return hipGetLastError();
 }
 #define KNH_WIDE(sig, ...)                                                                            \

@@ -11,6 +11,20 @@
 
 namespace {
 
+// The streams knh_bank_process_blocks_begin gives its launches (bank.hip), whichever bank made them: a launch on one of them --
+// a rank's or a shard's local bank sees only the stream -- keeps to it (Bank::process, overlap_now).
+struct HostPipeStreams {
+  std::mutex m;
+  std::vector<hipStream_t> streams;
+  void add(hipStream_t s) { std::lock_guard<std::mutex> l(m); streams.push_back(s); }
+  void remove(hipStream_t s) { std::lock_guard<std::mutex> l(m); streams.erase(std::remove(streams.begin(), streams.end(), s), streams.end()); }
+  bool has(hipStream_t s) { std::lock_guard<std::mutex> l(m); return std::find(streams.begin(), streams.end(), s) != streams.end(); }
+};
+inline HostPipeStreams& host_pipe_streams() {
+  static HostPipeStreams h;
+  return h;
+}
+
 template <typename F>
 struct Bank final : knh_bank {
   typedef typename knh_dev::WordOf<F>::type W;
@@ -238,10 +252,46 @@ struct Bank final : knh_bank {
   F* d_voices = nullptr;
   uint32_t* d_done = nullptr;
   uint32_t* d_flags = nullptr;
-  uint32_t flags_parity = 0;        // which of the two flag sets the next launch uses
+  uint32_t flags_turn = 0;          // which of the three flag sets the next launch uses
   uint32_t* flags_last = nullptr;   // the set of the last launch (knh_bank_debug_words)
   hipStream_t flags_stream = nullptr;  // the stream of the last launch, whose fold kernel cleared the set of this one
   bool flags_stream_set = false;
+  // A launch's tree fold beside the next launch's voice kernel (process): the voice kernels of such launches run
+  // on a stream of the bank's, their folds -- in the form that needs no LDS -- on another, and the caller's stream waits for
+  // each fold.  Two sets of partial rows alternate; the second is made when the first such launch comes.
+  // KNH_FOLD_OVERLAP=0, read when the bank is made: every launch keeps to the caller's stream (A/B runs, tests).
+  // KNH_FOLD_WAVE=1: the single-stream tree folds of up to 256 rows take the LDS-free form too (tests of that form alone).
+  bool fold_overlap = [] { const char* e = std::getenv("KNH_FOLD_OVERLAP"); return !(e && e[0] == '0'); }();
+  bool fold_wave_always = [] { const char* e = std::getenv("KNH_FOLD_WAVE"); return e && e[0] == '1'; }();
+  hipStream_t voice_stream = nullptr, fold_stream = nullptr;
+  hipEvent_t caller_at = nullptr;                      // recorded on the caller's stream at the start of such a call
+  hipEvent_t voice_done[2] = {nullptr, nullptr};       // [set of partial rows]: the voice kernel that wrote it is through
+  hipEvent_t fold_done[2] = {nullptr, nullptr};        // [set of partial rows]: the fold that read it is through
+  bool fold_busy[2] = {false, false};                  // fold_done[k] has been recorded
+  F* d_partials2 = nullptr;
+  uint32_t overlap_turn = 0;                           // the set of partial rows the next such launch writes
+  bool last_overlapped = false;                        // the launch before ran on the bank's streams
+  uint64_t overlapped_launches = 0, wave_folds = 0;  // knh_bank_debug_words 9 and 10
+  int ensure_overlap_streams(unsigned n_waves) {
+    // The two streams must not share a hardware queue with each other or with the caller's stream: a fold that sits in the
+    // queue of the voice kernels runs between them, not beside them (measured: profiles/r15_fold_overlap.json).  A process has
+    // few hardware queues and the runtime hands streams of one priority the same ones in turn, but it keeps the queues of each
+    // priority apart: the voice stream takes the highest priority, the fold stream -- whose work is hidden and never
+    // urgent -- the lowest, and the caller's stream is whatever the caller made it.
+    if (!voice_stream || !fold_stream) {
+      int least = 0, greatest = 0;
+      KNH_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+      if (!voice_stream) KNH_HIP(hipStreamCreateWithPriority(&voice_stream, hipStreamNonBlocking, greatest));
+      if (!fold_stream) KNH_HIP(hipStreamCreateWithPriority(&fold_stream, hipStreamNonBlocking, least));
+    }
+    if (!caller_at) KNH_HIP(hipEventCreateWithFlags(&caller_at, hipEventDisableTiming));
+    for (int k = 0; k < 2; ++k) {
+      if (!voice_done[k]) KNH_HIP(hipEventCreateWithFlags(&voice_done[k], hipEventDisableTiming));
+      if (!fold_done[k]) KNH_HIP(hipEventCreateWithFlags(&fold_done[k], hipEventDisableTiming));
+    }
+    if (!d_partials2) KNH_HIP(hipMalloc(&d_partials2, static_cast<size_t>(partials_blocks) * fold_planes * n_waves * block_size * sizeof(F)));
+    return KNH_OK;
+  }
   // pinned host staging
   // Event lists are read by the kernel straight from pinned host memory (each is read once, a few hundred KB per
   // launch): no copy in the stream, the kernel's first waves pull them over PCIe while the others start.  Two
@@ -320,7 +370,15 @@ struct Bank final : knh_bank {
     if (own_stream) (void)hipStreamSynchronize(own_stream);
     resolver.quiesce();
     if (flags_stream_set && flags_stream != own_stream) (void)hipStreamSynchronize(flags_stream);
-    void* dev_ptrs[] = {d_state, d_sine, d_seg_table, d_delay, d_buffer, d_wavetables, d_partials, d_out, d_voices, d_done, d_flags, d_input, d_prog, d_sin_slots, d_fold_count};
+    // the bank's voice and fold streams go with it: a bank that is closed leaves no hardware queue taken
+    for (hipStream_t st : {voice_stream, fold_stream})
+      if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+    if (caller_at) (void)hipEventDestroy(caller_at);
+    for (int k = 0; k < 2; ++k) {
+      if (voice_done[k]) (void)hipEventDestroy(voice_done[k]);
+      if (fold_done[k]) (void)hipEventDestroy(fold_done[k]);
+    }
+    void* dev_ptrs[] = {d_state, d_sine, d_seg_table, d_delay, d_buffer, d_wavetables, d_partials, d_partials2, d_out, d_voices, d_done, d_flags, d_input, d_prog, d_sin_slots, d_fold_count};
     for (void* p : dev_ptrs)
       if (p) (void)hipFree(p);
     void* host_ptrs[] = {h_ev_start2[0], h_ev_start2[1], h_events2[0], h_events2[1], h_out, h_input, h_done, h_rs_voices, h_rs_words, h_rs_seg};
@@ -1060,9 +1118,10 @@ struct Bank final : knh_bank {
     KNH_HIP(hipMemset(d_out, 0, desc.out_channels * bs * sizeof(F)));
     KNH_HIP(hipMalloc(&d_done, static_cast<size_t>(nv) * sizeof(uint32_t)));
     KNH_HIP(hipMemset(d_done, 0xFF, static_cast<size_t>(nv) * sizeof(uint32_t)));
-    // two sets of 16 words, used by alternate launches: the fold kernel of a launch clears the other set's counters
-    KNH_HIP(hipMalloc(&d_flags, 48 * sizeof(uint32_t)));  // (+ a third set: a resident launch's diagnostics)
-    KNH_HIP(hipMemset(d_flags, 0, 48 * sizeof(uint32_t)));
+    // three sets of 16 words, used by the launches in turn: the fold kernel of launch N clears the counters of launch N + 2's
+    // set (it may run beside launch N + 1's voice kernel, which accumulates into its own: process)
+    KNH_HIP(hipMalloc(&d_flags, 64 * sizeof(uint32_t)));  // (+ a fourth set: a resident launch's diagnostics)
+    KNH_HIP(hipMemset(d_flags, 0, 64 * sizeof(uint32_t)));
     for (int b = 0; b < 2; ++b) {
       KNH_HIP(hipHostMalloc(&h_ev_start2[b], (static_cast<size_t>(nv) + 2) * sizeof(uint32_t)));
       // room for two events per voice from the start: a list that has to grow later costs a resident kernel its place (it knows
@@ -1129,7 +1188,7 @@ struct Bank final : knh_bank {
       rs.launch_voice = [this](const knh_dev::Resident& r) {
         VoiceKernelArgs<F> a;
         fill_launch_args(a, 1, 0, static_cast<uint32_t>(block_size));
-        a.flags = d_flags + 32;  // (a third set: the two the ordinary launches alternate stay as their fold kernels left them)
+        a.flags = d_flags + 48;  // (a set of its own: the three the ordinary launches rotate stay as their fold kernels left them)
         a.res = r;
         return launch_voice(a, (nv + 63) / 64, own_stream);
       };
@@ -2103,6 +2162,7 @@ struct Bank final : knh_bank {
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : own_stream;
     if (resolver.take_overflow()) warn("Not enough space for scheduled changes in WrPreciseTiming, change ignored");
     const uint32_t fb = static_cast<uint32_t>(offset), fe = static_cast<uint32_t>(offset + ftp);
+    const bool restart_flushed = !rs_voices.empty();  // (the restart kernel goes to `s`: a voice kernel on the bank's stream waits for it)
     { int rr = flush_restart(s); if (rr != KNH_OK) return rr; }  // voices restarted since the last launch: their new state first
     mid_block = fe < block_size;
     // Assemble the launch's state patches block by block, in the order the reference would apply them.
@@ -2176,13 +2236,29 @@ struct Bank final : knh_bank {
     if (want_voices && !stage_out) KNH_HIP(ensure_voices());
     const bool rows_per_voice = form.facts.rows_per_voice;  // (a lane per frame: the rows are the voices' signals)
     const unsigned n_waves = rows_per_voice ? nv : (nv + 63) / 64;
+    // This launch's fold beside the next launch's voice kernel: an ordinary launch of a pipelined kernel whose tree mix stays on
+    // the device and whose caller does not wait for it; up to 256 rows (the LDS-free fold's reach).  Where it was measured not
+    // to pay it is not done (profiles/r15_fold_overlap.json, legs_first_cut_overlap_in_every_form): the whole-chain forms (a one-voice bank: -0.3 % kernel-only), and
+    // the launches of knh_bank_process_blocks_begin, which has two launches in flight on a stream of its own and a copy to the
+    // host behind each (-23 %).
+    const bool overlap_now = fold_overlap && !sync && out_device && !voices_host && !stage_out && desc.mix_mode == KNH_MIX_TREE &&
+                             form.facts.walks_ranges && !rows_per_voice && n_waves <= 256u && fe > fb && !host_pipe_streams().has(s);
     if (n_blocks > partials_blocks) {
       KNH_HIP(hipStreamSynchronize(s));
+      if (voice_stream) KNH_HIP(hipStreamSynchronize(voice_stream));  // (what reads or writes either set of rows is idle)
+      if (fold_stream) KNH_HIP(hipStreamSynchronize(fold_stream));
+      const size_t bytes = static_cast<size_t>(n_blocks) * fold_planes * n_waves * block_size * sizeof(F);
       KNH_HIP(hipFree(d_partials));
       d_partials = nullptr;
-      KNH_HIP(hipMalloc(&d_partials, static_cast<size_t>(n_blocks) * fold_planes * n_waves * block_size * sizeof(F)));
+      KNH_HIP(hipMalloc(&d_partials, bytes));
+      if (d_partials2) {
+        KNH_HIP(hipFree(d_partials2));
+        d_partials2 = nullptr;
+        KNH_HIP(hipMalloc(&d_partials2, bytes));
+      }
       partials_blocks = n_blocks;
     }
+    if (overlap_now) { int r2 = ensure_overlap_streams(n_waves); if (r2 != KNH_OK) return r2; }
     if (!out_device && n_blocks > out_blocks) {
       KNH_HIP(hipStreamSynchronize(s));
       KNH_HIP(hipFree(d_out));
@@ -2199,9 +2275,10 @@ struct Bank final : knh_bank {
     if (flags_stream_set && flags_stream != s) KNH_HIP(hipStreamSynchronize(flags_stream));  // that set was cleared in the other stream's order
     flags_stream = s;
     flags_stream_set = true;
-    uint32_t* const flags_now = d_flags + 16 * flags_parity;
-    uint32_t* const flags_next = d_flags + 16 * (flags_parity ^ 1u);
-    flags_parity ^= 1u;
+    // (the fold of this launch clears the set of the launch after the next: the next launch's kernel may be running beside it)
+    uint32_t* const flags_now = d_flags + 16 * flags_turn;
+    uint32_t* const flags_next = d_flags + 16 * ((flags_turn + 2u) % 3u);
+    flags_turn = (flags_turn + 1u) % 3u;
     flags_last = flags_now;
     VoiceKernelArgs<F> a;
     fill_launch_args(a, n_blocks, fb, fe);
@@ -2221,6 +2298,27 @@ struct Bank final : knh_bank {
       }
       in_blocks_set = 0;  // one set_input per process call
     }
+    // The stream the voice kernel goes to.  An overlapped launch's kernel runs on the bank's voice stream, behind the kernel of
+    // the launch before and beside that launch's fold.  It waits for the caller's stream only where that stream carries
+    // something the kernel reads -- the bank's input, a restart of voices, a launch that kept to the caller's stream: the
+    // caller's stream itself waits for every fold (below), so a kernel that always waited for it would start after the fold
+    // it is meant to run beside.  What else the caller enqueued before this call -- readers of the output buffer, an earlier
+    // reduce of it -- is ordered in front of the fold, which is what writes that buffer.
+    hipStream_t vs = s;
+    const uint32_t row_set = overlap_now ? overlap_turn : 0u;
+    if (overlap_now) {
+      overlap_turn ^= 1u;
+      vs = voice_stream;
+      a.partials = row_set ? d_partials2 : d_partials;
+      KNH_HIP(hipEventRecord(caller_at, s));
+      if (!last_overlapped || uses_input || restart_flushed) KNH_HIP(hipStreamWaitEvent(vs, caller_at, 0));
+      // The rows this kernel writes were read by the fold of the launch before the last, and that fold cleared this launch's
+      // flag set.  The HOST waits for that fold, not the voice stream: a wait for another queue's event is a packet between two
+      // voice kernels that costs the chip ~15 us of every launch (profiles/r15_fold_overlap.json), while the fold in question
+      // ran beside the kernel before this one -- the call returns at once unless the caller is two launches ahead of the device,
+      // and then the device still has a launch queued behind the one it is running.
+      if (fold_busy[row_set]) KNH_HIP(hipEventSynchronize(fold_done[row_set]));
+    }
     a.ev_start = have_events && !launch_n_ranges ? h_ev_start : nullptr;  // pinned host memory, device-visible
     a.events = h_events;
     if (launch_n_ranges) {  // the launch's events are range events: they travel in the kernel arguments
@@ -2233,7 +2331,7 @@ struct Bank final : knh_bank {
     }
     if (resolver.pending()) {  // calls to nodes whose queues the device resolves: the lists are made there, the host's merged in
       DevEventResolver::Lists lists{};
-      int r2 = resolver.resolve(s, n_blocks, fb, fe, have_events ? h_ev_start : nullptr, h_events, have_events ? h_ev_start[nv] : 0u, &lists);
+      int r2 = resolver.resolve(vs, n_blocks, fb, fe, have_events ? h_ev_start : nullptr, h_events, have_events ? h_ev_start[nv] : 0u, &lists);
       if (r2 != KNH_OK) return r2;
       a.ev_start = lists.ev_start;
       a.events = lists.events;
@@ -2255,16 +2353,29 @@ struct Bank final : knh_bank {
         }
       }
       tp = &timing_pool[timing_used++];
-      KNH_HIP(hipEventRecord(tp->first, s));
     }
-    KNH_HIP(rows_per_voice ? launch_frames(a, s) : launch_voice(a, n_waves, s));
-    if (tp) KNH_HIP(hipEventRecord(tp->second, s));
+    // An overlapped launch of a pre-built kernel carries its events in the dispatch itself (knh::LaunchEvents): the timing
+    // pair, or else the event its fold waits for.  Everywhere else they are recorded around the kernel.
+    const bool carried = overlap_now && !form.jit;
+    if (tp && !carried) KNH_HIP(hipEventRecord(tp->first, vs));
+    if (carried) knh::launch_events() = tp ? knh::LaunchEvents{tp->first, tp->second} : knh::LaunchEvents{nullptr, voice_done[row_set]};
+    const hipError_t launched = rows_per_voice ? launch_frames(a, vs) : launch_voice(a, n_waves, vs);
+    // (a launcher that takes the events clears them: one that left them would have launched a kernel whose fold waits for an
+    // event nobody records -- no wait at all)
+    const bool events_left = knh::launch_events().start || knh::launch_events().stop;
+    knh::launch_events() = knh::LaunchEvents{};
+    KNH_HIP(launched);
+    if (carried && events_left) {
+      (void)hipStreamSynchronize(vs);
+      return fail(KNH_ERR_INTERNAL, "the launcher of this kernel form did not take the launch's events (knh::launch_voice_kernel)");
+    }
+    if (tp && !carried) KNH_HIP(hipEventRecord(tp->second, vs));
     // (the interpreter's rows are the voices' signals; one plane: a voice with two connected outputs never runs there, init)
     if (stage_out && rows_per_voice)
       KNH_HIP(hipMemcpyAsync(stage_out, d_partials, static_cast<size_t>(nv) * block_size * sizeof(F), hipMemcpyDeviceToDevice, s));
-    { int r2 = resolver.kernel_enqueued(s); if (r2 != KNH_OK) return r2; }
+    { int r2 = resolver.kernel_enqueued(vs); if (r2 != KNH_OK) return r2; }
     if (have_events && list_in_use >= 0) {
-      KNH_HIP(hipEventRecord(list_done[list_in_use], s));
+      KNH_HIP(hipEventRecord(list_done[list_in_use], vs));
       list_busy[list_in_use] = true;
       list_in_use = -1;
     }
@@ -2282,9 +2393,29 @@ struct Bank final : knh_bank {
     // twice as many "blocks" of one channel each.
     const unsigned fold_channels = pan ? 1u : desc.out_channels;
     // (the interpreter's rows ARE the voices' signals: one buffer serves both mix orders and the per-voice debug output)
+    if (overlap_now) {
+      // The fold on the bank's fold stream: behind this launch's voice kernel, and behind what the caller's stream held when
+      // the call began (readers of `dst`).  The caller's stream waits for it: whatever the caller enqueues after this call sees
+      // the mixed blocks and the flags, as it does behind a launch that kept to that stream.
+      if (!carried) KNH_HIP(hipEventRecord(voice_done[row_set], vs));
+      KNH_HIP(hipStreamWaitEvent(fold_stream, carried && tp ? tp->second : voice_done[row_set], 0));
+      KNH_HIP(hipStreamWaitEvent(fold_stream, caller_at, 0));
+      KNH_HIP(launch_fold_wave(a.partials, n_waves, static_cast<unsigned>(block_size), fb, fe, dst, fold_channels, static_cast<unsigned>(block_size), n_blocks * fold_planes, accumulate, flags_next, fold_stream));
+      KNH_HIP(hipEventRecord(fold_done[row_set], fold_stream));
+      fold_busy[row_set] = true;
+      KNH_HIP(hipStreamWaitEvent(s, fold_done[row_set], 0));
+      last_overlapped = true;
+      overlapped_launches += 1;
+      wave_folds += 1;
+      return KNH_OK;
+    }
+    last_overlapped = false;
     if (desc.mix_mode == KNH_MIX_LEFT_FOLD)
       KNH_HIP(launch_fold(false, rows_per_voice ? d_partials : d_voices, nv, static_cast<unsigned>(block_size), fb, fe, dst, fold_channels, static_cast<unsigned>(block_size), fold_planes, accumulate, flags_next, s, hand_over ? &hd : nullptr));
-    else
+    else if (fold_wave_always && !hand_over && n_waves <= 256u && fe > fb) {
+      KNH_HIP(launch_fold_wave(d_partials, n_waves, static_cast<unsigned>(block_size), fb, fe, dst, fold_channels, static_cast<unsigned>(block_size), n_blocks * fold_planes, accumulate, flags_next, s));
+      wave_folds += 1;
+    } else
       KNH_HIP(launch_fold(true, d_partials, n_waves, static_cast<unsigned>(block_size), fb, fe, dst, fold_channels, static_cast<unsigned>(block_size), n_blocks * fold_planes, accumulate, flags_next, s, hand_over ? &hd : nullptr));
 
     if (!sync) return KNH_OK;
@@ -2357,6 +2488,12 @@ struct Bank final : knh_bank {
   static hipError_t launch_fold(bool tree, const double* rows, unsigned n, unsigned len, unsigned fb, unsigned fe, double* out, unsigned ch, unsigned os, unsigned nb, bool acc, uint32_t* zf, hipStream_t s, const knh_dev::HostDone* hd) {
     return knh::launch_fold_f64(tree, rows, n, len, fb, fe, out, ch, os, nb, acc, zf, s, hd);
   }
+  static hipError_t launch_fold_wave(const float* rows, unsigned n, unsigned len, unsigned fb, unsigned fe, float* out, unsigned ch, unsigned os, unsigned nb, bool acc, uint32_t* zf, hipStream_t s) {
+    return knh::launch_fold_wave_f32(rows, n, len, fb, fe, out, ch, os, nb, acc, zf, s);
+  }
+  static hipError_t launch_fold_wave(const double* rows, unsigned n, unsigned len, unsigned fb, unsigned fe, double* out, unsigned ch, unsigned os, unsigned nb, bool acc, uint32_t* zf, hipStream_t s) {
+    return knh::launch_fold_wave_f64(rows, n, len, fb, fe, out, ch, os, nb, acc, zf, s);
+  }
 
   int read_done_frames(uint32_t* out) override {
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
@@ -2380,6 +2517,13 @@ struct Bank final : knh_bank {
     out16[3] = !form.facts.rows_per_voice ? 0u
              : form.jit ? frame_vpw
              : knh::interp_voices_per_workgroup(nv, static_cast<unsigned>(h_prog.size()), static_cast<unsigned>(n_slots), interp_sigs, static_cast<unsigned>(block_size), sizeof(F) == 8);
+    // words 9 and 10, the host's in an ordinary build: launches so far whose fold went to the bank's fold stream, beside the
+    // launch after them, and launches whose tree fold took the form without LDS.  (A -DKNH_DAG_STAMPS build's kernels write
+    // their stamps into words 4..11: there the stamps stay.)
+#ifndef KNH_DAG_STAMPS
+    out16[9] = static_cast<uint32_t>(overlapped_launches);
+    out16[10] = static_cast<uint32_t>(wave_folds);
+#endif
     return KNH_OK;
   }
   int synchronize() override {

@@ -1506,4 +1506,39 @@ __global__ void __launch_bounds__(256) fold_tree_kernel(const F* rows, u32 n_row
   fold_signal_host(host);
 }
 
+// The same fold for up to 256 rows with no LDS at all, so that it can start on a CU whose LDS a pipeline workgroup fills
+// (voice_bank.hpp runs it beside the next launch's voice kernel).  One wavefront handles 64 frames, a lane per frame: the lane
+// walks its rows sixteen at a time in registers -- what thread (g, f) of fold_tree_kernel does for chunk g -- and then folds the
+// chunks' nodes as thread (0, f) does.  Same tree, same additions, same bits; a row's 64 frames are one 256-byte read (f32).
+template <typename F>
+__global__ void __launch_bounds__(64) fold_tree_wave_kernel(const F* rows, u32 n_rows, u32 row_len, u32 frame_begin,
+                                                             u32 frame_end, F* out, u32 channels, u32 out_stride, u32 accumulate, u32* zero_flags) {
+  if (zero_flags && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { zero_flags[0] = 0u; zero_flags[1] = 0u; }  // see fold_rows_kernel
+  const u32 n = frame_begin + blockIdx.x * 64u + threadIdx.x;
+  if (n >= frame_end) return;
+  rows += (long)blockIdx.y * n_rows * row_len;   // blockIdx.y = block of the launch
+  out += (long)blockIdx.y * channels * out_stride;
+  const u32 chunks = (n_rows + 15u) / 16u;       // 1..16 (the launcher keeps n_rows within 1..256)
+  F c[16];
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    F acc = (F)0;
+    if ((u32)g < chunks) {  // uniform
+      const u32 r0 = (u32)g * 16u;
+      const u32 cnt = n_rows - r0 < 16u ? n_rows - r0 : 16u;
+      const F* q = rows + (long)r0 * row_len + n;
+      F v[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) v[k] = (u32)k < cnt ? q[(long)k * row_len] : (F)0;
+      acc = cnt == 16u ? tree_reduce<F, 16, true>(v, 1u, 16u) : tree_reduce<F, 16, false>(v, 1u, cnt);
+    }
+    c[g] = acc;
+  }
+  const F total = chunks == 16u ? tree_reduce<F, 16, true>(c, 1u, 16u) : tree_reduce<F, 16, false>(c, 1u, chunks);
+  for (u32 ch = 0; ch < channels; ++ch) {
+    F* o = out + (long)ch * out_stride + n;
+    *o = accumulate ? *o + total : total;
+  }
+}
+
 }  // namespace knh_dev
