@@ -313,6 +313,11 @@ class VoiceBank:
         assert a.shape[1:] == (self.in_channels, self.block_size), a.shape
         self._check(self._lib.knh_bank_set_input(self._h, a.shape[0], a.ctypes.data_as(C.c_void_p)))
 
+    def set_input_device(self, device_ptr: int, n_blocks: int):
+        """The input block(s) of the next process call, read where they lie in device memory: [n_blocks, in_channels,
+        block_size] of the bank's sample type, in place by the time the launch's stream reaches it -- knh_bank_set_input_device."""
+        self._check(self._lib.knh_bank_set_input_device(self._h, n_blocks, C.c_void_p(device_ptr or None)))
+
     def process_block(self, frames_to_process: Optional[int] = None, block_start_offset: int = 0, frame_clock: int = 0,
                       out: Optional[np.ndarray] = None):
         ftp = self.block_size if frames_to_process is None else frames_to_process
@@ -364,9 +369,11 @@ class VoiceBank:
         self._check(self._lib.knh_bank_process_blocks_end(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def process_blocks_device(self, n_blocks: int, out_device_ptr: int = 0, hip_stream: int = 0, frame_clock: int = 0):
-        self._check(self._lib.knh_bank_process_blocks_device(self._h, n_blocks, frame_clock, C.c_void_p(out_device_ptr or None),
-                                                             C.c_void_p(hip_stream or None)))
+    def process_blocks_device(self, n_blocks: int, out_device_ptr: int = 0, hip_stream: int = 0, frame_clock: int = 0,
+                              add: bool = False):
+        """add: the bank's mix is added to what the buffer holds (knh_bank_process_blocks_device_add)."""
+        call = self._lib.knh_bank_process_blocks_device_add if add else self._lib.knh_bank_process_blocks_device
+        self._check(call(self._h, n_blocks, frame_clock, C.c_void_p(out_device_ptr or None), C.c_void_p(hip_stream or None)))
 
     def read_done_frames(self) -> np.ndarray:
         d = np.zeros(self.n_voices, dtype=np.uint32)
