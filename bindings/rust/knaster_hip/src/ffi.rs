@@ -136,6 +136,7 @@ pub const KNH_STAGE_FLAG_SMOOTH_PARAMS: u16 = 1 << 1;
 pub const KNH_STAGE_FLAG_READER_CH1: u16 = 1 << 2;
 pub const KNH_STAGE_FLAG_WAVETABLE: u16 = 1 << 3;
 pub const KNH_STAGE_FLAG_ENV_SOURCE: u16 = 1 << 4;
+pub const KNH_STAGE_FLAG_FEEDBACK: u16 = 1 << 5;
 
 // knh_mix_mode
 pub const KNH_MIX_TREE: u32 = 0;

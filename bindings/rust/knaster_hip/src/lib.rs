@@ -112,6 +112,16 @@ pub fn floor() -> Stage {
 pub fn sqrt() -> Stage {
     stage(KNH_STAGE_MATH1_SQRT)
 }
+/// A feedback edge inside the voice, `a.to_feedback_replace(b)` (graph_edit.rs:499-547): a source stage
+/// (`KNH_STAGE_INPUT` flagged `KNH_STAGE_FLAG_FEEDBACK`) whose signal is the node output of stage `tap` (its 0-based index
+/// in the stage list: later, earlier or right behind) one block late, zeros in the first block.  No constructor arguments,
+/// no parameters; `to_feedback` onto an input that already has an edge is a `KNH_STAGE_MATH_ADD` of the two.
+pub fn feedback(tap: u16) -> Stage {
+    let mut s = stage(KNH_STAGE_INPUT);
+    s.flags = KNH_STAGE_FLAG_FEEDBACK;
+    s.input = tap + 1;
+    s
+}
 pub trait StageExt {
     /// `.precise_timing::<N>()` on the stage's node (wrappers_core.rs:106-111)
     fn precise_timing(self, max_changes_per_block: u16) -> Self;

@@ -359,7 +359,39 @@ enum {
    * envelope has run out while its amplitude envelope sounds is running; a voice whose only finishing stages are envelope
    * sources never reports KNH_FLAG_ALL_DONE (its done frames and KNH_FLAG_ANY_DONE are still reported).
    * A voice with such a stage is fused at knh_bank_init (no pre-built kernel, never a lane per frame). */
-  KNH_STAGE_FLAG_ENV_SOURCE = 1u << 4
+  KNH_STAGE_FLAG_ENV_SOURCE = 1u << 4,
+  /* kind = KNH_STAGE_INPUT with this flag: a FEEDBACK EDGE inside the voice, `a.to_feedback(b)` / `to_feedback_replace`
+   * (graph_edit.rs:311-359, 499-547; Graph::connect2_feedback, graph.rs:1220-1254).  The stage is the reference's
+   * FeedbackSource node, and stands for the FeedbackSink beside it too: knh_chain_ugen_count counts 2.  It is a SOURCE of the
+   * voice whose signal, at frame f of a block, is the output of the stage `input` names (1 + its index; non-zero) at frame f
+   * of the PREVIOUS block -- a delay of exactly one block, block_size frames -- and zeros in the first block after
+   * knh_bank_init or knh_bank_restart_voices (the contract of graph.rs:153-155 and of graph_tests.rs:185-254, not the buffer
+   * code of graph.rs:882-909 / :2449-2453: DESIGN.md section 2).  `input` may name ANY stage of the voice that is a node with one output: a
+   * later one (the loop of a comb, of a Karplus-Strong string, of a feedback-FM operator), an earlier one (the edge is
+   * delayed all the same: `feedback_nodes2`) or the stage right behind it; "the output of stage k" is the node's output
+   * behind its wrapper stages, as everywhere.  An edge has "no impact on node ordering": the stage list stays in dependency
+   * order without it.  The ring behind an edge is block_size samples per voice, indexed by the frame's place in its block,
+   * so a block rendered by one call, by several partial calls or as one of the blocks of knh_bank_process_blocks gives the
+   * same bits; knh_bank_restart_voices clears it, knh_bank_algorithmic_bytes_per_voice_block counts block_size samples read
+   * and written per edge.
+   * No constructor arguments (no channel), no parameters: ar_param, input2 and delayed_changes_per_block must be 0, no other
+   * flag may be set, and a parameter call that names the stage is KNH_ERR_INVALID_ARGUMENT ahead of
+   * KNH_ERR_NOT_INITIALISED, as for KNH_STAGE_FLAG_READER_CH1.  It needs neither knh_bank_desc.in_channels nor
+   * knh_bank_set_input.  Unlike a bank input it is a NODE: it may drive an ar_param (the input2 of another stage), be a
+   * connected output, feed several stages.  An additive `to_feedback` onto an input that already has an edge is a
+   * KNH_STAGE_MATH_ADD of the two, which is what the reference inserts (graph.rs:800-814).
+   * Refused at knh_bank_create with KNH_ERR_INVALID_ARGUMENT: the flag on another kind or with another flag; input == 0 or
+   * beyond the last stage; input naming a KNH_STAGE_INPUT stage, flagged or not (put the input through `* 1.0`), a
+   * KNH_STAGE_FLAG_READER_CH1 stage, or a KNH_STAGE_PAN2 / KNH_STAGE_GALACTIC stage (two outputs); non-zero ar_param, input2
+   * or delayed_changes_per_block.  With KNH_ERR_UNSUPPORTED_CHAIN: a chain that ends in Galactic; delay stages plus feedback
+   * edges above KNH_MAX_DELAY_STAGES in one voice (they share the restart kernel's ring table); more than one envelope stage
+   * (multiplying or KNH_STAGE_FLAG_ENV_SOURCE) in a voice with a feedback edge -- the place of the FeedbackSink among the
+   * tasks, and with it which envelope's mark names the done frame, is not pinned here.
+   * A voice with such a stage is a graph, fused at knh_bank_init: never a lane per frame, never a pipeline.  It works the same
+   * in every way of creating a bank -- knh_bank_create, _create_sharded, _create_multi_device, _create_rank[_custom]: each
+   * voice range is an ordinary bank with rings of its own, and an edge never leaves its voice.  The resident form takes
+   * such a bank as it takes any graph voice; per-block calls and launched blocks give the same bits. */
+  KNH_STAGE_FLAG_FEEDBACK = 1u << 5
 };
 
 typedef struct knh_stage_desc {

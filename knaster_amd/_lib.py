@@ -35,6 +35,7 @@ STAGE_FLAG_SMOOTH_PARAMS = 2
 STAGE_FLAG_READER_CH1 = 4  # a STAGE_BUFFER_READER stage with it: output channel 1 of the reader stage `input` names
 STAGE_FLAG_WAVETABLE = 8  # a STAGE_SIN_WT stage with it: OscWt on a Wavetable of the stage's pool (add_wavetable)
 STAGE_FLAG_ENV_SOURCE = 16  # a STAGE_MUL_ENV_ASR / _AR / MUL_ENVELOPE stage with it: the envelope alone, a source of the voice (one node, no multiply)
+STAGE_FLAG_FEEDBACK = 32  # a STAGE_INPUT stage with it: a feedback edge, the output of the stage `input` names one block late (FeedbackSink + FeedbackSource)
 WAVETABLE_SIZE, WAVETABLE_TABLES = 16384, 17  # samples per partial table, partial tables per Wavetable
 # knh_svf_type
 SVF_LOW, SVF_HIGH, SVF_BAND, SVF_NOTCH, SVF_PEAK, SVF_ALL, SVF_BELL, SVF_LOW_SHELF, SVF_HIGH_SHELF = range(9)

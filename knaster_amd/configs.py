@@ -241,3 +241,36 @@ def fm_cascade(depth: int, n_voices: int = 1, block_size: int = 128, sample_type
     scale = 1.0 + detune * np.arange(n_voices)
     w.ctor = {s: (a * scale if st[s].kind == L.STAGE_SIN_WT else np.full(n_voices, a)).reshape(n_voices, 1) for s, a in ctor.items()}
     return w
+
+
+FEEDBACK_COMB_DELAYS = (3, 17, 40, 63, 64, 65, 70, 100)  # samples, dealt to the voices in turn: on both sides of a 16-, 32- and 64-sample tile
+
+
+def feedback_comb(n_voices: int, block: int, sample_type: int = L.F32, feedback: bool = True, gain: float = 0.6) -> Workload:
+    """A feedback comb per voice, the loop closed by a feedback edge (STAGE_FLAG_FEEDBACK: one block late, knaster_hip.h):
+         x = SinWt(f) * EnvAsr;  d = SampleDelay(x + gain * fb);  fb = d, one block late;  out = d * (1 / N)
+    so the loop's delay is block + d samples, d per voice from FEEDBACK_COMB_DELAYS.  Stage 2 is the edge's source, its tap the
+    delay (stage 5); stage 3 is the loop gain (below 1).  feedback=False: the same voice with the edge removed,
+    SinWt * EnvAsr -> SampleDelay -> * (1 / N).  delay_times is set on the delay stage before block 0, restart on the envelope."""
+    nv = n_voices
+    p = voice_parameters(nv)
+    col = lambda a: np.asarray(a, dtype=np.float64).reshape(nv, -1)
+    env = np.stack([p["attack"], p["release"]], axis=1)
+    d = np.array([FEEDBACK_COMB_DELAYS[v % len(FEEDBACK_COMB_DELAYS)] for v in range(nv)], dtype=np.float64)
+    ring = col(np.full(nv, 160.5 / SAMPLE_RATE))  # a ring of 160 samples
+    if feedback:
+        st = [Stage(L.STAGE_SIN_WT), Stage(L.STAGE_MUL_ENV_ASR), Stage(L.STAGE_INPUT, flags=L.STAGE_FLAG_FEEDBACK, input=6),
+              Stage(L.STAGE_MUL_CONST, delayed_changes_per_block=2), Stage(L.STAGE_MATH_ADD, input=2, input2=4), Stage(L.STAGE_SAMPLE_DELAY),
+              Stage(L.STAGE_MUL_CONST)]
+        w = Workload("feedback_comb", st, nv, block, sample_type, 2,
+                     description="SinWt * EnvAsr + 0.6 * fb -> SampleDelay(d) -> fb (one block late); * 1/N")
+        w.ctor = {0: col(p["freq"]), 1: env, 3: col(np.full(nv, gain)), 5: ring, 6: col(np.full(nv, 1.0 / nv))}
+        w.restart = (1, 3)
+        w.param_sets = ((5, 0, (d + 0.25) / SAMPLE_RATE),)
+    else:
+        st = [Stage(L.STAGE_SIN_WT), Stage(L.STAGE_MUL_ENV_ASR), Stage(L.STAGE_SAMPLE_DELAY), Stage(L.STAGE_MUL_CONST)]
+        w = Workload("comb_no_edge", st, nv, block, sample_type, 2, description="SinWt * EnvAsr -> SampleDelay(d); * 1/N")
+        w.ctor = {0: col(p["freq"]), 1: env, 2: ring, 3: col(np.full(nv, 1.0 / nv))}
+        w.restart = (1, 3)
+        w.param_sets = ((2, 0, (d + 0.25) / SAMPLE_RATE),)
+    return w

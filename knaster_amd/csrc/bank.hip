@@ -62,6 +62,8 @@ knh_bank* make_bank(const knh_bank_desc& d, const std::string& sig) {
     if (s.kind == KNH_STAGE_BUFFER_READER && s.ar_param != 0) s.n_slots = 14;
     // the second output of a BufferReader (KNH_STAGE_FLAG_READER_CH1) is no node: no slots, no parameters, no constructor arguments
     if (s.ch1()) s.n_slots = s.n_params = s.n_ctor = 0;
+    // a feedback edge (KNH_STAGE_FLAG_FEEDBACK) is no bank input: no channel, no state word (knh_dev::FbRingT finds its ring by edge and voice)
+    if (s.feedback()) s.n_slots = s.n_params = s.n_ctor = 0;
     // OscWt (KNH_STAGE_FLAG_WAVETABLE) keeps the table it reads and its pool entry beside SinWt's three words (knh_dev::OscWtT)
     if (s.wavetable()) s.n_slots = 5;
     b->stages.push_back(s);
@@ -445,7 +447,7 @@ int32_t knh_bank_connect_outputs(knh_bank* bank, uint32_t n_channels, const uint
       return bank->fail(KNH_ERR_INVALID_ARGUMENT, "a chain that ends in Pan2 or Galactic makes its two outputs itself");
     uint32_t out[2];
     for (int c = 0; c < 2; ++c) {
-      if (bank->stages[stages[c]].kind == KNH_STAGE_INPUT)
+      if (bank->stages[stages[c]].kind == KNH_STAGE_INPUT && !bank->stages[stages[c]].feedback())  // (a feedback edge's source is a node)
         return bank->fail(KNH_ERR_INVALID_ARGUMENT, "an output connection starts at a node, not at a bank input (put the input through `* 1.0`)");
       out[c] = stages[c];  // the node's output: behind the wrapper stages that follow it (build_signature, node_output)
       while (out[c] + 1 < n && is_wrapper_kind(bank->stages[out[c] + 1].kind)) ++out[c];
@@ -784,6 +786,10 @@ int32_t knh_bank_algorithmic_bytes_per_voice_block(const knh_bank* bank, uint32_
         // (l | r) >> Galactic: the second staging plane, written by the chain before the reverb and read by it (0 before knh_bank_init)
         case KNH_STAGE_GALACTIC:
           if (s.input2 != 0) { r += word * static_cast<uint32_t>(bank->block_size); w += word * static_cast<uint32_t>(bank->block_size); }
+          break;
+        // a feedback edge: last block's samples read from its ring, this block's written to it (0 before knh_bank_init)
+        case KNH_STAGE_INPUT:
+          if (s.feedback()) { r += word * static_cast<uint32_t>(bank->block_size); w += word * static_cast<uint32_t>(bank->block_size); }
           break;
         default: break;
       }

@@ -32,6 +32,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
   for (uint32_t i = 0; i < n; ++i) {
     if (st[i].kind >= KNH_STAGE_KIND_COUNT) { *why = "unknown stage kind"; return KNH_ERR_INVALID_ARGUMENT; }
     const bool ch1 = is_reader_ch1(st[i]);
+    const bool fb = is_feedback(st[i].kind, st[i].flags);  // a feedback edge: the FeedbackSource, 'x'
     if (is_wrapper_kind(st[i].kind) && i > 0) {  // the node the wrapper would wrap: a reader with two outputs?
       uint32_t k = i - 1;
       while (k > 0 && is_wrapper_kind(st[k].kind)) --k;
@@ -49,7 +50,22 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     const bool ar = st[i].kind == KNH_STAGE_SIN_WT && (st[i].flags & KNH_STAGE_FLAG_AR_FREQ);
     const bool wt = st[i].kind == KNH_STAGE_SIN_WT && (st[i].flags & KNH_STAGE_FLAG_WAVETABLE);  // OscWt: 'M' for 'W', 'k' for 'R'
     const bool math2 = is_math2_kind(st[i].kind);
-    if (st[i].flags & ~(KNH_STAGE_FLAG_AR_FREQ | KNH_STAGE_FLAG_SMOOTH_PARAMS | KNH_STAGE_FLAG_READER_CH1 | KNH_STAGE_FLAG_WAVETABLE | KNH_STAGE_FLAG_ENV_SOURCE)) { *why = "unknown stage flag"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (st[i].flags & ~(KNH_STAGE_FLAG_AR_FREQ | KNH_STAGE_FLAG_SMOOTH_PARAMS | KNH_STAGE_FLAG_READER_CH1 | KNH_STAGE_FLAG_WAVETABLE | KNH_STAGE_FLAG_ENV_SOURCE | KNH_STAGE_FLAG_FEEDBACK)) { *why = "unknown stage flag"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (st[i].flags & KNH_STAGE_FLAG_FEEDBACK) {  // Graph::connect2_feedback: the flagged stage is the edge's FeedbackSource, `input` the node it taps
+      if (st[i].kind != KNH_STAGE_INPUT) { *why = "FEEDBACK is only defined for KNH_STAGE_INPUT"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (st[i].flags != KNH_STAGE_FLAG_FEEDBACK) { *why = "a FEEDBACK stage takes no other stage flag"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (st[i].ar_param != 0 || st[i].input2 != 0 || st[i].delayed_changes_per_block != 0) {
+        *why = "a FEEDBACK stage is a feedback edge, not a parameterised node: ar_param, input2 and delayed_changes_per_block must be 0";
+        return KNH_ERR_INVALID_ARGUMENT;
+      }
+      if (st[i].input == 0) { *why = "a FEEDBACK stage names the stage whose output it delays by one block (input = 1 + its index)"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (st[i].input > n) { *why = "a FEEDBACK stage names a stage of this voice: input is beyond the last stage"; return KNH_ERR_INVALID_ARGUMENT; }
+      const knh_stage_desc& tap = st[st[i].input - 1];
+      if (tap.kind >= KNH_STAGE_KIND_COUNT) { *why = "unknown stage kind"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (tap.kind == KNH_STAGE_INPUT) { *why = "a feedback edge starts at a node, not at a bank input or another feedback edge (put the input through `* 1.0`)"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (is_reader_ch1(tap)) { *why = "a feedback edge cannot start at a READER_CH1 stage (put that channel through `* 1.0`)"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (tap.kind == KNH_STAGE_PAN2 || tap.kind == KNH_STAGE_GALACTIC) { *why = "a feedback edge starts at a node with one output: not at Pan2 or Galactic"; return KNH_ERR_INVALID_ARGUMENT; }
+    }
     if ((st[i].flags & KNH_STAGE_FLAG_ENV_SOURCE) && !is_env_kind(st[i].kind)) { *why = "ENV_SOURCE is only defined for MUL_ENV_ASR, MUL_ENV_AR and MUL_ENVELOPE"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((st[i].flags & KNH_STAGE_FLAG_ENV_SOURCE) && (st[i].flags & (KNH_STAGE_FLAG_AR_FREQ | KNH_STAGE_FLAG_READER_CH1 | KNH_STAGE_FLAG_WAVETABLE))) { *why = "ENV_SOURCE cannot be combined with AR_FREQ, READER_CH1 or WAVETABLE"; return KNH_ERR_INVALID_ARGUMENT; }
     if (env_src && st[i].input != 0) { *why = "an ENV_SOURCE stage is a source: it reads no signal (input = 0)"; return KNH_ERR_INVALID_ARGUMENT; }
@@ -59,7 +75,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     if ((st[i].flags & KNH_STAGE_FLAG_SMOOTH_PARAMS) && is_wrapper_kind(st[i].kind)) { *why = "SMOOTH_PARAMS applies to a node, not to a wrapper stage"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((st[i].flags & KNH_STAGE_FLAG_AR_FREQ) && st[i].kind != KNH_STAGE_SIN_WT) { *why = "AR_FREQ is only defined for SIN_WT"; return KNH_ERR_INVALID_ARGUMENT; }
     // operands: `input` / `input2` name the stage whose output is read (1 + its index), 0 = the stage before this one
-    if (st[i].input > i || st[i].input2 > i) { *why = "a stage reads the output of an earlier stage"; return KNH_ERR_INVALID_ARGUMENT; }
+    if ((st[i].input > i && !fb) || st[i].input2 > i) { *why = "a stage reads the output of an earlier stage"; return KNH_ERR_INVALID_ARGUMENT; }
     if (math2 && (st[i].input == 0 || st[i].input2 == 0)) { *why = "a KNH_STAGE_MATH_* stage names both of its operands (input, input2)"; return KNH_ERR_INVALID_ARGUMENT; }
     if (!math2 && st[i].input2 != 0 && st[i].ar_param == 0 && st[i].kind != KNH_STAGE_GALACTIC) { *why = "input2 is the second operand of the KNH_STAGE_MATH_* stages, the driver of an audio-rate parameter (ar_param) and the right input of Galactic"; return KNH_ERR_INVALID_ARGUMENT; }
     if (math2 && st[i].ar_param != 0) { *why = "a KNH_STAGE_MATH_* stage has no parameters"; return KNH_ERR_INVALID_ARGUMENT; }
@@ -69,12 +85,12 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       if (st[i].flags & KNH_STAGE_FLAG_SMOOTH_PARAMS) { *why = "a KNH_STAGE_MATH1_* stage has no parameters: SMOOTH_PARAMS does not apply"; return KNH_ERR_INVALID_ARGUMENT; }
     }
     if (is_wrapper_kind(st[i].kind) && st[i].input != 0) { *why = "a wrapper stage wraps the stage before it (input = 0)"; return KNH_ERR_INVALID_ARGUMENT; }
-    if (source && !ar && st[i].input != 0) { *why = "a source stage reads no signal"; return KNH_ERR_INVALID_ARGUMENT; }
+    if (source && !ar && !fb && st[i].input != 0) { *why = "a source stage reads no signal"; return KNH_ERR_INVALID_ARGUMENT; }
     if ((!source || ar) && !have_x) { *why = "stage needs a preceding signal"; return KNH_ERR_INVALID_ARGUMENT; }
-    if ((st[i].kind == KNH_STAGE_SAMPLE_DELAY || st[i].kind == KNH_STAGE_ALLPASS_DELAY || st[i].kind == KNH_STAGE_ALLPASS_FB_DELAY) &&
-        std::count_if(sig->begin(), sig->end(), [](char c) { return c == 'D' || c == 'Y' || c == 'Z'; }) >= KNH_MAX_DELAY_STAGES) {
-      // (every delay stage has a ring of its own per voice; the restart kernel's arguments name each stage's rings: RestartArgs)
-      *why = "a voice holds at most KNH_MAX_DELAY_STAGES delay stages";
+    if ((st[i].kind == KNH_STAGE_SAMPLE_DELAY || st[i].kind == KNH_STAGE_ALLPASS_DELAY || st[i].kind == KNH_STAGE_ALLPASS_FB_DELAY || fb) &&
+        std::count_if(sig->begin(), sig->end(), [](char c) { return c == 'D' || c == 'Y' || c == 'Z' || c == 'x'; }) >= KNH_MAX_DELAY_STAGES) {
+      // (every delay stage and every feedback edge has a ring of its own per voice; the restart kernel's arguments name each one's rings: RestartArgs)
+      *why = "a voice holds at most KNH_MAX_DELAY_STAGES delay stages and feedback edges together";
       return KNH_ERR_UNSUPPORTED_CHAIN;
     }
     if (st[i].kind == KNH_STAGE_MUL_ENVELOPE && sig->find_first_of("Vl") != std::string::npos) { *why = "at most one Envelope stage per chain"; return KNH_ERR_INVALID_ARGUMENT; }
@@ -93,6 +109,7 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
         return KNH_ERR_INVALID_ARGUMENT;
       }
       if (sig->find_first_of("DYZ") != std::string::npos) { *why = "a chain that ends in Galactic holds no other delay stage"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (sig->find('x') != std::string::npos) { *why = "a chain that ends in Galactic holds no feedback edge"; return KNH_ERR_UNSUPPORTED_CHAIN; }
     }
     if (st[i].ar_param != 0) {  // an audio-rate parameter: the node's float parameter ar_param - 1 is driven by the signal input2 names
       const uint32_t p = st[i].ar_param - 1u;
@@ -100,10 +117,10 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       if (!ar_param_supported(st[i].kind, p)) { *why = "this parameter cannot be driven at audio rate here (knh_stage_desc.ar_param lists what can)"; return KNH_ERR_UNSUPPORTED_CHAIN; }
       if (st[i].input2 == 0) { *why = "an audio-rate parameter names the signal that drives it (input2)"; return KNH_ERR_INVALID_ARGUMENT; }
       if (st[i].flags & (KNH_STAGE_FLAG_AR_FREQ | KNH_STAGE_FLAG_SMOOTH_PARAMS)) { *why = "ar_param cannot be combined with AR_FREQ or SMOOTH_PARAMS on one stage"; return KNH_ERR_INVALID_ARGUMENT; }
-      if (kKinds[st[i].kind].sig == 'I' || st[st[i].input2 - 1].kind == KNH_STAGE_INPUT) { *why = "an audio-rate parameter edge starts at a node, not at a bank input (put the input through `* 1.0`)"; return KNH_ERR_INVALID_ARGUMENT; }
+      if (kKinds[st[i].kind].sig == 'I' || (st[st[i].input2 - 1].kind == KNH_STAGE_INPUT && !is_feedback(KNH_STAGE_INPUT, st[st[i].input2 - 1].flags))) { *why = "an audio-rate parameter edge starts at a node, not at a bank input (put the input through `* 1.0`)"; return KNH_ERR_INVALID_ARGUMENT; }
     }
     // ('T': a reader with two outputs; '2': its second output, which is no device stage and leaves the signature below)
-    sig->push_back(env_src ? env_source_sig(st[i].kind) : wt ? (ar ? 'k' : 'M') : ar ? 'R' : ch1 ? '2' : (st[i].kind == KNH_STAGE_BUFFER_READER && companion[i] >= 0) ? 'T' : kKinds[st[i].kind].sig);
+    sig->push_back(fb ? 'x' : env_src ? env_source_sig(st[i].kind) : wt ? (ar ? 'k' : 'M') : ar ? 'R' : ch1 ? '2' : (st[i].kind == KNH_STAGE_BUFFER_READER && companion[i] >= 0) ? 'T' : kKinds[st[i].kind].sig);
     have_x = true;
   }
   // A voice that is a graph (a stage that names its operands, a MathUGen of two signals, a second source): every stage is
@@ -114,7 +131,14 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
   const bool connected = outs && n > 0 && !(outs[0] == n - 1 && outs[1] == n - 1);
   bool dag = connected;
   {
-    uint32_t sources = 0;
+    uint32_t sources = 0, edges = 0, envelopes = 0;
+    for (uint32_t i = 0; i < n; ++i) { edges += is_feedback(st[i].kind, st[i].flags); envelopes += is_env_kind(st[i].kind); }
+    if (edges > 0 && envelopes > 1) {
+      // (where the FeedbackSink stands among the tasks -- and with it which envelope's mark names the done frame -- is not pinned here)
+      *why = "a voice with a feedback edge holds at most one envelope stage";
+      return KNH_ERR_UNSUPPORTED_CHAIN;
+    }
+    dag = dag || edges > 0;  // always a graph voice
     for (uint32_t i = 0; i < n; ++i) {
       const bool ar = st[i].kind == KNH_STAGE_SIN_WT && (st[i].flags & KNH_STAGE_FLAG_AR_FREQ);
       sources += (std::strchr("WNPUKOGBFI", kKinds[st[i].kind].sig) != nullptr || is_env_source(st[i].kind, st[i].flags)) && !ar && !is_reader_ch1(st[i]);
@@ -138,8 +162,17 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       while (k + 1 < static_cast<int>(n) && is_wrapper_kind(st[k + 1].kind)) ++k;
       return k;
     };
+    // Feedback edges (KNH_STAGE_FLAG_FEEDBACK): edge e's source is stage fb_src[e], its tap the node output fb_tap[e].  The device
+    // list has two ops per edge: 'x' fills the source's signal slot from the voice's ring, 'y' -- no host stage stands for it --
+    // stores the tapped signal's slot to the ring, directly behind the tapped node's output, and passes the signal on.  Both
+    // touch the same ring positions tile by tile, so their order is the edge's one-block delay: a tap LATER than the source has
+    // its 'x' at the source's place (the 'y' comes later in the same tile); a tap EARLIER than the source has its 'x'
+    // immediately in front of its 'y', the slot held until the source's last reader (graph_tests.rs:221-254, feedback_nodes2).
+    std::vector<uint32_t> fb_src, fb_tap;
+    for (uint32_t i = 0; i < n; ++i)
+      if ((*sig)[i] == 'x') { fb_src.push_back(i); fb_tap.push_back(static_cast<uint32_t>(node_output(static_cast<int>(st[i].input) - 1))); }
     for (uint32_t i = 0; i < n; ++i) {
-      const bool reads = i > 0 && !(std::strchr("WMNPUKOGBFIT2bjl", (*sig)[i]) != nullptr);  // 'R' reads, the plain sources do not (nor does a reader's second output: it IS the reader)
+      const bool reads = i > 0 && !(std::strchr("WMNPUKOGBFIT2bjlx", (*sig)[i]) != nullptr);  // 'R' reads, the plain sources do not (nor does a reader's second output: it IS the reader)
       if (is_math2_kind(st[i].kind)) { a[i] = node_output(st[i].input - 1); b[i] = node_output(st[i].input2 - 1); }
       else if (reads) a[i] = st[i].input ? node_output(st[i].input - 1) : static_cast<int>(i) - 1;
       if (st[i].ar_param != 0) b[i] = node_output(st[i].input2 - 1);  // the signal that drives the parameter
@@ -154,8 +187,11 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
     std::vector<int> slot(n, -1);
     std::vector<char> busy;
     std::string out;
+    auto num = [](int v) { return v < 0 ? std::string("_") : std::to_string(v); };  // "_": none
+    int last_o = -1;  // the slot the last device op writes: the voice's signal unless the list's end says otherwise
     for (uint32_t i = 0; i < n; ++i) {
       if ((*sig)[i] == '2') continue;  // a reader's second output: its slot was handed out with the reader's, it is no device stage
+      if ((*sig)[i] == 'x' && slot[i] >= 0) continue;  // a feedback source behind its tap: its 'x' stands in front of the edge's 'y'
       const int sa = a[i] >= 0 ? slot[a[i]] : -1, sb = b[i] >= 0 ? slot[b[i]] : -1;
       // operands whose last reader this is give their slot back first: the stage may then write where it read
       if (a[i] >= 0 && last_use[a[i]] == static_cast<int>(i)) busy[sa] = 0;
@@ -177,11 +213,31 @@ int build_signature(const knh_stage_desc* st, uint32_t n, std::string* sig, std:
       }
       out.push_back((*sig)[i]);
       if (st[i].ar_param != 0) out += "%" + std::to_string(st[i].ar_param - 1);  // "%P": parameter P at audio rate (knh_dev::ArP)
-      auto num = [](int v) { return v < 0 ? std::string("_") : std::to_string(v); };  // "_": none
+      if ((*sig)[i] == 'x') out += "$" + std::to_string(std::find(fb_src.begin(), fb_src.end(), i) - fb_src.begin());  // "$E": edge E's ring (knh_dev::FbRead<E>)
       out += "@" + num(sa) + "," + num(sb) + "," + num(o);
       if (o2 >= 0) out += "," + num(o2);  // "@a,b,o,o2": the slot of the node's second output (knh_dev::At2)
+      last_o = o;
+      for (size_t e = 0; e < fb_src.size(); ++e) {  // the edges that tap this node's output
+        if (fb_tap[e] != i) continue;
+        const int s_tap = slot[i];
+        if (fb_src[e] > i) {  // the source comes later: last block's samples leave the ring before this block's go in
+          const char was = busy[s_tap];
+          busy[s_tap] = 1;  // (a tapped signal nobody else reads still holds its slot until the 'y' behind it)
+          int r = -1;
+          for (size_t k = 0; r < 0 && k < busy.size(); ++k)
+            if (!busy[k]) r = static_cast<int>(k);
+          if (r < 0) { r = static_cast<int>(busy.size()); busy.push_back(0); }
+          busy[s_tap] = was;
+          if (last_use[fb_src[e]] >= 0) busy[r] = 1;
+          slot[fb_src[e]] = r;
+          out += "x$" + std::to_string(e) + "@_,_," + num(r);
+        }
+        out += "y$" + std::to_string(e) + "@" + num(s_tap) + ",_," + num(s_tap);  // (in place: the tapped signal goes on as it is)
+        last_o = s_tap;
+      }
     }
     *sig = out + "#" + std::to_string(busy.size());  // "#R": the number of slots
+    if (!connected && !(st[n - 1].flags & KNH_STAGE_FLAG_READER_CH1) && last_o != slot[n - 1]) *sig += "=" + std::to_string(slot[n - 1]);  // (the voice's signal is not the last device op's: a feedback source whose 'x' stands earlier)
     if (!connected && (st[n - 1].flags & KNH_STAGE_FLAG_READER_CH1)) *sig += "=" + std::to_string(slot[n - 1]);  // "#R=k": the voice's signal is a reader's second output, in slot k (knh_dev::Out1)
     if (connected) *sig += ":" + std::to_string(slot[outs[0]]) + "," + std::to_string(slot[outs[1]]);  // "#R:l,r": the slots of the two connected outputs
   }

@@ -320,7 +320,7 @@ struct ShardedBank final : knh_bank {
   }
 
   int param_apply(uint32_t voice, uint32_t stage, uint32_t param, uint32_t kind, double f, int64_t i) override {
-    if (stage < stages.size() && stages[stage].ch1()) return fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams);  // (about the chain: named ahead of the state, as a range does)
+    if (stage < stages.size() && no_params_message(stages[stage])) return fail(KNH_ERR_INVALID_ARGUMENT, no_params_message(stages[stage]));  // (about the chain: named ahead of the state, as a range does)
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (voice >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
     flush_deferred();
@@ -328,7 +328,7 @@ struct ShardedBank final : knh_bank {
     return adopt(k, shard[k]->param_apply(voice - base[k], stage, param, kind, f, i));
   }
   int set_delay(uint32_t voice, uint32_t stage, uint32_t param, uint16_t delay) override {
-    if (stage < stages.size() && stages[stage].ch1()) return fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams);  // (about the chain: named ahead of the state, as a range does)
+    if (stage < stages.size() && no_params_message(stages[stage])) return fail(KNH_ERR_INVALID_ARGUMENT, no_params_message(stages[stage]));  // (about the chain: named ahead of the state, as a range does)
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (voice >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
     flush_deferred();
@@ -337,7 +337,7 @@ struct ShardedBank final : knh_bank {
   }
   int call_at(uint32_t block_offset, bool is_delay, uint32_t voice, uint32_t stage, uint32_t param, uint32_t kind, double f, int64_t i,
               uint16_t delay) override {
-    if (stage < stages.size() && stages[stage].ch1()) return fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams);  // (about the chain: named ahead of the state, as a range does)
+    if (stage < stages.size() && no_params_message(stages[stage])) return fail(KNH_ERR_INVALID_ARGUMENT, no_params_message(stages[stage]));  // (about the chain: named ahead of the state, as a range does)
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (voice >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
     flush_deferred();

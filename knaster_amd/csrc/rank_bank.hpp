@@ -264,7 +264,7 @@ struct RankBank final : knh_bank {
   }
   int check_global(uint32_t voice, uint32_t stage, uint32_t param) {
     if (stage < stages.size() && is_math1_kind(stages[stage].kind)) return fail(KNH_ERR_INVALID_ARGUMENT, "a KNH_STAGE_MATH1_* stage has no parameters");
-    if (stage < stages.size() && stages[stage].ch1()) return fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams);
+    if (stage < stages.size() && no_params_message(stages[stage])) return fail(KNH_ERR_INVALID_ARGUMENT, no_params_message(stages[stage]));
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (voice >= total) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
     if (stage >= stages.size()) return fail(KNH_ERR_OUT_OF_RANGE, "stage out of range");
@@ -300,7 +300,7 @@ struct RankBank final : knh_bank {
                  const uint32_t* kinds, const double* fvalues, const int64_t* ivalues, const uint16_t* delays) override {
     if (!initialised) {  // (a call that names a reader's second output is a mistake about the chain: named ahead of the state, as check_global does)
       for (size_t k = 0; k < count; ++k)
-        if (stgs[k] < stages.size() && stages[stgs[k]].ch1()) return fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams);
+        if (stgs[k] < stages.size() && no_params_message(stages[stgs[k]])) return fail(KNH_ERR_INVALID_ARGUMENT, no_params_message(stages[stgs[k]]));
       return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     }
     r_voices.clear(); r_stages.clear(); r_params.clear(); r_kinds.clear(); r_f.clear(); r_i.clear(); r_d.clear();
@@ -310,7 +310,7 @@ struct RankBank final : knh_bank {
       if (v >= total) { rc = fail(KNH_ERR_OUT_OF_RANGE, "voice out of range"); continue; }
       if (stgs[k] >= stages.size()) { rc = fail(KNH_ERR_OUT_OF_RANGE, "stage out of range"); continue; }
       if (is_math1_kind(stages[stgs[k]].kind)) { rc = fail(KNH_ERR_INVALID_ARGUMENT, "a KNH_STAGE_MATH1_* stage has no parameters"); continue; }
-      if (stages[stgs[k]].ch1()) { rc = fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams); continue; }
+      if (no_params_message(stages[stgs[k]])) { rc = fail(KNH_ERR_INVALID_ARGUMENT, no_params_message(stages[stgs[k]])); continue; }
       if (params[k] >= static_cast<uint32_t>(stages[stgs[k]].n_params)) { rc = fail(KNH_ERR_OUT_OF_RANGE, "parameter index out of range"); continue; }
       if (block_offset >= 65536) { rc = fail(KNH_ERR_OUT_OF_RANGE, "block_offset too large"); continue; }
       if (!kind_ok(stgs[k], params[k], kinds[k])) { rc = fail(KNH_ERR_WRONG_VALUE_KIND, "parameter value kind does not match the parameter type"); continue; }

@@ -66,7 +66,11 @@ inline bool is_env_kind(uint16_t kind) { return kind == KNH_STAGE_MUL_ENV_ASR ||
 // signature characters are 'b' (EnvAsr), 'j' (EnvAr), 'l' (Envelope) for 'A', 'E', 'V'.
 inline bool is_env_source(uint16_t kind, uint16_t flags) { return is_env_kind(kind) && (flags & KNH_STAGE_FLAG_ENV_SOURCE); }
 inline char env_source_sig(uint16_t kind) { return kind == KNH_STAGE_MUL_ENV_ASR ? 'b' : kind == KNH_STAGE_MUL_ENV_AR ? 'j' : 'l'; }
-inline int stage_nodes(uint16_t kind, uint16_t flags) { return is_env_source(kind, flags) ? 1 : kKinds[kind].n_nodes; }
+// A feedback edge inside the voice (KNH_STAGE_FLAG_FEEDBACK on KNH_STAGE_INPUT): the reference's FeedbackSource node, standing
+// for the FeedbackSink beside it too (two nodes).  A source; its signature character is 'x' (the ring's read), and the
+// device list has a 'y' (the ring's write) behind the tapped node that no host stage stands for (build_signature).
+inline bool is_feedback(uint16_t kind, uint16_t flags) { return kind == KNH_STAGE_INPUT && (flags & KNH_STAGE_FLAG_FEEDBACK); }
+inline int stage_nodes(uint16_t kind, uint16_t flags) { return is_env_source(kind, flags) ? 1 : is_feedback(kind, flags) ? 2 : kKinds[kind].n_nodes; }
 inline bool is_math2_kind(uint16_t kind) { return kind >= KNH_STAGE_MATH_ADD && kind <= KNH_STAGE_MATH_POW; }
 inline bool is_math1_kind(uint16_t kind) { return kind >= KNH_STAGE_MATH1_CEIL && kind <= KNH_STAGE_MATH1_EXP; }
 // A voice that is a graph rather than a chain: explicit operands, a MathUGen of two signals, or a second source.
@@ -246,9 +250,15 @@ struct StageInfo {
   bool wavetable() const { return kind == KNH_STAGE_SIN_WT && (flags & KNH_STAGE_FLAG_WAVETABLE); }
   // the envelope alone, a source of the voice (KNH_STAGE_FLAG_ENV_SOURCE): same slots, parameters and constructor arguments as `x * env`
   bool env_source() const { return is_env_source(kind, flags); }
+  // a feedback edge (KNH_STAGE_FLAG_FEEDBACK): no slots, no parameters, no constructor arguments; `input` names the tapped stage
+  bool feedback() const { return is_feedback(kind, flags); }
 };
+const char kFeedbackNoParams[] = "a KNH_STAGE_FLAG_FEEDBACK stage is a feedback edge (FeedbackSink + FeedbackSource): it has no parameters";
 const char kCh1NoParams[] = "a KNH_STAGE_FLAG_READER_CH1 stage is the second output of a BufferReader, not a node: it has no parameters (address the reader stage)";
 inline bool is_reader_ch1(const knh_stage_desc& d) { return d.kind == KNH_STAGE_BUFFER_READER && (d.flags & KNH_STAGE_FLAG_READER_CH1); }
+// The message for a parameter call that names a stage which is no parameterised node (a reader's second output, a feedback
+// edge), or null: such a call is a mistake about the chain, named ahead of KNH_ERR_NOT_INITIALISED.
+inline const char* no_params_message(const StageInfo& s) { return s.ch1() ? kCh1NoParams : s.feedback() ? kFeedbackNoParams : nullptr; }
 
 // Which (stage kind, float parameter) pairs can be driven at audio rate (knh_stage_desc.ar_param): the setters restated on
 // the device (voice_stages.hpp, ar_set).

@@ -237,6 +237,10 @@ struct Bank final : knh_bank {
   void* d_delay = nullptr;
   uint32_t delay_stride = 0;        // kRingGranule once there are rings
   uint32_t ring_sink_row = 0;       // the spare ring's first granule
+  // Feedback edges (KNH_STAGE_FLAG_FEEDBACK): a ring of one block per (edge, voice), entries of `rings` behind the delay stages'
+  // (so knh_bank_restart_voices clears them with the rest), edge after edge in stage order and all of one stride -- a device
+  // stage finds edge e's ring of voice v from these two numbers alone (knh_dev::FbRingT).
+  uint32_t fb_row0 = 0, fb_granules = 0;
   std::vector<DelayRings> rings;    // per delay stage, in chain order
   std::vector<int> ring_of_stage;   // [stage] -> its entry of `rings`, -1: no delay stage
   std::vector<uint32_t> delay_len;  // [delay stage (entry of `rings`)][voice]: ring length (samples)
@@ -341,6 +345,8 @@ struct Bank final : knh_bank {
     a.delay_ring = d_delay;
     a.delay_stride = delay_stride;
     a.ring_sink_row = ring_sink_row;
+    a.fb_row0 = fb_row0;
+    a.fb_granules = fb_granules;
     a.buffer = d_buffer;
     a.wavetables = d_wavetables;
     a.input = nullptr;
@@ -683,7 +689,7 @@ struct Bank final : knh_bank {
           for (PoolEntry& e : pool) { e.off = static_cast<uint32_t>(off); off += (static_cast<uint64_t>(e.n_frames) * e.channels + 63ull) & ~63ull; }
         }
       } break;
-      case KNH_STAGE_INPUT: uses_input = true; break;
+      case KNH_STAGE_INPUT: uses_input = uses_input || !S.feedback(); break;  // (a feedback edge's ring comes behind the delay stages': init)
       case KNH_STAGE_ALLPASS_FB_DELAY: case KNH_STAGE_ALLPASS_DELAY: case KNH_STAGE_SAMPLE_DELAY: {
         // the stage's rings: behind the delay stages before it, as far apart as its own longest ring asks
         uint32_t mx = 0;
@@ -809,6 +815,7 @@ struct Bank final : knh_bank {
       } break;
       case KNH_STAGE_SAFETY_LIMITER: break;
       case KNH_STAGE_INPUT: {
+        if (S.feedback()) break;  // a feedback edge: no channel, no state (its ring is found by edge and voice)
         if (!(a[0] >= 0.0) || a[0] >= static_cast<double>(desc.in_channels)) return fail(KNH_ERR_INVALID_ARGUMENT, "KNH_STAGE_INPUT: channel is not below knh_bank_desc.in_channels");
         put(0, static_cast<W>(static_cast<uint32_t>(a[0])));
       } break;
@@ -1053,6 +1060,18 @@ struct Bank final : knh_bank {
         if (rc != KNH_OK) return rc;
       }
     }
+    fb_row0 = fb_granules = 0;
+    for (size_t si = 0; si < stages.size(); ++si) {
+      if (!stages[si].feedback()) continue;
+      // FeedbackSink's buffer: one block (graph.rs:153-155), zero until the first block has gone through
+      const uint64_t base = rings.empty() ? 0u : rings.back().base + static_cast<uint64_t>(nv) * rings.back().stride;
+      const uint32_t own = (static_cast<uint32_t>(bs) + kRingGranule - 1u) / kRingGranule * kRingGranule;
+      if ((base + static_cast<uint64_t>(nv) * own) / kRingGranule >= 0xFFFFFFFFull) return fail(KNH_ERR_INVALID_ARGUMENT, "the delay rings of the bank are too long in sum");
+      if (fb_granules == 0) { fb_row0 = static_cast<uint32_t>(base / kRingGranule); fb_granules = own / kRingGranule; }
+      ring_of_stage[si] = static_cast<int>(rings.size());
+      rings.push_back(DelayRings{static_cast<uint32_t>(si), own, base});
+      delay_len.resize(rings.size() * nv, 0u);
+    }
     // device allocations
     KNH_HIP(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
     KNH_HIP(hipMalloc(&d_state, st.size() * sizeof(W)));
@@ -1242,7 +1261,7 @@ struct Bank final : knh_bank {
         // (the stage's own rings: another delay stage's longer ones are no room for this one's)
         if (len > rings[static_cast<size_t>(ring_of_stage[stage])].stride) return fail(KNH_ERR_OUT_OF_RANGE, "the delay's ring would be longer than the rings allocated at knh_bank_init");
       }
-      if (S.kind == KNH_STAGE_INPUT && (!(a[0] >= 0.0) || a[0] >= static_cast<double>(desc.in_channels)))
+      if (S.kind == KNH_STAGE_INPUT && !S.feedback() && (!(a[0] >= 0.0) || a[0] >= static_cast<double>(desc.in_channels)))
         return fail(KNH_ERR_INVALID_ARGUMENT, "KNH_STAGE_INPUT: channel is not below knh_bank_desc.in_channels");
     }
     for (size_t k = 0; k < count && n_args && keep; ++k)
@@ -1366,7 +1385,7 @@ struct Bank final : knh_bank {
     // little too large -- every parameter entry point comes through here (or through RankBank's copy of these checks).  Ahead of
     // the initialised check on purpose: the chain is known from knh_bank_create on (knaster_hip.h says so)
     if (stage < stages.size() && is_math1_kind(stages[stage].kind)) return fail(KNH_ERR_INVALID_ARGUMENT, "a KNH_STAGE_MATH1_* stage has no parameters");
-    if (stage < stages.size() && stages[stage].ch1()) return fail(KNH_ERR_INVALID_ARGUMENT, kCh1NoParams);  // (the same rule: it is no node)
+    if (stage < stages.size() && no_params_message(stages[stage])) return fail(KNH_ERR_INVALID_ARGUMENT, no_params_message(stages[stage]));  // (the same rule: it is no node)
     if (!initialised) return fail(KNH_ERR_NOT_INITIALISED, "bank not initialised");
     if (voice >= nv) return fail(KNH_ERR_OUT_OF_RANGE, "voice out of range");
     if (stage >= stages.size()) return fail(KNH_ERR_OUT_OF_RANGE, "stage out of range");

@@ -610,6 +610,7 @@ struct VoiceKernelArgs {
   void* delay_ring;                 // the delay stages' rings, per stage [n_voices][that stage's stride] of F, then the spare ring; or null
   u32 delay_stride;                 // the granule rings start on, in samples (Ctx::delay_stride)
   u32 ring_sink_row;                // the spare ring's first granule (Ctx::ring_sink_row)
+  u32 fb_row0, fb_granules;         // feedback edges: the first granule of edge 0's ring of voice 0, granules per ring (Ctx::fb_row0; edge E's rings are [n_voices] of them)
   const void* buffer;               // BufferReader's pool of Buffers (single channel, F; a voice's offset and length are its slots), or null
   const void* wavetables;           // OscWt's pools of Wavetables (every flagged stage's, one allocation of F; a voice's table and entry are its slots), or null
   const void* input;                // the bank node's input channels, [n_blocks][in_channels][block_size] of F, or null
@@ -1102,6 +1103,10 @@ __global__ void __launch_bounds__(WAVES * 64) voice_kernel(VoiceKernelArgs<F> a)
   ctx.delay_ring = a.delay_ring;
   ctx.delay_stride = a.delay_stride;
   ctx.ring_sink_row = a.ring_sink_row;
+  ctx.fb_row0 = a.fb_row0;
+  ctx.fb_granules = a.fb_granules;
+  ctx.fb_voices = a.n_voices;
+  ctx.voice = 0u;
   ctx.buffer = a.buffer;
   ctx.wavetables = a.wavetables;
   ctx.input_block = a.input;
@@ -1119,7 +1124,8 @@ __global__ void __launch_bounds__(WAVES * 64) voice_kernel(VoiceKernelArgs<F> a)
   fl.v = fold_voice_of_lane((u32)lane);
   fl.nv = nv;
   const bool live = fl.v < nv;
-  const u32 voice = live ? v0 + fl.v : v0 + nv - 1;  // idle lanes shadow the last live voice, never store
+  const u32 voice = live ? v0 + fl.v : v0 + nv - 1;  // idle lanes shadow the last live voice: no store of their own to state, rows or flags (a delay's or a feedback edge's ring gets the last voice's samples twice, the same values to the same place)
+  ctx.voice = voice;
 
   ChainT chain;
   chain.load(a.state + voice, a.stride);

@@ -129,6 +129,11 @@ struct Ctx {
   u32 sample_rate;          // ctx.sample_rate(), for setters that run on the device (audio-rate parameters)
   __attribute__((address_space(3))) char* ring_tile;  // this wavefront's RingLines tile in LDS (whole-chain kernels of up to eight wavefronts), or null
   u32 ring_sink_row;        // the spare ring behind the last stage's last voice's (its first granule): where lanes without a voice move their lines
+  // Feedback edges (FbRead / FbWrite): edge E's ring of voice v starts at granule fb_row0 + (E * fb_voices + v) * fb_granules
+  // of the delay allocation and holds one block.  `voice` is the one value here that differs from lane to lane: the voice
+  // whose state the lane holds (a lane past the last voice shadows the last voice and moves the same samples to the same place).
+  u32 fb_row0, fb_granules, fb_voices;
+  u32 voice;
 };
 
 // ---------------------------------------------------------------------------
@@ -2434,6 +2439,87 @@ struct SampleDelayT : StageDefaults {
 };
 typedef SampleDelayT<true> SampleDelay;
 typedef SampleDelayT<false> SampleDelayNoAhead;
+
+// A feedback edge inside the voice -- Graph::connect2_feedback (graph.rs:1220-1254): "the signal data will be delayed by one
+// block".  The edge's ring holds one block per voice and is indexed by the frame's place in its block, which is what every
+// tick is handed (frame0: the kernels count frames from the block's start, whichever part of the block a call processes): no
+// write pointer, no state, nothing an event could address.  FbRead<E> (the FeedbackSource; 'x' in the signature) gives out the
+// sample the same frame of the previous block left there -- zeros after init and after a restart, the host clears the ring --
+// and FbWrite<E> ('y'; the FeedbackSink) puts the tapped signal's sample in its place and passes the signal on.  The host orders
+// the two (build_signature): within a tile, and within a sample of the sample-by-sample path, an edge's read comes before its write.
+// A tile of whole lines moves through the wavefront's RingLines tile like a delay's (read and write position are the same and
+// the tile ends inside the ring: no chunk ever wraps); any other tile goes as 16-byte pieces of the lane's own ring, or sample
+// by sample.
+template <int E, bool WRITE>
+struct FbRingT : StageDefaults {
+  static constexpr int kSlots = 0;
+  static constexpr u32 kMutableMask = 0u;
+  static constexpr bool kUsesSine = false;
+  static constexpr bool kIsEnv = false;
+  static constexpr bool kNeedsBind = false;
+  static constexpr bool kHasSeg = false;
+  static constexpr bool kUsesRing = true;
+  template <typename F> struct Regs {};
+  template <typename F, typename W> static __device__ __forceinline__ void load(Regs<F>&, const W*, long) {}
+  template <typename F, typename W> static __device__ __forceinline__ void store(const Regs<F>&, W*, long) {}
+  static __device__ __forceinline__ u32 row(const Ctx& c) { return c.fb_row0 + ((u32)E * c.fb_voices + c.voice) * c.fb_granules; }
+  template <typename F> static __device__ __forceinline__ F* ring(const Ctx& c) { return reinterpret_cast<F*>(c.delay_ring) + (long)row(c) * c.delay_stride; }
+  template <typename F, bool FMA>
+  static __device__ __forceinline__ F tick(Regs<F>&, F x, const Ctx& c, u32 frame, u32&) {
+    F* const g = ring<F>(c);
+    if constexpr (WRITE) { g[frame] = x; return x; }
+    else return g[frame];
+  }
+  template <typename F, bool FMA, int T>
+  static __device__ __forceinline__ void tick_tile(Regs<F>&, F (&x)[T], const Ctx& c, u32 frame0, u32&) {
+    typedef RingLines<F> RL;
+    if constexpr (T % RL::TS == 0) {
+      if (c.ring_tile != nullptr) {  // (known per kernel)
+        const int lane = (int)(threadIdx.x & 63u);
+        typename RL::Owned own;
+        RL::exchange(c.ring_tile, lane, true, row(c), frame0, frame0, c.fb_granules * c.delay_stride, c, own);
+#pragma unroll
+        for (int s = 0; s < T / RL::TS; ++s) {
+          if constexpr (WRITE) {
+            RL::store(c.ring_tile, lane, own, &x[s * RL::TS], (u32)(s * RL::TS));
+          } else {
+            typename RL::Lines l;
+            RL::load(own, (u32)(s * RL::TS), l);
+            RL::to_samples(c.ring_tile, lane, l, &x[s * RL::TS]);
+          }
+        }
+        return;
+      }
+    }
+    constexpr int VW = 16 / (int)sizeof(F);
+    F* const g = ring<F>(c) + frame0;
+    if constexpr (T % VW == 0) {
+      typedef F Vec __attribute__((ext_vector_type(VW), aligned(sizeof(F))));
+#pragma unroll
+      for (int j = 0; j < T / VW; ++j) {
+        if constexpr (WRITE) {
+          Vec v;
+#pragma unroll
+          for (int k = 0; k < VW; ++k) v[k] = x[j * VW + k];
+          reinterpret_cast<Vec*>(g)[j] = v;
+        } else {
+          const Vec v = reinterpret_cast<const Vec*>(g)[j];
+#pragma unroll
+          for (int k = 0; k < VW; ++k) x[j * VW + k] = v[k];
+        }
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < T; ++j) {
+        if constexpr (WRITE) g[j] = x[j];
+        else x[j] = g[j];
+      }
+    }
+  }
+  template <typename F> static __device__ __forceinline__ void on_event(Regs<F>&, u32, u32, u64, u32) {}
+};
+template <int E> using FbRead = FbRingT<E, false>;
+template <int E> using FbWrite = FbRingT<E, true>;
 
 // AllpassDelay -- delay.rs:93-206: out = allpass(buffer[read]); read += 1; buffer[write] = x; write += 1 (both modulo the
 // ring), with a first-order allpass interpolator (delay.rs:53-90: out = coeff * (in - prev_out) + prev_in) for the

@@ -333,6 +333,9 @@ struct NodeRec {
   int in0 = -1, in1 = -1;   // input edges (node ids)
   int in0_ch = 0, in1_ch = 0;  // ... and the output channel of that node the edge starts at (a two-channel BufferReader's 1)
   int link_source = -1, link_param = -1;  // audio-rate parameter edge (graph_edit.rs:735-754)
+  // >= 0: the node is the FeedbackSource of a feedback edge (to_feedback, graph_edit.rs:311-359): its signal is the output of
+  // node fb_tap one block late.  It stands for the edge's FeedbackSink too (a KNH_STAGE_FLAG_FEEDBACK stage, knaster_hip.h).
+  int fb_tap = -1;
   // where the node ended up after commit
   int bank = -1, voice = -1, stage = -1;
   // a Constant that scales several channels (`play * amp.out([0, 0])`) stands behind a MUL_CONST stage per channel: the
@@ -358,6 +361,9 @@ struct ChainPlan {
   // two different signals on the two graph outputs (`(l | r).to_graph_out()`): the stages whose nodes they are, -1: the
   // voice's one signal, the last stage's, on every output (knh_bank_connect_outputs)
   int out_stage[2] = {-1, -1};
+  // feedback edges: (the KNH_STAGE_FLAG_FEEDBACK stage, the node it taps) -- the stage's `input` is named once the whole voice
+  // is traced: the tapped node may come later in the list than the edge's source, that is what the edge is for
+  std::vector<std::pair<int, int>> feedback;
   std::string signature() const {
     std::string s;
     if (out_stage[0] >= 0) s += "out" + std::to_string(out_stage[0]) + "," + std::to_string(out_stage[1]) + ";";
@@ -398,6 +404,13 @@ class Sig {  // SH / DH of graph_edit.rs:266-277: one or more output channels of
     return Sig(g_, n, ch);
   }
   void to_graph_out() const { g_->to_graph_out(*this); }  // additive (graph_edit.rs:363-369)
+  // a.to_feedback(b) / a.to_feedback_replace(b) (graph_edit.rs:311-359, 499-547; Graph::connect2_feedback, graph.rs:1220-1254):
+  // this signal reaches b's input ONE BLOCK LATE ("breaking potential cycles in the graph"), zeros in the first block.  b is a
+  // pushed UGen with one input, or a `signal (op) number` node (its signal operand).  to_feedback adds to what the input
+  // already has -- a MathUGen Add of the two, as in the reference (graph.rs:800-814) -- to_feedback_replace takes its place.
+  // Returns b, like `to`.  The edge becomes a KNH_STAGE_FLAG_FEEDBACK stage of the voice (knaster_hip.h).
+  Sig to_feedback(const Sig& sink) const { return g_->to_feedback(*this, sink, true); }
+  Sig to_feedback_replace(const Sig& sink) const { return g_->to_feedback(*this, sink, false); }
   // (l | r): the channels of `l`, then those of `r`, as one handle (Stack, graph_edit.rs:1219-1368)
   Sig operator|(const Sig& o) const {
     std::vector<int> n(nodes_), ch(chans_);
@@ -590,6 +603,11 @@ class Graph {
       return finish();
     }
     const UGenSpec& s = n.spec;
+    if (n.fb_tap >= 0) {  // the source of a feedback edge: a source stage; the tapped node is NOT walked from here (it may read this one)
+      p.feedback.emplace_back(static_cast<int>(p.stages.size()), n.fb_tap);
+      push_stage(p, KNH_STAGE_INPUT, KNH_STAGE_FLAG_FEEDBACK, 0, -1, {});
+      return finish();
+    }
     if (s.is_constant) throw GraphError("a constant must be an operand of * + - /");
     if (s.is_env && n.in0 >= 0) throw GraphError("an envelope has no inputs: it is an operand of `*` or a signal of its own, not a processor of one");
     if (s.kind == KNH_STAGE_GALACTIC) {
@@ -708,6 +726,16 @@ class Graph {
         const uint16_t right = trace_channel(conn[1].first, conn[1].second, v.plan, v.nodes, done);
         v.plan.out_stage[0] = left - 1;  // (a signal's name is 1 + the stage whose output it is)
         v.plan.out_stage[1] = right - 1;
+      }
+      // feedback edges: every tapped node has a stage by now, or gets its stages here, behind the output's (a node that only
+      // an edge reads: graph_tests.rs:221-254) -- which may find further edges
+      for (size_t k = 0; k < v.plan.feedback.size(); ++k) {
+        const std::pair<int, int> edge = v.plan.feedback[k];
+        v.plan.stages[static_cast<size_t>(edge.first)].input = trace(edge.second, v.plan, v.nodes, done);
+      }
+      if (same && !pan && v.plan.stages.size() != left) {  // the voice's signal is no longer the last stage's: say which it is
+        if (outputs_ != 2) throw GraphError("to_feedback(): a node that only a feedback edge reads needs a stereo graph here (its stages come behind the output's)");
+        v.plan.out_stage[0] = v.plan.out_stage[1] = left - 1;
       }
       voices.push_back(std::move(v));
     }
@@ -904,6 +932,38 @@ class GraphEdit {
       return sink;
     }
     n.in0 = src.node();
+    return sink;
+  }
+  Sig<F> to_feedback(const Sig<F>& src, const Sig<F>& sink, bool additive) {
+    const int sink_id = sink.node();
+    {
+      const NodeRec& n = graph_->nodes_[static_cast<size_t>(sink_id)];
+      const bool ugen = n.type == NodeRec::UGEN && n.spec.inputs == 1 && !n.spec.is_constant && !n.spec.is_env && n.fb_tap < 0;
+      const bool op_const = n.type == NodeRec::MATH && n.math_kind != 0xFFFF;
+      if (!ugen && !op_const) throw GraphError("to_feedback(): the sink is a pushed UGen with one input or a `signal (op) number` node");
+      if (src.channels()[0] != 0) throw GraphError("to_feedback(): the edge starts at a node's first output (put the other channel through `* 1.0`)");
+    }
+    NodeRec fb;  // FeedbackSink + FeedbackSource (graph.rs:882-909): one node here, one KNH_STAGE_FLAG_FEEDBACK stage
+    fb.type = NodeRec::UGEN;
+    fb.spec = UGenSpec(KNH_STAGE_INPUT, {});
+    fb.fb_tap = src.node();
+    graph_->nodes_.push_back(fb);
+    int in = static_cast<int>(graph_->nodes_.size()) - 1;
+    const int old = graph_->nodes_[static_cast<size_t>(sink_id)].in0, old_ch = graph_->nodes_[static_cast<size_t>(sink_id)].in0_ch;
+    if (additive && old >= 0) {  // the input has an edge already: an Add node of the two (graph.rs:800-814)
+      NodeRec m;
+      m.type = NodeRec::MATH;
+      m.math_kind = 0xFFFF;
+      m.math2_kind = KNH_STAGE_MATH_ADD;
+      m.in0 = old;
+      m.in0_ch = old_ch;
+      m.in1 = in;
+      graph_->nodes_.push_back(m);
+      in = static_cast<int>(graph_->nodes_.size()) - 1;
+    }
+    NodeRec& n = graph_->nodes_[static_cast<size_t>(sink_id)];
+    n.in0 = in;
+    n.in0_ch = 0;
     return sink;
   }
   void to_graph_out(const Sig<F>& s) {
